@@ -11,8 +11,16 @@ with the reference's calls, kept on the device); the per-call redraw is reported
 under models.din_per_call (eager, it has host work).  Multi-GPU is replicas (the forward has
 no exchange step): every rank runs its own batch, `value` = all ranks' samples / max time.
 
-Extra keys: `models` (N=1, rank 0) times DCN@4096, DeepFM configs[1] and BST configs[3] the
-same way; `roofline` prices the dominant kernel with HIP events around its own launches on the
+A plain run does only what the headline needs: it builds the model and the seeded inputs, runs
+`--warmup` prepared launches, times `--steps` of them (`ms_per_step` = that window / steps) and
+prints the line.  `--dump-outputs DIR` also writes what the last timed step computed — the
+(prob, logit, l2_reg) a caller of the forward receives — as DIR/prob.npy, logit.npy, l2_reg.npy
+(float32); model, weights and inputs are seeded, so two builds can be compared output for output.
+Every other leg below runs only with `--full`.
+
+Extra keys (`--full`): `config.graph_replay_ms_per_step` times the hipGraph replay of the same
+forward beside the prepared launch; `models` (N=1, rank 0) times DCN@4096, DeepFM configs[1]
+and BST configs[3] the same way; `roofline` prices the dominant kernel with HIP events around its own launches on the
 stream it runs on; `cpu_baseline` times the oracle (CPU restatement, per-call draws included)
 on a bounded sample of the same workload on this host; `loader` times the host input path
 (raw ID strings -> bucketed batch on the GPU -> forward, rankops.loader) against the reference's
@@ -55,10 +63,17 @@ DCN_FLOP = 379_236
 ZIPF_A = 1.1  # Zipf(1.1) index variant for cache sensitivity
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too (graph replay beside the prepared launch, "
+                         "roofline, the other models, loader, training steps, eval metrics, sharded DeepFM, CPU "
+                         "baselines); without it only the headline's steps are set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed (prob, logit, l2_reg) as "
+                         "DIR/<name>.npy in float32")
     ap.add_argument("--din-streams", type=int, default=1,
                     help="DIN headline: batches in flight on as many HIP streams (default 1; "
                          "tools/din_streams.py measures 2-4)")
@@ -73,9 +88,16 @@ def parse():
                                         "din_per_call,din_zipf,dcn_eager,din_eager,deepfm_eager,bst_eager")
     ap.add_argument("--no-loader", action="store_true", help="skip the host input-path (bucketing) leg")
     ap.add_argument("--no-train", action="store_true", help="skip the training-step legs")
-    ap.add_argument("--details", default=DEFAULT_DETAILS,
-                    help="file for the full result (every leg); the stdout line is the compact summary")
-    return ap.parse_args()
+    ap.add_argument("--details", default=None,
+                    help="file for the full result (every leg); the stdout line is the compact summary "
+                         "(default: DEFAULT_DETAILS with --full, no file without it)")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: every leg beside the headline is skipped
+        args.no_extras = args.no_cpu = args.no_sharded = args.no_model_curve = True
+        args.no_loader = args.no_train = True
+    elif args.details is None:
+        args.details = DEFAULT_DETAILS
+    return args
 
 
 def dist_setup(args):
@@ -941,7 +963,7 @@ def compact_result(full: dict, details_path: str = None) -> dict:
     its legs reduced to {value, cores, gpu_over_cpu}, and one-line summaries of the extra legs; the
     full result (every leg's detail) is in `details_path` (bench_details.json)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-            "vs_baseline", "dtype", "data", "config", "build")
+            "vs_baseline", "dtype", "data", "config", "build", "outputs")
     out = {k: full[k] for k in keep if k in full}
     r = full.get("roofline")
     if r:
@@ -994,9 +1016,37 @@ def emit(result: dict, details_path: str):
     print(line, flush=True)
 
 
+# ------------------------------------------------------------------ --dump-outputs
+
+OUTPUT_NAMES = ("prob", "logit", "l2_reg")  # DIN.forward's return (din.py:294-323), the headline's outputs
+DUMP_MAX_BYTES = 64 << 20  # all arrays of one dump together
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(dirpath, names, outputs):
+    """Writes each output as `dirpath`/<name>.npy in float32 and returns {name: shape} of what was
+    written.  An array past its share of DUMP_MAX_BYTES is cut to a fixed sample of its rows (the
+    same seeded, sorted row choice on every run)."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(names))
+    written = {}
+    for name, t in zip(names, outputs):
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        a = np.asarray(a, dtype=np.float32, order="C")
+        if a.nbytes > share:
+            rows = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return {"dir": dirpath, "arrays": written}
+
+
 # ------------------------------------------------------------------ main
 
-def bench_one(name, batch, steps, warmup, world, rank, zipf=None, streams=1):
+def bench_one(name, batch, steps, warmup, world, rank, zipf=None, streams=1, graph_beside=True, last_outputs=None):
+    """Times `name`.  `graph_beside=False` (DIN, a plain run) leaves out the hipGraph capture and
+    its replay timing beside the prepared launch.  `last_outputs` (DIN): a list that receives the
+    output tensors of the last timed step."""
     model, inp, fn, cfg, model_name = workload(name, batch, rank, zipf)
     if name.endswith("per_call") or name.endswith("_eager"):
         # eager: one Python forward per step, as the reference's evaluate() / predict loops call
@@ -1009,15 +1059,21 @@ def bench_one(name, batch, steps, warmup, world, rank, zipf=None, streams=1):
         mode = "eager, per-call H2 draws" if name.endswith("per_call") else "eager (no graph), frozen H2"
         return {"samples_per_s": round(batch * n / t, 1), "mode": mode,
                 "ms_per_step": round(1e3 * t / n, 4)}, model, inp, cfg, model_name
-    g, _ = graph_of(fn)
+    g = None
+    if graph_beside or model_name != "din":
+        g, _ = graph_of(fn)
     res = {}
+    runs = None
     if model_name == "din":
         # the whole DIN forward is one kernel: a prepared launch (DIN.prepare ->
-        # rk_din_forward_plan) replays it without a graph's per-replay gap; the graph replay of the
-        # same forward is timed too and reported beside it
-        run = model.prepare(inp["dense"], inp["category"], inp["sequence"], inp["target"])
-        tg = max_over_ranks(world, time_replays(g.replay, steps, warmup, world))
-        res["graph_replay_ms_per_step"] = round(1e3 * tg / steps, 4)
+        # rk_din_forward_plan) replays it without a graph's per-replay gap; with `graph_beside`
+        # the graph replay of the same forward is timed too and reported beside it
+        with torch.no_grad():
+            run = model.prepare(inp["dense"], inp["category"], inp["sequence"], inp["target"])
+        runs = [run]
+        if g is not None:
+            tg = max_over_ranks(world, time_replays(g.replay, steps, warmup, world))
+            res["graph_replay_ms_per_step"] = round(1e3 * tg / steps, 4)
         res["step"] = "prepared single-kernel launch (rk_din_plan_launch)"
         if streams > 1:
             # S batches in flight: S prepared launches, each with its own inputs (seeded apart),
@@ -1082,7 +1138,14 @@ def bench_one(name, batch, steps, warmup, world, rank, zipf=None, streams=1):
         res["step"] = "prepared launch (rk_bst_small_forward)"
     else:
         run = g.replay
+    live = None
+    if last_outputs is not None and runs is not None:
+        # each prepared launch's own output tensors, which every later launch rewrites in place
+        live = [r() for r in runs]
+        torch.cuda.synchronize()
     t = time_replays(run, steps, warmup, world)
+    if live is not None:  # time_replays ends synchronized: the tensors hold the last timed step's results
+        last_outputs.extend(live[(cnt[0] - 1) % streams] if streams > 1 else live[0])
     t = max_over_ranks(world, t)
     res.update({"samples_per_s": round(world * batch * steps / t, 1), "ms_per_step": round(1e3 * t / steps, 4)})
     if zipf is not None:
@@ -1090,15 +1153,18 @@ def bench_one(name, batch, steps, warmup, world, rank, zipf=None, streams=1):
     return res, model, inp, cfg, model_name
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     world, rank, local = dist_setup(args)
     import rankops
     rankops.load_library()
     torch.backends.cuda.matmul.allow_tf32 = False
 
+    last = [] if args.dump_outputs and rank == 0 else None
     head, model, inp, cfg, model_name = bench_one("din", args.batch, args.steps, args.warmup, world, rank,
-                                                  streams=args.din_streams)
+                                                  streams=args.din_streams, graph_beside=args.full,
+                                                  last_outputs=last)
+    dumped = dump_outputs(args.dump_outputs, OUTPUT_NAMES, last) if last is not None else None
     result = {
         "metric": METRIC,
         "value": head["samples_per_s"],
@@ -1127,7 +1193,9 @@ def main():
     result["build"] = {"lib_src_hash": bi.get("src"), "tree_src_hash": bi.get("tree_src"), "arch": bi.get("arch"),
                        "extra_flags": bi.get("extra"),
                        "lib_matches_tree": bi.get("tree_src") is not None and bi.get("src") == bi.get("tree_src")}
-    if rank == 0:
+    if dumped:
+        result["outputs"] = dumped
+    if rank == 0 and args.full:
         # the kernel the headline times: a prepared plan's launch (rk_din_plan_launch, host cost a
         # few us against the ~44-us kernel, so back-to-back launches keep the GPU busy)
         launch = model.prepare(inp["dense"], inp["category"], inp["sequence"], inp["target"]).plan.launch

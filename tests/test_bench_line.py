@@ -69,6 +69,48 @@ def test_compact_line_falls_back_when_extras_grow(tmp_path):
     assert "models" not in d and d["roofline"]["frac"] == full["roofline"]["frac"]
 
 
+LEG_SWITCHES = ("no_extras", "no_cpu", "no_sharded", "no_model_curve", "no_loader", "no_train")
+
+
+def test_plain_run_times_the_headline_only():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.details) == (7, 2, False, None, None)
+    assert all(getattr(a, k) for k in LEG_SWITCHES)  # every leg beside the headline is off
+
+
+def test_full_run_keeps_every_leg_and_its_switches():
+    a = bench.parse(["--full"])
+    assert a.full and not any(getattr(a, k) for k in LEG_SWITCHES)
+    assert a.details == bench.DEFAULT_DETAILS
+    b = bench.parse(["--full", "--no-cpu", "--details", "x.json", "--dump-outputs", "out"])
+    assert b.no_cpu and not b.no_extras and b.details == "x.json" and b.dump_outputs == "out"
+
+
+def test_dump_outputs_float32_arrays(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    prob = torch.rand(300, 1, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
+    d = str(tmp_path / "dump")
+    info = bench.dump_outputs(d, ("prob", "l2_reg"), (prob, 0.25))
+    assert info == {"dir": d, "arrays": {"prob": [300, 1], "l2_reg": []}}
+    got = np.load(os.path.join(d, "prob.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, prob.numpy().astype(np.float32))
+    l2 = np.load(os.path.join(d, "l2_reg.npy"))
+    assert l2.dtype == np.float32 and l2.shape == () and l2 == np.float32(0.25)
+    # past the size bound: the same sorted row sample on every run, within the bound
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 100 * 4)
+    rows = []
+    for _ in range(2):
+        info = bench.dump_outputs(d, ("prob", "l2_reg"), (prob, 0.25))
+        assert info["arrays"]["prob"] == [100, 1]
+        rows.append(np.load(os.path.join(d, "prob.npy")))
+    assert np.array_equal(rows[0], rows[1])
+    full = prob.numpy().astype(np.float32)[:, 0]
+    pos = np.searchsorted(np.sort(full), rows[0][:, 0])  # every sampled value is one of the rows
+    assert np.array_equal(np.sort(full)[pos], rows[0][:, 0])
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 2 * 100 * 4 + 2 * 128
+
+
 def test_counter_staleness_tags():
     bench._LIB_SRC = "abc"
     try:
