@@ -150,6 +150,16 @@ SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p],
     ),
+    "rk_dien_interest": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32,
+         c_int32, c_int32] + [c_void_p] * 9 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
+    ),
+    "rk_dien_interest_dense": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32]
+        + [c_void_p] * 9 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
+    ),
     "rk_dice_forward": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
     "rk_bst_attention": (

@@ -271,6 +271,34 @@ def din_attention_dense(query, keys, keys_length, weights, use_softmax, out):
           "rk_din_attention_dense")
 
 
+DIEN_CELLS = {"AGRU": 0, "AUGRU": 1}
+
+
+def dien_interest(query_ptr, ld_query, key_table, seq, seq_len, T, H, nh, cell_type, weights, out_ptr, ld_out,
+                  att, batch, device):
+    """rk_dien_interest: GRU + attention + AGRU/AUGRU over key_table[seq] in one launch; query / out
+    are strided pointers (they may lie in one row buffer), weights = (Wg, bg, Wc, bc, A, Vg, vg, Vc,
+    vc), att an optional [batch, T] output of the attention weights."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    check(lib.rk_dien_interest(query_ptr, ld_query, ptr(key_table), key_table.shape[0], key_table.stride(0),
+                               ptr(seq), seq.stride(0), T, ptr(seq_len), batch, H, nh, cell_type,
+                               *[ptr(w) for w in weights], out_ptr, ld_out, ptr(att),
+                               att.stride(0) if att is not None else 0, _lib.raw_stream(device)),
+          "rk_dien_interest")
+
+
+def dien_interest_dense(query, keys, keys_length, nh, cell_type, weights, out, att):
+    """rk_dien_interest_dense: keys [B, T, H] (rows 16-B aligned), query [B, H], out [B, nh]."""
+    lib = _lib.load()
+    _lib.ensure_device(keys.device)
+    B, T, H = keys.shape
+    check(lib.rk_dien_interest_dense(ptr(query), query.stride(0), ptr(keys), keys.stride(0), keys.stride(1), T,
+                                     ptr(keys_length), B, H, nh, cell_type, *[ptr(w) for w in weights], ptr(out),
+                                     out.stride(0), ptr(att), att.stride(0) if att is not None else 0,
+                                     _lib.stream_of(keys)), "rk_dien_interest_dense")
+
+
 def dice_forward(x, scale, shift, alpha, y):
     lib = _lib.load()
     check(lib.rk_dice_forward(ptr(x), x.stride(0), x.shape[0], x.shape[1], ptr(scale), ptr(shift), ptr(alpha),

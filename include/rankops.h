@@ -25,6 +25,9 @@
  *                      bst.py:59-64,73-75,86-90,203-214,238-247
  *   rk_din_attention   din_attention() with the history gathered from the table  din.py:42-84,300-305
  *   rk_din_attention_dense  din_attention(query, keys[B,T,H], keys_length, is_softmax)  din.py:42-84
+ *   rk_dien_interest   DIEN's GRU + attention + AGRU/AUGRU with the history gathered from the table
+ *                      DIEN/dien.py:198-229, custom_grucell.py:19-167, rnn.py:201-219
+ *   rk_dien_interest_dense  the same over a dense history tensor keys[B,T,H]
  *   rk_dice_forward    Dice.forward() in eval (BatchNorm running statistics)           din.py:26-36
  *   rk_row_l2norm_mean DIN mini-batch-aware l2 term          din.py:318-322
  *   rk_afm_forward     AFM.forward()                         afm.py:92-119
@@ -239,6 +242,39 @@ int rk_din_attention_dense(const float* query, int64_t ld_query, const float* ke
                            int32_t H, const float* w1, const float* b1, const float* w2,
                            const float* b2, const float* w3, const float* b3, int32_t use_softmax,
                            float* out, int64_t ld_out, void* stream);
+
+/* DIEN interest extractor + interest evolution, eval forward, one launch (DIEN/dien.py:198-229):
+ *   h_t   = GRUCell(x_t, h_{t-1}), x_t = key_table[seq[b, t]], h_{-1} = 0  (TF GRUCell: [r|u] =
+ *           sigmoid([x, h] Wg^T + bg), c = tanh([x, r*h] Wc^T + bc), h_t = u*h + (1-u)*c)
+ *   a     = softmax over all T positions of s_t = h_t . (A query[b]), s_t = -2^32+1 for t >= seq_len[b]
+ *   s_t   = AGRU (cell_type 0: (1-a_t)*s + a_t*c) or AUGRU (cell_type 1: u' = (1-a_t)*u,
+ *           u'*s + (1-u')*c) over the inputs h_t with weights Vg / Vc, t < seq_len[b] only
+ *   out[b, 0:nh] = s after step seq_len[b]-1 (zeros when seq_len[b] == 0);
+ *   att_out[b, 0:T] = a when att_out != NULL (uniform 1/T when seq_len[b] == 0).
+ * Weights, row-major: Wg [2nh, H+nh] (r rows first, then u), bg [2nh], Wc [nh, H+nh], bc [nh],
+ * A [nh, H], Vg [2nh, 2nh], vg [2nh], Vc [nh, 2nh], vc [nh].  query row b at query + b*ld_query and
+ * out row b at out + b*ld_out may lie in one row buffer (the query is read before out is written).
+ * seq_len is clamped to [0, T]; ids at t >= seq_len[b] are never read; an out-of-range id at
+ * t < seq_len[b] reads a zero row and raises RK_FLAG_INDEX_OOB.  Table rows 16-B aligned.
+ * Envelope: H in {8,16,32}, nh in {8,16}, 1 <= T <= 256 (else RK_ERR_UNSUPPORTED).
+ * Deterministic: no atomics, two launches on the same inputs are bit-equal.                     */
+int rk_dien_interest(const float* query, int64_t ld_query, const float* key_table,
+                     int64_t key_rows, int64_t ld_key, const int64_t* seq, int64_t ld_seq,
+                     int32_t T, const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                     int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                     const float* bc, const float* A, const float* Vg, const float* vg,
+                     const float* Vc, const float* vc, float* out, int64_t ld_out, float* att_out,
+                     int64_t ld_att, void* stream);
+
+/* rk_dien_interest with a dense history tensor: key row t of sample b at
+ * keys + b * ld_keys_b + t * ld_keys_t (16-B aligned rows); rows at t >= keys_length[b] are never
+ * read.  Bit-equal to rk_dien_interest on the same data.                                        */
+int rk_dien_interest_dense(const float* query, int64_t ld_query, const float* keys, int64_t ld_keys_b,
+                           int64_t ld_keys_t, int32_t T, const int64_t* keys_length, int64_t batch,
+                           int32_t H, int32_t nh, int32_t cell_type, const float* Wg, const float* bg,
+                           const float* Wc, const float* bc, const float* A, const float* Vg,
+                           const float* vg, const float* Vc, const float* vc, float* out,
+                           int64_t ld_out, float* att_out, int64_t ld_att, void* stream);
 
 /* Dice (din.py:26-36) in eval: p = sigmoid(x * bn_scale + bn_shift) with the BatchNorm folded
  * by rk_bn_fold, y = alpha * (1 - p) * x + p * x;  x, y: [rows, n].                          */
