@@ -18,7 +18,12 @@
 //   * the attention output goes into the LDS row; the row's l2 norm (din.py:318-322) is taken.
 //  Phase B: the fcn tail + output layer + sigmoid over the 16 LDS rows (mlp_stream.h for the
 //  compiled [512, 256, 128] plan, mlp_core.h otherwise).
-// The l2 term is finished by a one-wave reduction over the per-workgroup partial sums.
+// The l2 term is finished by a one-wave reduction over the per-workgroup partial sums: the hand-off
+// (din_l2_handoff) runs in an idle wave beside the streamed phase B's last layer, after the generic
+// phase B otherwise.
+// Staging order: column map, segment descriptors and lengths are loaded first; the packed attention
+// image (or the split formed from w1..w3) goes through registers into LDS before the first barrier,
+// beside them (contiguous launches: behind the row gather).
 #include <cstdlib>
 #include <new>
 
@@ -84,22 +89,30 @@ struct DinLds {
 
 #ifdef RK_DIN_PHASES  // timing build only (tools/din_phases.py): per-workgroup wall-clock marks
 constexpr int kDinPhaseWG = 1024;
+constexpr int kDinMarks = 9;
 // entry, staged, phase A done, phase B done, wave 0 assigned, image copied, classes counted,
-// wave 0's row and first keys loaded (tid 0)
-__device__ unsigned long long g_din_ts[kDinPhaseWG][8];
+// wave 0's row and first keys loaded (tid 0), l2 hand-off done (lane 0 of the wave that ran it; 0: no
+// hand-off in this launch)
+__device__ unsigned long long g_din_ts[kDinPhaseWG][kDinMarks];
 __device__ unsigned long long g_din_wave[kDinPhaseWG][16];    // per-wave phase-A cycles (clock64)
 // marks are kept in LDS while the kernel runs (a global store mid-kernel joins the vmcnt queue
 // every later wait drains) and written out by din_marks_flush() at the end
-__shared__ unsigned long long s_din_ts[8];
+__shared__ unsigned long long s_din_ts[kDinMarks];
 __shared__ unsigned long long s_din_wave[16];
 #define DIN_TS(i)                                \
   do {                                           \
     if (tid == 0) s_din_ts[i] = wall_clock64();  \
   } while (0)
+// the entry mark; the other marks start at 0 (threads of wave 0, in step with tid 0: a mark that the
+// launch does not set reads 0)
+#define DIN_TS_ENTRY()                                              \
+  do {                                                              \
+    if (tid < kDinMarks) s_din_ts[tid] = tid ? 0 : wall_clock64();  \
+  } while (0)
 __device__ __forceinline__ void din_marks_flush(int tid) {
   __syncthreads();
   if (blockIdx.x < kDinPhaseWG) {
-    if (tid < 8) g_din_ts[blockIdx.x][tid] = s_din_ts[tid];
+    if (tid < kDinMarks) g_din_ts[blockIdx.x][tid] = s_din_ts[tid];
     if (tid < 16) g_din_wave[blockIdx.x][tid] = s_din_wave[tid];
   }
 }
@@ -107,6 +120,7 @@ __device__ __forceinline__ void din_marks_flush(int tid) {
 #define DIN_TS(i) \
   do {            \
   } while (0)
+#define DIN_TS_ENTRY() DIN_TS(0)
 #endif
 
 // Balanced assignment (NIT > 0).  The attention cost of a sample is its tile count, and with one
@@ -149,13 +163,79 @@ constexpr int din_pre_chunks() {
 }
 // balanced launches gather each wave's row inside phase A: the waves count their rows in here
 static __shared__ unsigned s_din_rows_ready;
+// The l2 hand-off: the last workgroup to publish its partial finishes the mean.  By atomic
+// read-modify-writes only (round 6): one lane per workgroup publishes its
+// partial with an agent-scope atomic exchange and waits for its return (the exchange is then
+// performed at the location's coherence point), then adds to ONE counter (agent-scope atomic); the
+// workgroup whose add returns n-1 reads every partial with an atomic fetch-add of 0.  Every access
+// of the hand-off is an agent-scope RMW on a single location — coherent across the XCDs (the RMWs
+// of one location are totally ordered at its coherence point) — and the order across locations is
+// by completion: a partial's exchange has returned before its workgroup's add is issued, and the
+// reader issues its partial RMWs after its own add returned n-1.  That is not a C++ happens-before
+// (which would take a release / acquire pair: buffer_wbl2 / buffer_inv, 1.7-3.5 us each on the
+// critical path), but unlike rounds 3-5's sc1 plain stores and loads it does not depend on how a
+// cache treats non-atomic accesses.  The partials are non-negative sums of norms, so adding 0
+// returns them unchanged.  tests/test_gpu_din_plan.py and tests/test_gpu_din_staging.py check l2
+// over repeated launches.
+// Called by the 64 lanes of one wave, after a workgroup barrier that follows every wave's store of
+// its norm into norms[0..16).
+__device__ __forceinline__ void din_l2_handoff(float* l2_part, unsigned* l2_count, float* l2_out, float l2_scale,
+                                               int64_t batch, const float* norms, int lane) {
+  unsigned prev = 0;
+  if (lane == 0) {
+    float t = 0.f;
+    for (int w = 0; w < kMlpRows; ++w) t += norms[w];
+    const float old = __hip_atomic_exchange(l2_part + blockIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the counter's add waits for the exchange to return (a use of its result orders it after)
+    unsigned one = 1u;
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(one) : "v"(old) : "memory");
+    prev = __hip_atomic_fetch_add(l2_count, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  prev = __builtin_amdgcn_readfirstlane(prev);
+  if (prev == gridDim.x - 1) {
+    float t = 0.f;
+    for (int i = lane; i < (int)gridDim.x; i += 64)
+      t += __hip_atomic_fetch_add(l2_part + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = wave_sum(t);  // the order of row_l2norm_final_kernel (embedding.hip)
+    if (lane == 0) {
+      l2_out[0] = l2_scale * (t / (float)batch);
+      __hip_atomic_store(l2_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+#ifdef RK_DIN_PHASES
+  if (lane == 0) s_din_ts[8] = wall_clock64();
+#endif
+}
+
+// What the hand-off needs of the kernel's arguments, left in LDS by the kernel before its first
+// barrier: the stage below has no runtime members (they would be read back from scratch behind the
+// weight ring).
+struct DinL2Args {
+  float* part;
+  unsigned* count;
+  float* out;
+  float scale;
+  int64_t batch;
+};
+static __shared__ DinL2Args s_din_l2;
+
+// The DIN stage of the streamed phase B (plan P).
 // WAIT: balanced launches only (contiguous ones stage every row before the first barrier); a
 // compile-time flag — a runtime member would be read back from scratch behind the weight ring
 // DMA: the last four waves may have copied the epilogue image into LDS by LDS-DMA after their
 // phase A: the copies retire before the barrier that opens phase B (loads
 // retire in order; exactly the RK_STREAM_RING ring loads were issued after them).
-template <bool WAIT, bool DMA>
+// side(): the l2 hand-off beside phase B's last layer instead of after the head.  That layer is
+// narrower than 16 tiles and leaves the last wave without one; naming it the side layer makes
+// mlp_stream.h run side() in the idle waves when the layer opens and drop the layer's lockstep
+// barrier, so the last wave can sit on its atomics' returns (two dependent round trips, a third in
+// the reader) with nobody waiting for it before the barrier that closes the layer.  The norms were
+// ordered before this by the barrier that opened phase B.
+template <class P, int H, bool WAIT, bool DMA>
 struct DinRowsReady {
+  static constexpr int kSideLayer = P::NL - 1;
+  static_assert(P::NL >= 2 && P::nt(P::NL - 1) < kMlpWaves && P::tpw(P::NL - 1, kMlpWaves - 1) == 0,
+                "the side layer leaves the last wave without a tile");
   __device__ void issue() const {}
   __device__ void operator()() const {
     if constexpr (DMA) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RK_STREAM_RING) : "memory");
@@ -166,7 +246,13 @@ struct DinRowsReady {
       asm volatile("" ::: "memory");  // the rows are read after the count
     }
   }
-  __device__ void side() const {}
+  __device__ void side() const {
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) != kMlpWaves - 1) return;
+    const DinL2Args l2 = s_din_l2;
+    if (!l2.part) return;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    din_l2_handoff(l2.part, l2.count, l2.out, l2.scale, l2.batch, sm + DinLds<H>::NORM, (int)threadIdx.x & 63);
+  }
 };
 
 // P: the compiled layer plan of phase B (mlp_stream.h), or void for the generic mlp_rows.
@@ -186,7 +272,7 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l32 = lane & 31, half = lane >> 5, hk = 4 * half;
-  DIN_TS(0);
+  DIN_TS_ENTRY();
 
   // ---- the column map and the row segments' descriptors, issued first: with contiguous samples
   // (NIT == 0) they are in LDS one bare barrier later, and the feature-row gather starts while the
@@ -366,6 +452,9 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
   }
   DIN_TS(6);
   if (KS > 0 && tid == 0) s_din_rows_ready = 0u;
+  if constexpr (!std::is_void_v<P>) {  // the stage's hand-off arguments (DinRowsReady::side)
+    if (tid == 0) s_din_l2 = DinL2Args{a.l2_part, a.l2_count, a.l2_out, a.l2_scale, a.batch};
+  }
   __syncthreads();
   DIN_TS(1);
 #ifdef RK_DIN_PHASES
@@ -687,46 +776,14 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
              NIT > 0 ? s_rows : nullptr);
   else
     mlp_stream_rows<P, kEpiLdsCaller>(a.L, buf0, a.ld0, buf1, a.ld1, sm + a.epi_off, m0, rows, a.head, tid,
-                                      PreChunks<KS, DinRowsReady<(NIT > 0 && KS > 0), true>>{}, nullptr,
+                                      PreChunks<KS, DinRowsReady<P, H, (NIT > 0 && KS > 0), true>>{}, nullptr,
                                       NIT > 0 ? s_rows : nullptr);
   DIN_TS(3);
-  // l2 partials: the last workgroup to publish its partial finishes the mean.  Hand-off by atomic
-  // read-modify-writes only (round 6): one lane per workgroup publishes its
-  // partial with an agent-scope atomic exchange and waits for its return (the exchange is then
-  // performed at the location's coherence point), then adds to ONE counter (agent-scope atomic); the
-  // workgroup whose add returns n-1 reads every partial with an atomic fetch-add of 0.  Every access
-  // of the hand-off is an agent-scope RMW on a single location — coherent across the XCDs (the RMWs
-  // of one location are totally ordered at its coherence point) — and the order across locations is
-  // by completion: a partial's exchange has returned before its workgroup's add is issued, and the
-  // reader issues its partial RMWs after its own add returned n-1.  That is not a C++ happens-before
-  // (which would take a release / acquire pair: buffer_wbl2 / buffer_inv, 1.7-3.5 us each on the
-  // critical path), but unlike rounds 3-5's sc1 plain stores and loads it does not depend on how a
-  // cache treats non-atomic accesses.  The partials are non-negative sums of norms, so adding 0
-  // returns them unchanged.
-  // tests/test_gpu_din_plan.py checks l2 against the deterministic host-order sum over repeated
-  // launches.  (The norms in LDS were ordered before this by mlp_rows' barriers.)
-  if (a.l2_part && tid < 64) {
-    unsigned prev = 0;
-    if (tid == 0) {
-      float t = 0.f;
-      for (int w = 0; w < kMlpRows; ++w) t += sm[Ly::NORM + w];
-      const float old = __hip_atomic_exchange(a.l2_part + blockIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // the counter's add waits for the exchange to return (a use of its result orders it after)
-      unsigned one = 1u;
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(one) : "v"(old) : "memory");
-      prev = __hip_atomic_fetch_add(a.l2_count, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    prev = __builtin_amdgcn_readfirstlane(prev);
-    if (prev == gridDim.x - 1) {
-      float t = 0.f;
-      for (int i = tid; i < (int)gridDim.x; i += 64)
-        t += __hip_atomic_fetch_add(a.l2_part + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      t = wave_sum(t);  // the order of row_l2norm_final_kernel (embedding.hip)
-      if (tid == 0) {
-        a.l2_out[0] = a.l2_scale * (t / (float)a.batch);
-        __hip_atomic_store(a.l2_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+  // the l2 hand-off (din_l2_handoff): the streamed phase B ran it beside its last layer
+  // (DinRowsReady::side); here after the generic one.  (The norms in LDS were ordered before this by
+  // mlp_rows' barriers.)
+  if constexpr (std::is_void_v<P>) {
+    if (a.l2_part && tid < 64) din_l2_handoff(a.l2_part, a.l2_count, a.l2_out, a.l2_scale, a.batch, sm + Ly::NORM, tid);
   }
 #ifdef RK_DIN_PHASES
   din_marks_flush(tid);
@@ -1060,6 +1117,7 @@ RK_API int rk_din_plan_set_epilogue_image(void* plan, const float* image) {
 }
 
 #ifdef RK_DIN_PHASES
+RK_API int rk_debug_din_phase_marks(void) { return kDinMarks; }  // marks per workgroup in `ts` below
 RK_API int rk_debug_din_phases(unsigned long long* ts, unsigned long long* waves, unsigned long long* mlp) {
   if (hipMemcpyFromSymbol(ts, HIP_SYMBOL(g_din_ts), sizeof(g_din_ts)) != hipSuccess) return 1;
   if (hipMemcpyFromSymbol(waves, HIP_SYMBOL(g_din_wave), sizeof(g_din_wave)) != hipSuccess) return 1;

@@ -1,7 +1,10 @@
 """Phase split of din_forward_kernel<32> at the bench's DIN configs[2] workload, from a timing
 build of the library (make EXTRA=-DRK_DIN_PHASES OUT=<lib> BUILD=build_phases; point RANKOPS_LIB
 at it).  Per workgroup: wall-clock (100 MHz) marks at entry, after staging, after phase A
-(attention), after phase B (fcn tail); per wave: phase-A cycles.  Prints the distributions."""
+(attention), after phase B (fcn tail) and after the l2 hand-off; per wave: phase-A cycles.  Prints
+the distributions.  DIN_PLAN=1 times the headline's prepared launch (l2 term, packed epilogue
+image) instead of the bare kernel launcher.  A library with 8 marks per workgroup (no
+rk_debug_din_phase_marks) prints the marks it has."""
 import ctypes
 import os
 import sys
@@ -15,6 +18,9 @@ import torch  # noqa: E402
 batch = int(os.environ.get("BATCH", "4096"))
 model, inp, fn, cfg, name = bench.workload("din", batch, 0)
 launch = model.fused_kernel_launcher(inp["dense"], inp["category"], inp["sequence"], inp["target"])
+if os.environ.get("DIN_PLAN", "0") == "1":
+    with torch.no_grad():
+        launch = model.prepare(inp["dense"], inp["category"], inp["sequence"], inp["target"]).plan.launch
 us = 1e3 * bench.kernel_avg_ms(launch)
 torch.cuda.synchronize()
 n_launch = 5 + 50 + 1  # kernel_avg_ms warm-up + timed, and the launch below (RK_MLP_PHASES accumulates)
@@ -22,13 +28,14 @@ launch()
 torch.cuda.synchronize()
 from rankops import _lib  # noqa: E402
 lib = _lib.load()
-ts = (ctypes.c_ulonglong * (1024 * 8))()
+NM = lib.rk_debug_din_phase_marks() if hasattr(lib, "rk_debug_din_phase_marks") else 8  # marks per workgroup
+ts = (ctypes.c_ulonglong * (1024 * NM))()
 wv = (ctypes.c_ulonglong * (1024 * 16))()
 ml = (ctypes.c_ulonglong * (1024 * (4 * 8 + 4)))()
 lib.rk_debug_din_phases.argtypes = [ctypes.c_void_p] * 3
 assert lib.rk_debug_din_phases(ts, wv, ml) == 0
 nwg = min(1024, (batch + 15) // 16)
-t = np.array(ts, dtype=np.int64).reshape(1024, 8)[:nwg] * 10  # ns
+t = np.array(ts, dtype=np.int64).reshape(1024, NM)[:nwg] * 10  # ns
 w = np.array(wv, dtype=np.int64).reshape(1024, 16)[:nwg]
 t0 = t[:, 0].min()
 rel = (t - t0) / 1e3  # us from the first workgroup's entry
@@ -46,8 +53,11 @@ print("  image copied", q((t[:, 5] - t[:, 0]) / 1e3), "(tid 0, from entry)")
 print("  counted     ", q((t[:, 6] - t[:, 0]) / 1e3), "(tid 0, from entry)")
 print("assignment   ", q((t[:, 4] - t[:, 1]) / 1e3), "(wave 0)")
 print("  A.1 (wave 0)", q((t[:, 7] - t[:, 4]) / 1e3), "(row + first keys loaded, from assignment)")
+print("first MFMA   ", q((t[:, 7] - t[:, 0]) / 1e3), "(wave 0: end of A.1, from entry)")
 print("phase A      ", q((t[:, 2] - t[:, 1]) / 1e3))
 print("phase B      ", q((t[:, 3] - t[:, 2]) / 1e3))
+if NM > 8 and t[:, 8].all():  # (a launch without the l2 term leaves the mark 0)
+    print("hand-off done", q((t[:, 8] - t[:, 3]) / 1e3), "(relative to the end of phase B)")
 print("end          ", q(rel[:, 3]))
 print("wave A cycles", q(w.reshape(-1) / 1e3), "(k cycles)")
 print("wave A max/mean per WG", q(w.max(1) / np.maximum(w.mean(1), 1)))
