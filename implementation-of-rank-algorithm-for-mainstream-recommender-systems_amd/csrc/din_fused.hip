@@ -19,8 +19,8 @@
 //  Phase B: the fcn tail + output layer + sigmoid over the 16 LDS rows (mlp_stream.h for the
 //  compiled [512, 256, 128] plan, mlp_core.h otherwise).
 // The l2 term is finished by a one-wave reduction over the per-workgroup partial sums: the hand-off
-// (din_l2_handoff) runs in an idle wave beside the streamed phase B's last layer, after the generic
-// phase B otherwise.
+// (din_l2_handoff) runs as four side steps of the last wave from the opening of the streamed phase B
+// through its second layer (DinRowsReady::side_step), after the generic phase B otherwise.
 // Staging order: column map, segment descriptors and lengths are loaded first; the packed attention
 // image (or the split formed from w1..w3) goes through registers into LDS before the first barrier,
 // beside them (contiguous launches: behind the row gather).
@@ -34,6 +34,8 @@ namespace rk {
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) void glb_void;
+typedef __attribute__((address_space(1))) float glb_float;
+typedef __attribute__((address_space(1))) unsigned glb_uint;
 
 #ifndef RK_DIN_HOIST  // experiment (phase A's layer-1 operand per sample): see the tile loop
 #define RK_DIN_HOIST 0
@@ -89,10 +91,12 @@ struct DinLds {
 
 #ifdef RK_DIN_PHASES  // timing build only (tools/din_phases.py): per-workgroup wall-clock marks
 constexpr int kDinPhaseWG = 1024;
-constexpr int kDinMarks = 9;
+constexpr int kDinMarks = 13;
 // entry, staged, phase A done, phase B done, wave 0 assigned, image copied, classes counted,
 // wave 0's row and first keys loaded (tid 0), l2 hand-off done (lane 0 of the wave that ran it; 0: no
-// hand-off in this launch)
+// hand-off in this launch), 1 in the workgroup that read the partials (else 0), then the last wave's
+// marks of the streamed phase B (mlp_stream.h STREAM_LAST_TS): layer 0 opened, the last layer
+// opened, arrival at the barrier that closes it
 __device__ unsigned long long g_din_ts[kDinPhaseWG][kDinMarks];
 __device__ unsigned long long g_din_wave[kDinPhaseWG][16];    // per-wave phase-A cycles (clock64)
 // marks are kept in LDS while the kernel runs (a global store mid-kernel joins the vmcnt queue
@@ -112,7 +116,8 @@ __shared__ unsigned long long s_din_wave[16];
 __device__ __forceinline__ void din_marks_flush(int tid) {
   __syncthreads();
   if (blockIdx.x < kDinPhaseWG) {
-    if (tid < kDinMarks) g_din_ts[blockIdx.x][tid] = s_din_ts[tid];
+    if (tid < 10) g_din_ts[blockIdx.x][tid] = s_din_ts[tid];
+    if (tid >= 10 && tid < kDinMarks) g_din_ts[blockIdx.x][tid] = s_stream_last_ts[tid - 10];
     if (tid < 16) g_din_wave[blockIdx.x][tid] = s_din_wave[tid];
   }
 }
@@ -161,6 +166,11 @@ template <int H>
 constexpr int din_pre_chunks() {
   return (16 + 34 + H) / 16 < 7 ? (16 + 34 + H) / 16 : 7;
 }
+// Phase B's last layer (128 wide: waves 8..15 own no tile of it) without its one lockstep barrier, as
+// it ran while the l2 hand-off sat beside it (round 7); measured both ways (mlp_stream.h kSync)
+#ifndef RK_DIN_FREE_LAST
+#define RK_DIN_FREE_LAST 1
+#endif
 // balanced launches gather each wave's row inside phase A: the waves count their rows in here
 static __shared__ unsigned s_din_rows_ready;
 // The l2 hand-off: the last workgroup to publish its partial finishes the mean.  By atomic
@@ -203,7 +213,10 @@ __device__ __forceinline__ void din_l2_handoff(float* l2_part, unsigned* l2_coun
     }
   }
 #ifdef RK_DIN_PHASES
-  if (lane == 0) s_din_ts[8] = wall_clock64();
+  if (lane == 0) {
+    s_din_ts[8] = wall_clock64();
+    s_din_ts[9] = prev == gridDim.x - 1;
+  }
 #endif
 }
 
@@ -225,17 +238,116 @@ static __shared__ DinL2Args s_din_l2;
 // DMA: the last four waves may have copied the epilogue image into LDS by LDS-DMA after their
 // phase A: the copies retire before the barrier that opens phase B (loads
 // retire in order; exactly the RK_STREAM_RING ring loads were issued after them).
-// side(): the l2 hand-off beside phase B's last layer instead of after the head.  That layer is
-// narrower than 16 tiles and leaves the last wave without one; naming it the side layer makes
-// mlp_stream.h run side() in the idle waves when the layer opens and drop the layer's lockstep
-// barrier, so the last wave can sit on its atomics' returns (two dependent round trips, a third in
-// the reader) with nobody waiting for it before the barrier that closes the layer.  The norms were
-// ordered before this by the barrier that opened phase B.
+// Side steps (mlp_core.h stage_side_steps): the l2 hand-off of din_l2_handoff, the same accesses in
+// the same order, cut where it waits.  Its only inputs, the 16 norms, are final at the barrier that
+// opens phase B, some 18 us before the kernel ends; beside the last layer (round 7) its two or
+// three dependent agent-scope round trips, and the 256 workgroups' adds queueing on one word,
+// still ended 2.5 us after a launch without the l2 term (profiles/r08).  The last wave now runs
+//   0  when layer 0 opens: lane 0 sums the norms and issues the exchange of the partial;
+//   1  after chunk 3 of layer 1: the counter's add, data-dependent on the exchange's return;
+//   2  after chunk 11: prev becomes wave-uniform, and the workgroup that counted last issues its
+//      first kHeld reads per lane of the partials (fetch-add of 0);
+//   3  after chunk 19: the reader adds them in the loop's order, reads what a grid of more than
+//      64 kHeld workgroups leaves (waiting for each: one wave of one workgroup), wave_sum, l2_out,
+//      counter reset.
+// No step waits for what it issued.  Each sits behind a refill of the ring (RK_STREAM_REFILL_GROUP =
+// 4 chunks in the one-tile layer 1): the loads queued behind its atomic are the next refill's,
+// first used 8 chunks later, so the vmcnt queue (which retires in order) gives the atomic 8 chunks
+// (about 2.4 us) to return before the wave would stall on it, and a step reads its predecessor's
+// result 8 chunks on, where that wait has already been paid.  (Ahead of the refill the loads
+// behind the atomic would be needed after 4 chunks.)  The counter is reset mid-kernel, by the one
+// workgroup whose add returned n - 1: every add of the launch has been performed by then, and the
+// next launch's start after this kernel's end.
 template <class P, int H, bool WAIT, bool DMA>
 struct DinRowsReady {
-  static constexpr int kSideLayer = P::NL - 1;
-  static_assert(P::NL >= 2 && P::nt(P::NL - 1) < kMlpWaves && P::tpw(P::NL - 1, kMlpWaves - 1) == 0,
-                "the side layer leaves the last wave without a tile");
+#if RK_DIN_FREE_LAST
+  static constexpr int kFreeLayer = P::NL - 1;
+#endif
+  static constexpr int kSideSteps = 4, kSideWave = kMlpWaves - 1;
+  static constexpr int kHeld = 4;  // partials per lane the reader holds between steps 2 and 3
+  static constexpr int side_step_layer(int s) { return s == 0 ? 0 : 1; }
+  static constexpr int side_step_chunk(int s) { return s == 0 ? -1 : 8 * s - 5; }
+  static_assert(P::NL >= 2 && P::kc(1) >= 24 && RK_STREAM_RING == 8 && (RK_STREAM_REFILL_GROUP == 4 || RK_STREAM_REFILL_GROUP == 1),
+                "the steps sit behind refills of layer 1, a ring apart");
+  struct SideState {
+    glb_float* l2_part;  // wave-uniform from step 0 on (scalar registers): null without the l2 term
+    glb_uint* l2_count;
+    float old;          // lane 0: what the exchange returned (orders the counter's add behind it)
+    unsigned prev;      // the counter's add's return: lane 0 after step 1, wave-uniform after step 2
+    float part[kHeld];  // the reader's first partials, lane + 64 k
+  };
+  // a pointer read from LDS, as a wave-uniform global one.  (Global: the atomics are then global_
+  // instructions, whose returns the compiler counts in vmcnt; on the generic pointers that LDS
+  // yields they would be flat_ ones, and it drains the ring with vmcnt(0) at the next ring slot's use)
+  template <class T>
+  static __device__ __forceinline__ T uniform_global(const void* p) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return (T)(((uint64_t)hi << 32) | lo);
+  }
+  template <int S>
+  __device__ __forceinline__ void side_step(SideState& st) const {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = (int)threadIdx.x & 63;
+    // the hand-off's addresses out of LDS once, in step 0: the later steps of a launch without the l2
+    // term are a scalar test
+    if constexpr (S == 0) {
+      st.l2_part = uniform_global<glb_float*>(s_din_l2.part);
+      st.l2_count = uniform_global<glb_uint*>(s_din_l2.count);
+    }
+    glb_float* const l2_part = st.l2_part;
+    if (!l2_part) return;
+    const int grid = (int)gridDim.x;
+    if constexpr (S == 0) {
+      if (lane == 0) {
+        const float* norms = sm + DinLds<H>::NORM;
+        float t = 0.f;
+        for (int w = 0; w < kMlpRows; ++w) t += norms[w];
+        st.old = __hip_atomic_exchange(l2_part + blockIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    } else if constexpr (S == 1) {
+      if (lane == 0) {
+        // the add's address passes through a use of the exchange's result: the compiler's counted
+        // vmcnt for that result (none, where a ring load issued behind the exchange has been waited
+        // for since) stands in front of the add.  The address and not the operand: with an address
+        // it cannot prove uniform the compiler leaves the add as one instruction, where it would
+        // otherwise wrap it in a wave reduction that ends in vmcnt(0)
+        glb_uint* count = st.l2_count;
+        asm volatile("" : "+v"(count) : "v"(st.old) : "memory");
+        st.prev = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    } else if constexpr (S == 2) {
+      st.prev = __builtin_amdgcn_readfirstlane(st.prev);
+      if (st.prev == (unsigned)grid - 1u) {
+#pragma unroll
+        for (int k = 0; k < kHeld; ++k) {
+          const int i = lane + 64 * k;
+          st.part[k] = 0.f;  // (adding 0 leaves the non-negative sum as it is)
+          if (i < grid) st.part[k] = __hip_atomic_fetch_add(l2_part + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    } else {
+      if (st.prev == (unsigned)grid - 1u) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < kHeld; ++k) t += st.part[k];
+        for (int i = lane + 64 * kHeld; i < grid; i += 64)
+          t += __hip_atomic_fetch_add(l2_part + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = wave_sum(t);  // the order of row_l2norm_final_kernel (embedding.hip)
+        if (lane == 0) {
+          const DinL2Args l2 = s_din_l2;
+          ((glb_float*)l2.out)[0] = l2.scale * (t / (float)l2.batch);
+          __hip_atomic_store(st.l2_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+#ifdef RK_DIN_PHASES
+      if (lane == 0) {
+        s_din_ts[8] = wall_clock64();
+        s_din_ts[9] = st.prev == (unsigned)grid - 1u;
+      }
+#endif
+    }
+  }
   __device__ void issue() const {}
   __device__ void operator()() const {
     if constexpr (DMA) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RK_STREAM_RING) : "memory");
@@ -246,13 +358,7 @@ struct DinRowsReady {
       asm volatile("" ::: "memory");  // the rows are read after the count
     }
   }
-  __device__ void side() const {
-    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) != kMlpWaves - 1) return;
-    const DinL2Args l2 = s_din_l2;
-    if (!l2.part) return;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    din_l2_handoff(l2.part, l2.count, l2.out, l2.scale, l2.batch, sm + DinLds<H>::NORM, (int)threadIdx.x & 63);
-  }
+  __device__ void side() const {}
 };
 
 // P: the compiled layer plan of phase B (mlp_stream.h), or void for the generic mlp_rows.
@@ -452,7 +558,7 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
   }
   DIN_TS(6);
   if (KS > 0 && tid == 0) s_din_rows_ready = 0u;
-  if constexpr (!std::is_void_v<P>) {  // the stage's hand-off arguments (DinRowsReady::side)
+  if constexpr (!std::is_void_v<P>) {  // the stage's hand-off arguments (DinRowsReady::side_step)
     if (tid == 0) s_din_l2 = DinL2Args{a.l2_part, a.l2_count, a.l2_out, a.l2_scale, a.batch};
   }
   __syncthreads();
@@ -779,8 +885,8 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
                                       PreChunks<KS, DinRowsReady<P, H, (NIT > 0 && KS > 0), true>>{}, nullptr,
                                       NIT > 0 ? s_rows : nullptr);
   DIN_TS(3);
-  // the l2 hand-off (din_l2_handoff): the streamed phase B ran it beside its last layer
-  // (DinRowsReady::side); here after the generic one.  (The norms in LDS were ordered before this by
+  // the l2 hand-off (din_l2_handoff): the streamed phase B ran it as its stage's side steps
+  // (DinRowsReady::side_step); here after the generic one.  (The norms in LDS were ordered before this by
   // mlp_rows' barriers.)
   if constexpr (std::is_void_v<P>) {
     if (a.l2_part && tid < 64) din_l2_handoff(a.l2_part, a.l2_count, a.l2_out, a.l2_scale, a.batch, sm + Ly::NORM, tid);

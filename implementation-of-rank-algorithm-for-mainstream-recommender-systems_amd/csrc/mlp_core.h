@@ -498,6 +498,36 @@ template <int N, class S>
 struct RingEarly : S {
   static constexpr int kRingEarly = N;
 };
+// Side steps (mlp_stream.h): side work of ONE wave that is a chain of memory round trips (DIN's l2
+// hand-off), cut into kSideSteps pieces that only issue.  Step s runs in wave kSideWave after chunk
+// side_step_chunk(s) of layer side_step_layer(s) has refilled its ring slots (chunk -1: when the
+// layer opens); it issues its memory operation into the stage's SideState and returns, and the
+// next step consumes what came back.  The state is a local of the streamed tail, not a member of
+// the stage, so it lives in registers beside the ring.  A stage with the interface declares
+//   static constexpr int kSideSteps, kSideWave;
+//   static constexpr int side_step_layer(int s), side_step_chunk(int s);   // ascending
+//   struct SideState;  template <int S> __device__ void side_step(SideState&) const;
+// Stages without it get an empty state and no code.
+// A layer the stage wants run without the lockstep barriers (mlp_stream.h): kFreeLayer.
+template <class T, class = void>
+struct stage_free_layer {
+  static constexpr int value = -1;
+};
+template <class T>
+struct stage_free_layer<T, std::void_t<decltype(T::kFreeLayer)>> {
+  static constexpr int value = T::kFreeLayer;
+};
+struct NoSideState {};
+template <class T, class = void>
+struct stage_side_steps {
+  static constexpr int value = 0;
+  using State = NoSideState;
+};
+template <class T>
+struct stage_side_steps<T, std::void_t<decltype(T::kSideSteps)>> {
+  static constexpr int value = T::kSideSteps;
+  using State = typename T::SideState;
+};
 template <int N, class S>
 __device__ __forceinline__ RingEarly<N, S> ring_early(S s) {
   return RingEarly<N, S>{s};

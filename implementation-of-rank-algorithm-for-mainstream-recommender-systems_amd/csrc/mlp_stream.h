@@ -96,6 +96,21 @@ constexpr int kStreamStaticLds = 64;
 static __shared__ unsigned rk_stream_ready[RK_MLP_MAX_LAYERS];
 #endif
 
+// Timing build of the DIN forward (RK_DIN_PHASES, tools/din_phases.py): wall-clock marks of the
+// last wave (lane 0), kept in LDS and flushed by the kernel: [0] layer 0 opened (the barrier that
+// opens phase B passed), [1] the last layer opened, [2] arrival at the barrier that closes it
+#ifdef RK_DIN_PHASES
+__shared__ unsigned long long s_stream_last_ts[3];
+#define STREAM_LAST_TS(i)                                                    \
+  do {                                                                       \
+    if (tid == kMlpThreads - 64) s_stream_last_ts[i] = wall_clock64();       \
+  } while (0)
+#else
+#define STREAM_LAST_TS(i) \
+  do {                    \
+  } while (0)
+#endif
+
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (B < E) {
@@ -240,6 +255,23 @@ constexpr int side_last_pos(int KC, int c) {
   return -1;
 }
 
+// A stage's side steps (mlp_core.h stage_side_steps) sit where wave class W runs them: in ascending
+// order, in layers where the class owns a tile, at a chunk of the layer's loop (layer 0's starts
+// after the KS pre-barrier chunks) or at its opening.
+template <class P, class Stage, int W, int KS>
+constexpr bool side_steps_placed() {
+  int pl = -1, pc = -2;
+  for (int s = 0; s < stage_side_steps<Stage>::value; ++s) {
+    const int l = Stage::side_step_layer(s), c = Stage::side_step_chunk(s);
+    if (l < 0 || l >= P::NL || P::tpw(l, W) == 0) return false;
+    if (c != -1 && (c < (l == 0 ? KS : 0) || c >= P::kc(l))) return false;
+    if (l < pl || (l == pl && c <= pc)) return false;
+    pl = l;
+    pc = c;
+  }
+  return true;
+}
+
 // One wave class W (P::rep(W) == W) of the streamed tail.  `epi` is the LDS parameter image
 // (stored before the barrier that opens layer 0); `stage` as in mlp_rows (issue() before the ring,
 // operator() after it, before that barrier).  EPI: StreamEpiMode.
@@ -290,7 +322,9 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
   StreamEpi<P> ep_stage;
   constexpr bool kEarly = stage_has_early<Stage>::value;
   // the layer whose MFMAs the stage's side work runs beside: the stage's choice, else the second
-  constexpr int kSideL = stage_side_layer<Stage>::value >= 0 ? stage_side_layer<Stage>::value : (NL > 1 ? 1 : 0);
+  // (a stage with side steps has no side(): no layer, and none of the staggered call sites)
+  constexpr int kSideL = stage_side_steps<Stage>::value > 0 ? -1
+                         : stage_side_layer<Stage>::value >= 0 ? stage_side_layer<Stage>::value : (NL > 1 ? 1 : 0);
   // kEpiRegs: the parameters of the wave's columns of one layer (tiles j = 0, 1)
   ColEpi epr[2];
   auto load_epr = [&](auto LI) {
@@ -374,6 +408,29 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
 #endif
   mlp_lds_barrier();
   MLP_MARK(4 * RK_MLP_MAX_LAYERS, t_start);  // prologue done
+  STREAM_LAST_TS(0);
+
+  // the stage's side steps (mlp_core.h stage_side_steps), in the class of the wave that runs them:
+  // the steps placed at chunk c of layer l (c == -1: the layer's opening).  The wave test is a
+  // scalar branch; the step's memory operation joins the wave's vmcnt queue behind the ring loads
+  // issued so far, and its result is waited for (a counted vmcnt) only where a later step reads it
+  constexpr int kSteps = stage_side_steps<Stage>::value;
+  [[maybe_unused]] typename stage_side_steps<Stage>::State side_state{};
+  auto side_steps_at = [&](auto LI, auto CI) {
+    if constexpr (kSteps > 0) {
+      if constexpr (P::rep(Stage::kSideWave) == W) {
+        static_assert(side_steps_placed<P, Stage, W, KS>(), "side steps: ascending, at chunks of tiled layers");
+        static_for<0, kSteps>([&](auto SI) {
+          constexpr int s = SI;
+          if constexpr (Stage::side_step_layer(s) == decltype(LI)::value &&
+                        Stage::side_step_chunk(s) == decltype(CI)::value) {
+            if (wave == Stage::kSideWave) stage.template side_step<s>(side_state);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        });
+      }
+    }
+  };
 
   static_for<0, NL>([&](auto LI) {
     constexpr int l = LI;
@@ -381,10 +438,16 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
 #ifdef RK_MLP_PHASES
     const unsigned long long t0 = clock64();
 #endif
+    if constexpr (l == NL - 1) STREAM_LAST_TS(1);
+    side_steps_at(LI, std::integral_constant<int, -1>{});
     const rk_mlp_layer& L = layers[l];
     // lockstep barriers, except in a layer the stage chose for side work that leaves waves without
-    // a tile: those waves do the side work instead, and a barrier would make the others wait for it
-    constexpr bool kSync = !(stage_side_layer<Stage>::value == l && P::nt(l) < kMlpWaves);
+    // a tile: those waves do the side work instead, and a barrier would make the others wait for it;
+    // and except in a layer the stage wants free of them (DIN's 128-wide last layer, as it ran in
+    // round 7: with its one barrier restored the prepared launch measures the same, 35.56 / 35.50 /
+    // 35.48 us against 35.55 / 35.55 / 35.47: profiles/r08/l2_cost_new_sync_*.log)
+    constexpr bool kSync = !(stage_side_layer<Stage>::value == l && P::nt(l) < kMlpWaves) &&
+                           stage_free_layer<Stage>::value != l;
     // IP0: layer 0 in place in buf0, then the ping-pong one step behind
     constexpr bool kIn1 = IP0 ? (l > 0 && !(l & 1)) : (l & 1);
     constexpr bool kOut1 = IP0 ? (l & 1) : !(l & 1);
@@ -471,6 +534,9 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
           }
         }
         __builtin_amdgcn_sched_barrier(0);
+        // side steps placed at this chunk: behind its refill, so that the ring loads that queue behind
+        // the step's memory operation are those of the NEXT refill group, consumed a whole ring later
+        side_steps_at(LI, CI);
         // the stage's side work, once, beside the MFMAs of layer kSideL (default: the second),
         // staggered over the SIMD's four waves (wave w sits at position w / 4 of SIMD w % 4): wave
         // position k at chunk side_chunk(k), one per lockstep window when the layer has 32 chunks, so
@@ -553,6 +619,7 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
     if constexpr (EPI == kEpiRegs) load_epr(std::integral_constant<int, l + 1>{});
     if constexpr (l + 2 == NL) head_prefetch();
     MLP_MARK(4 * l + 2, t0);
+    if constexpr (l == NL - 1) STREAM_LAST_TS(2);
     if constexpr (!RK_STREAM_FLAGS || l + 1 == NL) mlp_lds_barrier();  // (flags: only before the head)
     MLP_MARK(4 * l + 3, t0);
 #if RK_MLP_EPI_PRIO

@@ -3,8 +3,11 @@ build of the library (make EXTRA=-DRK_DIN_PHASES OUT=<lib> BUILD=build_phases; p
 at it).  Per workgroup: wall-clock (100 MHz) marks at entry, after staging, after phase A
 (attention), after phase B (fcn tail) and after the l2 hand-off; per wave: phase-A cycles.  Prints
 the distributions.  DIN_PLAN=1 times the headline's prepared launch (l2 term, packed epilogue
-image) instead of the bare kernel launcher.  A library with 8 marks per workgroup (no
-rk_debug_din_phase_marks) prints the marks it has."""
+image) instead of the bare kernel launcher, DIN_L2=0 with it the same plan without the l2 term
+(l2_out == nullptr).  A library with 13 marks also prints the last wave's marks of the streamed
+phase B (phase B opened, last layer opened, arrival at its closing barrier) and the workgroup that
+read the l2 partials.  A library with 8 marks per workgroup (no rk_debug_din_phase_marks) prints the
+marks it has."""
 import ctypes
 import os
 import sys
@@ -19,6 +22,8 @@ batch = int(os.environ.get("BATCH", "4096"))
 model, inp, fn, cfg, name = bench.workload("din", batch, 0)
 launch = model.fused_kernel_launcher(inp["dense"], inp["category"], inp["sequence"], inp["target"])
 if os.environ.get("DIN_PLAN", "0") == "1":
+    if os.environ.get("DIN_L2", "1") == "0":  # the plan without the l2 term (l2_out == nullptr)
+        model.mini_batch_aware_regularization = False
     with torch.no_grad():
         launch = model.prepare(inp["dense"], inp["category"], inp["sequence"], inp["target"]).plan.launch
 us = 1e3 * bench.kernel_avg_ms(launch)
@@ -58,7 +63,17 @@ print("phase A      ", q((t[:, 2] - t[:, 1]) / 1e3))
 print("phase B      ", q((t[:, 3] - t[:, 2]) / 1e3))
 if NM > 8 and t[:, 8].all():  # (a launch without the l2 term leaves the mark 0)
     print("hand-off done", q((t[:, 8] - t[:, 3]) / 1e3), "(relative to the end of phase B)")
-print("end          ", q(rel[:, 3]))
+print("end          ", q(rel[:, 3]), f" max - med {np.max(rel[:, 3]) - np.median(rel[:, 3]):.2f}")
+if NM > 12:  # the last wave's marks of the streamed phase B, and the workgroup that read the partials
+    print("last wave: phase B opened", q(rel[:, 10]))
+    print("last wave: last layer opened", q(rel[:, 11]), "| from there to its closing barrier",
+          q((t[:, 12] - t[:, 11]) / 1e3))
+    print("last wave: at the last layer's closing barrier", q(rel[:, 12]))
+    for g in np.nonzero(t[:, 9])[0]:
+        print(f"reader workgroup {g}: phase A end {rel[g, 2]:.2f}, phase B {(t[g, 3] - t[g, 2]) / 1e3:.2f}, "
+              f"end {rel[g, 3]:.2f}, hand-off done {rel[g, 8]:.2f}, last layer opened {rel[g, 11]:.2f}, "
+              f"last wave at its closing barrier {rel[g, 12]:.2f}")
+    print(f"last workgroup to end: {int(np.argmax(rel[:, 3]))}; last to finish phase A: {int(np.argmax(rel[:, 2]))}")
 print("wave A cycles", q(w.reshape(-1) / 1e3), "(k cycles)")
 print("wave A max/mean per WG", q(w.max(1) / np.maximum(w.mean(1), 1)))
 print("lengths: mean", lens.mean(), "frac <= 32:", (lens <= 32).mean())
