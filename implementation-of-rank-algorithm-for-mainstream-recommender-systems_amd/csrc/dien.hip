@@ -21,129 +21,20 @@
 // first pass is done, and the second pass reads h_t and a_t back one step ahead again.
 // No cross-wave traffic, no atomics: results are bit-reproducible, and the table form and the
 // dense form run the same code after the gather.
-#include "common.h"
+#include "dien_cell.h"
 
 namespace rk {
 
-constexpr int kDienSamples = 4;  // samples per wave (= per workgroup)
-
-struct DienWeights {
-  const float *Wg, *bg, *Wc, *bc, *A, *Vg, *vg, *Vc, *vc;
-};
-
-template <int K>
-__device__ __forceinline__ float row_ror(float v) {
-  if constexpr (K == 0)
-    return v;
-  else
-    // row_ror:K; every lane of a row is a valid source, so bound_ctrl changes nothing but lets the
-    // compiler fold the move into the consuming v_fmac_f32
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + K, 0xF, 0xF, true));
-}
-// The lane (of the 16 of a row) whose value row_ror<K> delivers to lane p, asked of the hardware.
-template <int K>
-__device__ __forceinline__ int row_ror_source(int p) {
-  if constexpr (K == 0)
-    return p;
-  else
-    return __builtin_amdgcn_update_dpp(0, p, 0x120 + K, 0xF, 0xF, false);
-}
-
-// tanh on the transcendental unit: 2 * sigmoid(2x) - 1; absolute error ~1e-7, saturates to +-1.
-__device__ __forceinline__ float tanh_fast(float x) {
-  return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -2.88539008177792681f)), -1.0f);
-}
-
-// One GRU-shaped cell (XW inputs, NH units) as lane p of a sample's row sees it.
-template <int XW, int NH>
-struct DienCell {
-  static constexpr int NG = NH / 8;  // gate rows per lane: nh 8 -> row p; nh 16 -> rows p and p + 16
-  static constexpr int LD = XW + NH;
-  float gx[NG][XW], cx[XW];  // input halves of this lane's gate rows / candidate row
-  float gh[NG][NH], ch[NH];  // state halves, in rotation order
-  float gb[NG], cb;
-
-  template <int K>
-  __device__ __forceinline__ void load_rot(const float* Wg, const float* Wc, int p) {
-    const int unit = row_ror_source<K>(p) % NH;  // the unit whose state rotation K brings here
-#pragma unroll
-    for (int i = 0; i < NG; ++i) gh[i][K] = Wg[(p + 16 * i) * LD + XW + unit];
-    ch[K] = Wc[(p % NH) * LD + XW + unit];
-    if constexpr (K + 1 < NH) load_rot<K + 1>(Wg, Wc, p);
-  }
-
-  __device__ __forceinline__ void load(const float* Wg, const float* bg, const float* Wc, const float* bc, int p) {
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-#pragma unroll
-      for (int x = 0; x < XW; ++x) gx[i][x] = Wg[(p + 16 * i) * LD + x];
-      gb[i] = bg[p + 16 * i];
-    }
-#pragma unroll
-    for (int x = 0; x < XW; ++x) cx[x] = Wc[(p % NH) * LD + x];
-    cb = bc[p % NH];
-    load_rot<0>(Wg, Wc, p);
-  }
-
-  // Input halves (+ bias) of one step from the LDS row x (16-B aligned, XW floats).
-  __device__ __forceinline__ void input(const float* x, float (&gi)[NG], float& ci) const {
-#pragma unroll
-    for (int i = 0; i < NG; ++i) gi[i] = gb[i];
-    ci = cb;
-#pragma unroll
-    for (int c4 = 0; c4 < XW / 4; ++c4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * c4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-#pragma unroll
-        for (int i = 0; i < NG; ++i) gi[i] = fmaf(gx[i][4 * c4 + e], v[e], gi[i]);
-        ci = fmaf(cx[4 * c4 + e], v[e], ci);
-      }
-    }
-  }
-
-  template <int K>
-  __device__ __forceinline__ void gate_dot(float (&acc)[NG], float h) const {
-    const float hk = row_ror<K>(h);
-#pragma unroll
-    for (int i = 0; i < NG; ++i) acc[i] = fmaf(hk, gh[i][K], acc[i]);
-    if constexpr (K + 1 < NH) gate_dot<K + 1>(acc, h);
-  }
-  template <int K>
-  __device__ __forceinline__ void cand_dot(float& acc, float rh) const {
-    acc = fmaf(row_ror<K>(rh), ch[K], acc);
-    if constexpr (K + 1 < NH) cand_dot<K + 1>(acc, rh);
-  }
-
-  // Update gate u and candidate c of this lane's unit from the input halves and the state h.
-  __device__ __forceinline__ void step(const float (&gi)[NG], float ci, float h, int half, float& u,
-                                       float& c) const {
-    float acc[NG];
-#pragma unroll
-    for (int i = 0; i < NG; ++i) acc[i] = gi[i];
-    gate_dot<0>(acc, h);
-    float r;
-    if constexpr (NG == 1) {  // lanes 0-7 hold r, lanes 8-15 hold u of the same units
-      const float g = sigmoid_fast(acc[0]);
-      const float o = row_ror<8>(g);
-      r = half ? o : g;
-      u = half ? g : o;
-    } else {
-      r = sigmoid_fast(acc[0]);
-      u = sigmoid_fast(acc[NG - 1]);
-    }
-    float ac = ci;
-    cand_dot<0>(ac, r * h);
-    c = tanh_fast(ac);
-  }
-};
-
-template <int H, int NH>
+// SAVE (the train forward): the extractor states h_t, the evolution states s_t and the attention
+// weights also go to hs_out / ss_out [batch, T, NH] (rows t >= len zero) and att_out for the
+// backward (dien_train.hip).  The arithmetic is the eval kernel's, so the state is bit-equal.
+template <int H, int NH, bool SAVE>
 __global__ __launch_bounds__(64) void dien_interest_kernel(
     const float* query, int64_t ld_query, const float* __restrict__ key_table, int64_t key_rows, int64_t ld_key,
     const int64_t* __restrict__ seq, int64_t ld_seq, int64_t ld_kb, int T, const int64_t* __restrict__ seq_len,
     int64_t batch, DienWeights w, int cell_type, int sample_stride, float* out, int64_t ld_out,
-    float* __restrict__ att_out, int64_t ld_att, uint32_t* flags) {
+    float* __restrict__ att_out, int64_t ld_att, uint32_t* flags, float* __restrict__ hs_out,
+    float* __restrict__ ss_out) {
   constexpr int RW = H > NH ? H : NH;  // LDS row: x_t first, h_t after step t
   constexpr int NG = NH / 8;
   extern __shared__ __attribute__((aligned(16))) float dien_sm[];
@@ -217,6 +108,9 @@ __global__ __launch_bounds__(64) void dien_interest_kernel(
       g.step(gi, ci, h, half, u, c);
       h = fmaf(u, h - c, c);  // u*h + (1-u)*c
       if (p < NH) rows[t * RW + j] = h;
+      if constexpr (SAVE) {
+        if (p < NH) hs_out[(b * T + t) * NH + j] = h;
+      }
 #pragma unroll
       for (int i = 0; i < NG; ++i) gi[i] = gn[i];
       ci = cn;
@@ -293,12 +187,22 @@ __global__ __launch_bounds__(64) void dien_interest_kernel(
         const float u2 = fmaf(-a, u, u);  // (1-a)*u
         st = fmaf(u2, st - c, c);         // u'*s + (1-u')*c
       }
+      if constexpr (SAVE) {
+        if (p < NH) ss_out[(b * T + t) * NH + j] = st;
+      }
 #pragma unroll
       for (int i = 0; i < NG; ++i) gi[i] = gn[i];
       ci = cn;
       a = an;
     }
     if (live && p < NH) out[b * ld_out + j] = st;
+  }
+  if constexpr (SAVE) {
+    if (live)
+      for (int e = len * NH + p; e < T * NH; e += 16) {
+        hs_out[b * T * NH + e] = 0.f;
+        ss_out[b * T * NH + e] = 0.f;
+      }
   }
 }
 
@@ -318,9 +222,10 @@ static int launch_dien(const float* query, int64_t ld_query, const float* key_ta
                        int64_t ld_key, const int64_t* seq, int64_t ld_seq, int64_t ld_kb, int32_t T,
                        const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh, int32_t cell_type,
                        const DienWeights& w, float* out, int64_t ld_out, float* att_out, int64_t ld_att,
-                       void* stream, const char* who) {
+                       void* stream, const char* who, bool save = false, float* hs_out = nullptr,
+                       float* ss_out = nullptr) {
   if (!query || !key_table || !seq_len || !w.Wg || !w.bg || !w.Wc || !w.bc || !w.A || !w.Vg || !w.vg || !w.Vc ||
-      !w.vc || !out)
+      !w.vc || !out || (save && (!hs_out || !ss_out || !att_out)))
     return fail(RK_ERR_INVALID, "%s: null pointer", who);
   if (T <= 0 || batch < 0 || H <= 0 || nh <= 0 || ld_query < H || ld_out < nh || ld_key < H || (att_out && ld_att < T))
     return fail(RK_ERR_INVALID, "%s: bad shape T=%d H=%d nh=%d", who, T, H, nh);
@@ -337,12 +242,19 @@ static int launch_dien(const float* query, int64_t ld_query, const float* key_ta
   const unsigned blocks = (unsigned)((batch + kDienSamples - 1) / kDienSamples);
   hipStream_t st = (hipStream_t)stream;
   uint32_t* fl = device_flags();
+#define RK_DIEN_LAUNCH(HH, NN, SV)                                                                            \
+  if (shm > 64 * 1024) raise_lds_limit((const void*)dien_interest_kernel<HH, NN, SV>, (int)shm);              \
+  dien_interest_kernel<HH, NN, SV><<<blocks, 64, shm, st>>>(query, ld_query, key_table, key_rows, ld_key, seq, \
+                                                            ld_seq, ld_kb, T, seq_len, batch, w, cell_type,   \
+                                                            stride, out, ld_out, att_out, ld_att, fl, hs_out, \
+                                                            ss_out);
 #define RK_DIEN_CASE(HH, NN)                                                                                  \
   if (H == HH && nh == NN) {                                                                                  \
-    if (shm > 64 * 1024) raise_lds_limit((const void*)dien_interest_kernel<HH, NN>, (int)shm);                \
-    dien_interest_kernel<HH, NN><<<blocks, 64, shm, st>>>(query, ld_query, key_table, key_rows, ld_key, seq,  \
-                                                          ld_seq, ld_kb, T, seq_len, batch, w, cell_type,     \
-                                                          stride, out, ld_out, att_out, ld_att, fl);          \
+    if (save) {                                                                                               \
+      RK_DIEN_LAUNCH(HH, NN, true)                                                                            \
+    } else {                                                                                                  \
+      RK_DIEN_LAUNCH(HH, NN, false)                                                                           \
+    }                                                                                                         \
   }
   RK_DIEN_CASE(8, 8)
   RK_DIEN_CASE(16, 8)
@@ -351,6 +263,7 @@ static int launch_dien(const float* query, int64_t ld_query, const float* key_ta
   RK_DIEN_CASE(16, 16)
   RK_DIEN_CASE(32, 16)
 #undef RK_DIEN_CASE
+#undef RK_DIEN_LAUNCH
   return check_launch(who);
 }
 
@@ -378,4 +291,33 @@ RK_API int rk_dien_interest_dense(const float* query, int64_t ld_query, const fl
   const DienWeights w{Wg, bg, Wc, bc, A, Vg, vg, Vc, vc};
   return launch_dien(query, ld_query, keys, 0, ld_keys_t, nullptr, 0, ld_keys_b, T, keys_length, batch, H, nh,
                      cell_type, w, out, ld_out, att_out, ld_att, stream, "rk_dien_interest_dense");
+}
+
+RK_API int rk_dien_interest_train(const float* query, int64_t ld_query, const float* key_table, int64_t key_rows,
+                                  int64_t ld_key, const int64_t* seq, int64_t ld_seq, int32_t T,
+                                  const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh, int32_t cell_type,
+                                  const float* Wg, const float* bg, const float* Wc, const float* bc, const float* A,
+                                  const float* Vg, const float* vg, const float* Vc, const float* vc, float* out,
+                                  int64_t ld_out, float* att_out, int64_t ld_att, float* hs, float* ss,
+                                  void* stream) {
+  if (!seq) return fail(RK_ERR_INVALID, "rk_dien_interest_train: null pointer");
+  if (key_rows <= 0 || ld_seq < T) return fail(RK_ERR_INVALID, "rk_dien_interest_train: bad shape T=%d", T);
+  const DienWeights w{Wg, bg, Wc, bc, A, Vg, vg, Vc, vc};
+  return launch_dien(query, ld_query, key_table, key_rows, ld_key, seq, ld_seq, 0, T, seq_len, batch, H, nh,
+                     cell_type, w, out, ld_out, att_out, ld_att, stream, "rk_dien_interest_train", true, hs, ss);
+}
+
+RK_API int rk_dien_interest_train_dense(const float* query, int64_t ld_query, const float* keys, int64_t ld_keys_b,
+                                        int64_t ld_keys_t, int32_t T, const int64_t* keys_length, int64_t batch,
+                                        int32_t H, int32_t nh, int32_t cell_type, const float* Wg, const float* bg,
+                                        const float* Wc, const float* bc, const float* A, const float* Vg,
+                                        const float* vg, const float* Vc, const float* vc, float* out,
+                                        int64_t ld_out, float* att_out, int64_t ld_att, float* hs, float* ss,
+                                        void* stream) {
+  if (T > 0 && ld_keys_b < (int64_t)T * ld_keys_t && batch > 1)
+    return fail(RK_ERR_INVALID, "rk_dien_interest_train_dense: bad shape T=%d", T);
+  const DienWeights w{Wg, bg, Wc, bc, A, Vg, vg, Vc, vc};
+  return launch_dien(query, ld_query, keys, 0, ld_keys_t, nullptr, 0, ld_keys_b, T, keys_length, batch, H, nh,
+                     cell_type, w, out, ld_out, att_out, ld_att, stream, "rk_dien_interest_train_dense", true, hs,
+                     ss);
 }

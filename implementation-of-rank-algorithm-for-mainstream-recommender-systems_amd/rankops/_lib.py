@@ -160,6 +160,24 @@ SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32]
         + [c_void_p] * 9 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
     ),
+    "rk_dien_interest_train": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32,
+         c_int32, c_int32] + [c_void_p] * 9 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "rk_dien_interest_train_dense": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32]
+        + [c_void_p] * 9 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "rk_dien_interest_backward_workspace_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "rk_dien_interest_backward": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+         c_int32, c_int32, c_int32] + [c_void_p] * 9
+        + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]
+        + [c_void_p] * 9 + [c_void_p, c_void_p, c_int64, c_void_p],
+    ),
     "rk_dice_forward": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
     "rk_bst_attention": (

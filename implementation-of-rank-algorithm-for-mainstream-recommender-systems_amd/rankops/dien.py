@@ -4,8 +4,10 @@
 `DIEN(vocab_dir, hidden_units=None, activation='dice', dropout_rate=0.1, batch_norm=True,
 custom_gru_type='AGRU', gru_output_units=8)` takes the reference's flags (dien.py:40-53) and
 `forward(dense, category, sequence, target) -> (probability, logit)` the input dictionaries of
-`rankops.DIN`.  Eval mode only: train mode raises (common.check_eval); the auxiliary loss is left
-out (the reference says it does not run, dien.py:256-300).
+`rankops.DIN`.  Training is opt-in: `DIEN(..., trainable=True)` in `model.train()` returns outputs
+attached to `rankops.train._DIENTrain` (HIP backward of the recurrence, dien.py:314-334's loop works
+with `rankops.Adam`); a default-constructed model raises in train mode (common.check_eval).  The
+auxiliary loss is left out (the reference says it does not run, dien.py:256-300).
 
 Parameters: `embeddings.*` as in DIN except that target and history share the one `feedid` table
 (shared_embedding_columns, dien.py:126); `gru.gates` / `gru.candidate` (TF GRUCell: Linear(H+nh, 2nh)
@@ -25,7 +27,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import common, ops
+from . import common, ops, train
 from .common import EngineModule, Layer, check_eval, load_vocabulary, run_tail, table_rows
 from .din import FIELDS, SEQ_KEY, Dice
 
@@ -69,13 +71,80 @@ def _convert(rc_error, H, nh, T):
     raise rc_error
 
 
+class _DIENInterest(torch.autograd.Function):
+    """dien_interest / dien_interest_gather under autograd: rk_dien_interest_train(_dense) keeps the
+    states, rk_dien_interest_backward gives dquery, dkeys and the nine weight gradients; the gather
+    form scatters dkeys into a zeroed dense table gradient (rk_embedding_backward).  `keys` is the
+    history [B,T,H] (seq None) or the table [V,H] with ids seq [B,T]; inputs already validated."""
+
+    @staticmethod
+    def forward(ctx, query, keys, seq, keys_length, cell, nh, *ws):
+        dense = seq is None
+        B, H = query.shape
+        T = keys.shape[1] if dense else seq.shape[1]
+        dev = query.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        ws = [w.contiguous() for w in ws]
+        out, att = torch.empty(B, nh, **f32), torch.empty(B, T, **f32)
+        hs, ss = torch.empty(B, T, nh, **f32), torch.empty(B, T, nh, **f32)
+        if B > 0:
+            try:
+                if dense:
+                    ops.dien_interest_train_dense(query, keys, keys_length, nh, cell, ws, out, att, hs, ss)
+                else:
+                    ops.dien_interest_train(query.data_ptr(), query.stride(0), keys, seq, keys_length, T, H, nh, cell,
+                                            ws, out.data_ptr(), out.stride(0), att, hs, ss, B, dev)
+            except ops._lib.RankOpsError as e:
+                _convert(e, H, nh, T)
+        ctx.save_for_backward(query, keys, keys_length, att, hs, ss, *ws)
+        ctx.seq, ctx.cell, ctx.nh = seq, cell, nh
+        ctx.mark_non_differentiable(att)
+        return out, att
+
+    @staticmethod
+    def backward(ctx, d_out, _d_att):
+        query, keys, keys_length, att, hs, ss, *ws = ctx.saved_tensors
+        seq, cell, nh = ctx.seq, ctx.cell, ctx.nh
+        dense = seq is None
+        B, H = query.shape
+        T = keys.shape[1] if dense else seq.shape[1]
+        dev = query.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        if B == 0:
+            return (torch.zeros_like(query), torch.zeros_like(keys), None, None, None, None,
+                    *[torch.zeros_like(w) for w in ws])
+        d_out = d_out.to(torch.float32)
+        if d_out.stride(1) != 1 or d_out.stride(0) < nh:
+            d_out = d_out.contiguous()
+        dq = torch.empty(B, H, **f32)
+        dkeys = torch.empty(B, T, H, **f32)
+        ids = None if dense else torch.empty_like(seq)
+        wgrads = ops.dien_interest_backward(query.data_ptr(), query.stride(0), keys, seq, keys.stride(0) if dense else 0,
+                                            keys_length, T, H, nh, cell, ws, hs, ss, att, d_out.data_ptr(),
+                                            d_out.stride(0), dq.data_ptr(), H, False, dkeys, B, dev, ids)
+        if dense:
+            dk = dkeys
+        elif ctx.needs_input_grad[1]:
+            dk = train.zero_grads([keys], dev)[0]
+            ops.embedding_backward([ops.table_segment(dk, ids.reshape(-1), 0)], B * T, dkeys.view(B * T, H))
+        else:
+            dk = None
+        return (dq, dk, None, None, None, None, *wgrads)
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
 def dien_interest(query, keys, keys_length, weights, cell_type="AGRU", return_attention=False):
     """dien_interest(query[B,H], keys[B,T,H], keys_length[B], weights) -> final interest state [B,nh]
     (dien.py:198-229) on rk_dien_interest_dense: TF GRUCell over the keys, attention of the hidden
     states against `A . query` (softmax over all T positions, positions t >= keys_length masked
     with -2^32+1), then the AGRU / AUGRU cell over the hidden states for t < keys_length.
     `weights` = (Wg, bg, Wc, bc, A, Vg, vg, Vc, vc) device tensors (rankops.h);
-    `return_attention` adds the attention weights [B,T]."""
+    `return_attention` adds the attention weights [B,T].  Differentiable w.r.t. query, keys and the
+    weights (the attention output is not): with grad mode on and any of them requiring grad the
+    call goes through rk_dien_interest_train_dense / rk_dien_interest_backward."""
     cell = _cell(cell_type)
     query = ops.as_f32(query, "query")
     keys = ops.as_f32(keys, "keys")
@@ -91,6 +160,9 @@ def dien_interest(query, keys, keys_length, weights, cell_type="AGRU", return_at
         keys = keys.contiguous()
     if query.stride(1) != 1:
         query = query.contiguous()
+    if _wants_grad(query, keys, *weights):
+        out, att = _DIENInterest.apply(query, keys, None, keys_length.contiguous(), cell, nh, *ws)
+        return (out, att) if return_attention else out
     out = torch.empty(B, nh, device=keys.device, dtype=torch.float32)
     att = torch.empty(B, T, device=keys.device, dtype=torch.float32) if return_attention else None
     if B > 0:
@@ -103,7 +175,8 @@ def dien_interest(query, keys, keys_length, weights, cell_type="AGRU", return_at
 
 def dien_interest_gather(query, table, seq, keys_length, weights, cell_type="AGRU", return_attention=False):
     """dien_interest with the history given as (embedding table [V,H], ids [B,T]): the gather
-    happens inside the kernel (rk_dien_interest); ids at t >= keys_length are never read."""
+    happens inside the kernel (rk_dien_interest); ids at t >= keys_length are never read.
+    Differentiable like dien_interest; the table's gradient is dense (nn.Embedding's)."""
     cell = _cell(cell_type)
     query = ops.as_f32(query, "query")
     table = ops.as_f32(table, "table")
@@ -123,6 +196,9 @@ def dien_interest_gather(query, table, seq, keys_length, weights, cell_type="AGR
         table = table.contiguous()
     if query.stride(1) != 1:
         query = query.contiguous()
+    if _wants_grad(query, table, *weights):
+        out, att = _DIENInterest.apply(query, table, seq.contiguous(), keys_length.contiguous(), cell, nh, *ws)
+        return (out, att) if return_attention else out
     out = torch.empty(B, nh, device=query.device, dtype=torch.float32)
     att = torch.empty(B, T, device=query.device, dtype=torch.float32) if return_attention else None
     if B > 0:
@@ -144,8 +220,11 @@ def _tf_linear(in_features: int, out_features: int, bias_value: float = 0.0) -> 
 
 class DIEN(EngineModule):
     def __init__(self, vocab_dir, hidden_units=None, activation='dice', dropout_rate=0.1, batch_norm=True,
-                 custom_gru_type='AGRU', gru_output_units=8, *, vocab_sizes=None, embedding_dim=16):
+                 custom_gru_type='AGRU', gru_output_units=8, *, vocab_sizes=None, embedding_dim=16,
+                 trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)  # train mode is opt-in; parameters and initialisation are the same
+        self._dropout = train.DropoutStreams()
         if hidden_units is None:
             hidden_units = [512, 256, 128]
         _cell(custom_gru_type)
@@ -211,21 +290,27 @@ class DIEN(EngineModule):
         dev = dense_cols[0].device
         segs = [ops.dense_segment(v, 1, i) for i, v in enumerate(dense_cols)]
         col = len(dense_cols)
+        lookups = []  # (table weight, index, column) for the training backward
         for name, emb in self.embeddings.items():
             if name != "feedid" and name in category:
-                segs.append(ops.table_segment(emb.weight, ops.as_index(category[name], f"category[{name!r}]"), col))
+                idx = ops.as_index(category[name], f"category[{name!r}]")
+                segs.append(ops.table_segment(emb.weight, idx, col))
+                lookups.append((emb.weight, idx, col))
                 col += emb.embedding_dim
         tgt = self.embeddings["feedid"]
-        segs.append(ops.table_segment(tgt.weight, ops.as_index(target["feedid"], "target['feedid']"), col))
+        tgt_idx = ops.as_index(target["feedid"], "target['feedid']")
+        segs.append(ops.table_segment(tgt.weight, tgt_idx, col))
+        lookups.append((tgt.weight, tgt_idx, col))
         q_col = col
         state_col = q_col + tgt.embedding_dim
         seq = ops.as_index(sequence[SEQ_KEY], f"sequence[{SEQ_KEY!r}]").contiguous()
         seq_len = ops.as_index(sequence[f"{SEQ_KEY}_length"], "sequence length").contiguous()
-        return dict(B=B, dev=dev, segs=segs, q_col=q_col, state_col=state_col,
+        return dict(B=B, dev=dev, segs=segs, lookups=lookups, q_col=q_col, state_col=state_col,
                     width=state_col + self.gru_output_units, H=tgt.embedding_dim, seq=seq, seq_len=seq_len)
 
     def forward(self, dense, category, sequence, target, return_attention=False):
-        check_eval(self)
+        if not self.trainable:
+            check_eval(self)
         tgt = target.get("feedid", None) if isinstance(target, dict) else None
         if isinstance(tgt, torch.Tensor) and tgt.shape[0] == 0:  # an empty batch: nothing to launch
             dev = ops.require_gpu(tgt, "target['feedid']").device
@@ -237,6 +322,13 @@ class DIEN(EngineModule):
                              f"{self._tail[0].linear.in_features}")
         T = pl["seq"].shape[1]
         _check_envelope(H, nh, T)
+        if self.training:  # Dice / BatchNorm batch statistics, Dropout, HIP backward (rankops.train)
+            grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+            try:
+                prob, logit, att = train.dien_train_forward(self, pl, grad)
+            except ops._lib.RankOpsError as e:
+                _convert(e, H, nh, T)
+            return (prob, logit, att) if return_attention else (prob, logit)
         logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
         prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
         row = torch.empty(B, width, device=dev, dtype=torch.float32)

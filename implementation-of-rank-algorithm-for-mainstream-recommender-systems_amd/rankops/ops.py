@@ -299,6 +299,55 @@ def dien_interest_dense(query, keys, keys_length, nh, cell_type, weights, out, a
                                      _lib.stream_of(keys)), "rk_dien_interest_dense")
 
 
+def dien_interest_train(query_ptr, ld_query, key_table, seq, seq_len, T, H, nh, cell_type, weights, out_ptr, ld_out,
+                        att, hs, ss, batch, device):
+    """rk_dien_interest_train: rk_dien_interest that also keeps the extractor states hs [batch, T, nh],
+    the evolution states ss [batch, T, nh] and the attention weights att [batch, T] for the backward."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    check(lib.rk_dien_interest_train(query_ptr, ld_query, ptr(key_table), key_table.shape[0], key_table.stride(0),
+                                     ptr(seq), seq.stride(0), T, ptr(seq_len), batch, H, nh, cell_type,
+                                     *[ptr(w) for w in weights], out_ptr, ld_out, ptr(att), att.stride(0), ptr(hs),
+                                     ptr(ss), _lib.raw_stream(device)), "rk_dien_interest_train")
+
+
+def dien_interest_train_dense(query, keys, keys_length, nh, cell_type, weights, out, att, hs, ss):
+    """rk_dien_interest_train_dense: the same over keys [B, T, H] (rows 16-B aligned)."""
+    lib = _lib.load()
+    _lib.ensure_device(keys.device)
+    B, T, H = keys.shape
+    check(lib.rk_dien_interest_train_dense(ptr(query), query.stride(0), ptr(keys), keys.stride(0), keys.stride(1), T,
+                                           ptr(keys_length), B, H, nh, cell_type, *[ptr(w) for w in weights],
+                                           ptr(out), out.stride(0), ptr(att), att.stride(0), ptr(hs), ptr(ss),
+                                           _lib.stream_of(keys)), "rk_dien_interest_train_dense")
+
+
+def dien_interest_backward(query_ptr, ld_query, keys, seq, ld_keys_b, seq_len, T, H, nh, cell_type, weights, hs, ss,
+                           att, d_out_ptr, ld_dout, dquery_ptr, ld_dquery, accumulate_dquery, dkeys, batch, device,
+                           seq_masked=None):
+    """rk_dien_interest_backward: backprop through time of the interest recurrence.  `keys` is the
+    table [V, H] with ids `seq` [batch, T], or the dense history [batch, T, H] with seq None and
+    ld_keys_b its batch stride; d_out / dquery are strided pointers (they may lie in one row-gradient
+    buffer), dquery is added to when accumulate_dquery; dkeys [batch, T, H] is written (rows past the
+    length zero); seq_masked [batch, T] int64, when given, receives the ids with 0 past the length
+    (what the embedding scatter of dkeys takes).  Returns the nine weight gradients (Wg, bg, Wc, bc, A, Vg, vg, Vc, vc)."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    grads = [torch.empty_like(w) for w in weights]
+    nws = lib.rk_dien_interest_backward_workspace_floats(batch, T, H, nh)
+    ws = torch.empty(max(nws, 1), device=device, dtype=torch.float32)
+    dense = seq is None
+    check(lib.rk_dien_interest_backward(query_ptr, ld_query, ptr(keys), 0 if dense else keys.shape[0],
+                                        keys.stride(1) if dense else keys.stride(0), ptr(seq),
+                                        0 if dense else seq.stride(0), ld_keys_b, T, ptr(seq_len), batch, H, nh,
+                                        cell_type, *[ptr(w) for w in weights], ptr(hs), ptr(ss), ptr(att),
+                                        att.stride(0), d_out_ptr, ld_dout, dquery_ptr, ld_dquery,
+                                        int(accumulate_dquery), ptr(dkeys), *[ptr(g) for g in grads], ptr(seq_masked),
+                                        ptr(ws), nws,
+                                        _lib.raw_stream(device)), "rk_dien_interest_backward")
+    return grads
+
+
 def dice_forward(x, scale, shift, alpha, y):
     lib = _lib.load()
     check(lib.rk_dice_forward(ptr(x), x.stride(0), x.shape[0], x.shape[1], ptr(scale), ptr(shift), ptr(alpha),

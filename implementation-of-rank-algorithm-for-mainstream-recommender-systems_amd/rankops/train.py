@@ -461,6 +461,86 @@ def din_units(model):
     return units
 
 
+def din_tail_forward(model, x, units, seed, slot):
+    """The fcn units Linear -> Dice / PReLU -> BatchNorm1d -> Dropout with batch statistics over the
+    row x [B, width], then output_layer + sigmoid (din.py:272-288, the tail DIEN shares); returns
+    (per-unit saved tensors, prob, logit)."""
+    B, dev = x.shape[0], x.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    saved = []
+    h = x
+    for u, (lin, dice, bn, p) in enumerate(units):
+        n, K = lin.out_features, lin.in_features
+        z = torch.empty(B, n, **f32)
+        ops.gemm(False, False, B, n, K, h, h.stride(0), lin.weight, lin.weight.stride(0), z)
+        y1 = torch.empty(B, n, **f32)
+        m1, s1 = torch.empty(n, **f32), torch.empty(n, **f32)
+        if isinstance(dice, torch.nn.PReLU):
+            ops.prelu_train_forward(z, lin.bias, dice, y1)
+        else:
+            ops.dice_train_forward(z, lin.bias, dice, y1, m1, s1,
+                                   torch.empty(2 * n, device=dev, dtype=torch.float64))
+        y2, m2, s2 = y1, m1, s1
+        if bn is not None or p > 0:
+            y2 = torch.empty(B, n, **f32)
+            m2, s2 = torch.empty(n, **f32), torch.empty(n, **f32)
+            ops.bn_act_train_forward(y1, None, bn, False, p, seed + u, slot, y2, m2, s2,
+                                     torch.empty(2 * n, device=dev, dtype=torch.float64))
+        saved.append((z, y1, m1, s1, y2, m2, s2))
+        h = y2
+    logit = torch.empty(B, 1, **f32)
+    prob = torch.empty(B, 1, **f32)
+    ops.mlp_forward(h, [], ops.make_epilogue(head_w=model.output_layer.weight, head_b=model.output_layer.bias,
+                                             head_logit=logit, head_prob=prob))
+    return saved, prob, logit
+
+
+def din_tail_backward(model, dprob, dlogit, prob, x, units, saved, seed, slot):
+    """Backward of din_tail_forward: rk_logit_head_backward, then the units last to first; returns
+    (dL/dx [B, width], per-unit grads [dW, db, dalpha, (dgamma, dbeta)], dw_out, db_out)."""
+    B, dev = x.shape[0], x.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    last = saved[-1][4] if saved else x
+    dy = torch.empty_like(last)
+    w_out = model.output_layer.weight
+    dw_out = torch.empty_like(w_out)
+    db_out = torch.empty(1, **f32)
+    ops.logit_head_backward(_grad_out(dlogit, prob), _grad_out(dprob, prob), prob, last, None, w_out, dy, None,
+                            dw_out, db_out)
+    unit_grads = [None] * len(units)
+    for u in range(len(units) - 1, -1, -1):
+        lin, dice, bn, p = units[u]
+        z, y1, m1, s1, y2, m2, s2 = saved[u]
+        n, K = lin.out_features, lin.in_features
+        h_in = saved[u - 1][4] if u > 0 else x
+        dy1 = dy
+        dg = dbt = None
+        if bn is not None or p > 0:
+            dy1 = torch.empty(B, n, **f32)
+            if bn is not None:
+                dg = torch.empty(n, **f32) if bn.weight is not None else None
+                dbt = torch.empty(n, **f32) if bn.bias is not None else None
+            ops.bn_act_backward(dy, y1, None, bn, False, p, seed + u, slot, m2, s2,
+                                torch.empty(2 * n, device=dev, dtype=torch.float64), dy1, dg, dbt)
+        dz = torch.empty(B, n, **f32)
+        if isinstance(dice, torch.nn.PReLU):
+            dalpha = torch.empty_like(dice.weight)
+            ops.prelu_backward(dy1, z, lin.bias, dice, torch.empty(dice.weight.numel(), device=dev,
+                                                                   dtype=torch.float64), dz, dalpha)
+        else:
+            dalpha = torch.empty(n, **f32)
+            ops.dice_backward(dy1, z, lin.bias, dice, m1, s1, torch.empty(3 * n, device=dev, dtype=torch.float64),
+                              dz, dalpha)
+        dW = torch.empty(n, K, **f32)
+        db = torch.empty(n, **f32)
+        ops.gemm(True, True, n, K, B, dz, dz.stride(0), h_in, h_in.stride(0), dW, row_sums=db)
+        dx = torch.empty(B, K, **f32)
+        ops.gemm(False, True, B, K, n, dz, dz.stride(0), lin.weight, lin.weight.stride(0), dx)
+        unit_grads[u] = [dW, db, dalpha] + ([t for t in (dg, dbt) if t is not None] if bn is not None else [])
+        dy = dx
+    return dy, unit_grads, dw_out, db_out
+
+
 class _DINTrain(torch.autograd.Function):
     """DIN forward + backward in train mode (din.py:294-323): gather, din_attention (att_net's
     layers as GEMMs on rk_linear with the activations kept for the backward, the weights drawn per
@@ -490,31 +570,7 @@ class _DINTrain(torch.autograd.Function):
         ops.din_att_pool_forward(a2, w3.reshape(-1), b3, keys, seq_len, T, H, model.use_softmax, wts, x, att_col)
         units = din_units(model)
         seed, slot = model._dropout.next(dev)
-        saved = []
-        h = x
-        for u, (lin, dice, bn, p) in enumerate(units):
-            n, K = lin.out_features, lin.in_features
-            z = torch.empty(B, n, **f32)
-            ops.gemm(False, False, B, n, K, h, h.stride(0), lin.weight, lin.weight.stride(0), z)
-            y1 = torch.empty(B, n, **f32)
-            m1, s1 = torch.empty(n, **f32), torch.empty(n, **f32)
-            if isinstance(dice, torch.nn.PReLU):
-                ops.prelu_train_forward(z, lin.bias, dice, y1)
-            else:
-                ops.dice_train_forward(z, lin.bias, dice, y1, m1, s1,
-                                       torch.empty(2 * n, device=dev, dtype=torch.float64))
-            y2, m2, s2 = y1, m1, s1
-            if bn is not None or p > 0:
-                y2 = torch.empty(B, n, **f32)
-                m2, s2 = torch.empty(n, **f32), torch.empty(n, **f32)
-                ops.bn_act_train_forward(y1, None, bn, False, p, seed + u, slot, y2, m2, s2,
-                                         torch.empty(2 * n, device=dev, dtype=torch.float64))
-            saved.append((z, y1, m1, s1, y2, m2, s2))
-            h = y2
-        logit = torch.empty(B, 1, **f32)
-        prob = torch.empty(B, 1, **f32)
-        ops.mlp_forward(h, [], ops.make_epilogue(head_w=model.output_layer.weight, head_b=model.output_layer.bias,
-                                                 head_logit=logit, head_prob=prob))
+        saved, prob, logit = din_tail_forward(model, x, units, seed, slot)
         l2 = torch.zeros((), **f32)
         if pl["want_l2"]:
             ops.row_l2norm_mean(x, cat_col0, width - cat_col0, float(model.l2_lambda), l2)
@@ -530,45 +586,8 @@ class _DINTrain(torch.autograd.Function):
         B, dev, H = pl["B"], pl["dev"], pl["H"]
         T = keys.shape[1]
         f32 = dict(device=dev, dtype=torch.float32)
-        last = saved[-1][4] if saved else x
-        dy = torch.empty_like(last)
-        w_out = model.output_layer.weight
-        dw_out = torch.empty_like(w_out)
-        db_out = torch.empty(1, **f32)
-        ops.logit_head_backward(_grad_out(dlogit, prob), _grad_out(dprob, prob), prob, last, None, w_out, dy, None,
-                                dw_out, db_out)
-        unit_grads = [None] * len(units)
-        for u in range(len(units) - 1, -1, -1):
-            lin, dice, bn, p = units[u]
-            z, y1, m1, s1, y2, m2, s2 = saved[u]
-            n, K = lin.out_features, lin.in_features
-            h_in = saved[u - 1][4] if u > 0 else x
-            dy1 = dy
-            dg = dbt = None
-            if bn is not None or p > 0:
-                dy1 = torch.empty(B, n, **f32)
-                if bn is not None:
-                    dg = torch.empty(n, **f32) if bn.weight is not None else None
-                    dbt = torch.empty(n, **f32) if bn.bias is not None else None
-                ops.bn_act_backward(dy, y1, None, bn, False, p, ctx.seed + u, slot, m2, s2,
-                                    torch.empty(2 * n, device=dev, dtype=torch.float64), dy1, dg, dbt)
-            dz = torch.empty(B, n, **f32)
-            if isinstance(dice, torch.nn.PReLU):
-                dalpha = torch.empty_like(dice.weight)
-                ops.prelu_backward(dy1, z, lin.bias, dice, torch.empty(dice.weight.numel(), device=dev,
-                                                                       dtype=torch.float64), dz, dalpha)
-            else:
-                dalpha = torch.empty(n, **f32)
-                ops.dice_backward(dy1, z, lin.bias, dice, m1, s1, torch.empty(3 * n, device=dev, dtype=torch.float64),
-                                  dz, dalpha)
-            dW = torch.empty(n, K, **f32)
-            db = torch.empty(n, **f32)
-            ops.gemm(True, True, n, K, B, dz, dz.stride(0), h_in, h_in.stride(0), dW, row_sums=db)
-            dx = torch.empty(B, K, **f32)
-            ops.gemm(False, True, B, K, n, dz, dz.stride(0), lin.weight, lin.weight.stride(0), dx)
-            unit_grads[u] = [dW, db, dalpha] + ([t for t in (dg, dbt) if t is not None] if bn is not None else [])
-            dy = dx
-        dxr = dy  # dL/d[dense | category | target | attention]
+        dxr, unit_grads, dw_out, db_out = din_tail_backward(model, dprob, dlogit, prob, x, units, saved, ctx.seed, slot)
+        # dxr = dL/d[dense | category | target | attention]
         if pl["want_l2"] and dl2 is not None:
             ops.row_l2norm_backward(x, pl["cat_col0"], pl["width"] - pl["cat_col0"], float(model.l2_lambda) / B,
                                     dl2.to(torch.float32).reshape(1).contiguous(), dxr)
@@ -627,6 +646,104 @@ def din_train_forward(model, pl, att):
         looks.append((slot_of(w), idx, col))
     pl = dict(pl, seq_slot=slot_of(model.embeddings[pl["seq_key"]].weight))
     return _DINTrain.apply(model, pl, att, (weights, looks), *weights, *_din_params(model, units))
+
+
+# ---------------------------------------------------------------- DIEN
+
+def dien_tail_forward(model, pl, x, att, hs=None, ss=None):
+    """DIEN's train-mode forward over the gathered row x: the interest state into its last nh columns
+    (the train kernel when hs / ss are given, which keeps them for the backward), then DIN's tail."""
+    from .dien import _cell
+    B, dev, H, nh, width = pl["B"], pl["dev"], pl["H"], model.gru_output_units, pl["width"]
+    T = pl["seq"].shape[1]
+    table = model.embeddings["feedid"].weight
+    args = (ops._lib.fptr(x, pl["q_col"]), width, table, pl["seq"], pl["seq_len"], T, H, nh,
+            _cell(model.custom_gru_type), model.interest_weights(), ops._lib.fptr(x, pl["state_col"]), width, att)
+    if hs is None:
+        ops.dien_interest(*args, B, dev)
+    else:
+        ops.dien_interest_train(*args, hs, ss, B, dev)
+    units = din_units(model)
+    seed, slot = model._dropout.next(dev)
+    saved, prob, logit = din_tail_forward(model, x, units, seed, slot)
+    return units, seed, slot, saved, prob, logit
+
+
+class _DIENTrain(torch.autograd.Function):
+    """DIEN forward + backward in train mode (dien.py:166-254,314-334): rk_concat_gather, the train
+    interest forward (GRU, attention, AGRU / AUGRU, states kept), DIN's tail with batch statistics
+    and Dropout; backward: head, units, rk_dien_interest_backward reading d(state) from the row
+    gradient's state columns and adding dquery into its target columns, then the embedding scatters.
+    Inputs after the fixed arguments: the distinct tables, the nine interest weights, `_din_params`."""
+
+    @staticmethod
+    def forward(ctx, model, pl, emb_plan, *params):
+        B, dev, nh, width = pl["B"], pl["dev"], model.gru_output_units, pl["width"]
+        T = pl["seq"].shape[1]
+        f32 = dict(device=dev, dtype=torch.float32)
+        x = torch.empty(B, width, **f32)
+        ops.concat_gather(pl["segs"], B, x)  # [dense | category | target | .]
+        att = torch.empty(B, T, **f32)
+        hs, ss = torch.empty(B, T, nh, **f32), torch.empty(B, T, nh, **f32)
+        units, seed, slot, saved, prob, logit = dien_tail_forward(model, pl, x, att, hs, ss)
+        ctx.model, ctx.pl, ctx.units, ctx.seed, ctx.emb_plan = model, pl, units, seed, emb_plan
+        ctx.save_for_backward(x, att, hs, ss, prob, slot, *[t for s in saved for t in s])
+        ctx.mark_non_differentiable(att)
+        return prob, logit, att
+
+    @staticmethod
+    def backward(ctx, dprob, dlogit, _datt):
+        from .dien import _cell
+        model, pl, units = ctx.model, ctx.pl, ctx.units
+        x, att, hs, ss, prob, slot, *flat = ctx.saved_tensors
+        saved = [tuple(flat[7 * u:7 * u + 7]) for u in range(len(units))]
+        B, dev, H, nh, width = pl["B"], pl["dev"], pl["H"], model.gru_output_units, pl["width"]
+        seq = pl["seq"]
+        T = seq.shape[1]
+        dxr, unit_grads, dw_out, db_out = din_tail_backward(model, dprob, dlogit, prob, x, units, saved, ctx.seed, slot)
+        # dxr = dL/d[dense | category | target | state]: d(state) is read in place, dquery added in place
+        weights, looks = ctx.emb_plan
+        table = model.embeddings["feedid"].weight
+        dkeys = torch.empty(B, T, H, device=dev, dtype=torch.float32)
+        ids = torch.empty_like(seq)  # the history ids with 0 past the length (poisoned tails never scatter)
+        wgrads = ops.dien_interest_backward(ops._lib.fptr(x, pl["q_col"]), width, table, seq, 0, pl["seq_len"], T, H,
+                                            nh, _cell(model.custom_gru_type), model.interest_weights(), hs, ss, att,
+                                            ops._lib.fptr(dxr, pl["state_col"]), width,
+                                            ops._lib.fptr(dxr, pl["q_col"]), width, True, dkeys, B, dev, ids)
+        # one zeroed buffer per distinct table; feedid takes the target lookup and the history scatter
+        # (key rows past the length are exact zeros: the zero-skipping scatter stays contention-free)
+        grads = zero_grads(weights, dev)
+        ops.embedding_backward([ops.table_segment(grads[k], i, col) for k, i, col in looks], B, dxr)
+        ops.embedding_backward([ops.table_segment(grads[pl["seq_slot"]], ids.reshape(-1), 0)], B * T,
+                               dkeys.view(B * T, H))
+        return (None, None, None, *grads, *wgrads, *[t for g in unit_grads for t in g], dw_out, db_out)
+
+
+def dien_train_forward(model, pl, grad: bool):
+    """DIEN train-mode forward (rankops.DIEN.forward in model.train()): (prob, logit, attention),
+    attached to _DIENTrain when `grad`; otherwise the same launches with nothing kept."""
+    if not grad:
+        B, dev = pl["B"], pl["dev"]
+        x = torch.empty(B, pl["width"], device=dev, dtype=torch.float32)
+        ops.concat_gather(pl["segs"], B, x)
+        att = torch.empty(B, pl["seq"].shape[1], device=dev, dtype=torch.float32)
+        _, _, _, _, prob, logit = dien_tail_forward(model, pl, x, att)
+        return prob, logit, att
+    units = din_units(model)
+    weights, looks = [], []
+
+    def slot_of(w):
+        for k, t in enumerate(weights):
+            if t is w:
+                return k
+        weights.append(w)
+        return len(weights) - 1
+
+    for w, idx, col in pl["lookups"]:
+        looks.append((slot_of(w), idx, col))
+    pl = dict(pl, seq_slot=slot_of(model.embeddings["feedid"].weight))
+    return _DIENTrain.apply(model, pl, (weights, looks), *weights, *model.interest_weights(),
+                            *_din_params(model, units))
 
 
 # ---------------------------------------------------------------- AFM

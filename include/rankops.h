@@ -28,6 +28,8 @@
  *   rk_dien_interest   DIEN's GRU + attention + AGRU/AUGRU with the history gathered from the table
  *                      DIEN/dien.py:198-229, custom_grucell.py:19-167, rnn.py:201-219
  *   rk_dien_interest_dense  the same over a dense history tensor keys[B,T,H]
+ *   rk_dien_interest_train(_dense), rk_dien_interest_backward  the train forward that keeps the
+ *                      states, and backprop through time of the recurrence   DIEN/dien.py:314-334
  *   rk_dice_forward    Dice.forward() in eval (BatchNorm running statistics)           din.py:26-36
  *   rk_row_l2norm_mean DIN mini-batch-aware l2 term          din.py:318-322
  *   rk_afm_forward     AFM.forward()                         afm.py:92-119
@@ -275,6 +277,55 @@ int rk_dien_interest_dense(const float* query, int64_t ld_query, const float* ke
                            const float* Wc, const float* bc, const float* A, const float* Vg,
                            const float* vg, const float* Vc, const float* vc, float* out,
                            int64_t ld_out, float* att_out, int64_t ld_att, void* stream);
+
+/* Train forward of rk_dien_interest / rk_dien_interest_dense: the same launch (out is bit-equal to
+ * the eval entry points'), which also keeps what rk_dien_interest_backward needs: the extractor
+ * states hs [batch, T, nh], the evolution states ss [batch, T, nh] (rows t >= seq_len[b] zero in
+ * both) and the attention weights att_out [batch, T] (required here).  hs, ss 16-B aligned.
+ * Same envelope.                                                                                */
+int rk_dien_interest_train(const float* query, int64_t ld_query, const float* key_table,
+                           int64_t key_rows, int64_t ld_key, const int64_t* seq, int64_t ld_seq,
+                           int32_t T, const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                           int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                           const float* bc, const float* A, const float* Vg, const float* vg,
+                           const float* Vc, const float* vc, float* out, int64_t ld_out,
+                           float* att_out, int64_t ld_att, float* hs, float* ss, void* stream);
+int rk_dien_interest_train_dense(const float* query, int64_t ld_query, const float* keys,
+                                 int64_t ld_keys_b, int64_t ld_keys_t, int32_t T,
+                                 const int64_t* keys_length, int64_t batch, int32_t H, int32_t nh,
+                                 int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                                 const float* bc, const float* A, const float* Vg, const float* vg,
+                                 const float* Vc, const float* vc, float* out, int64_t ld_out,
+                                 float* att_out, int64_t ld_att, float* hs, float* ss, void* stream);
+
+/* Backward of the interest recurrence (backprop through time, t = seq_len-1 ... 0) given
+ * d_out[b, 0:nh] = dL/d(out) at d_out + b*ld_dout and the forward's inputs, hs, ss and att:
+ *   dquery[b, 0:H] at dquery + b*ld_dquery (added to when accumulate_dquery; d_out and dquery may
+ *   lie in one row-gradient buffer), dkeys [batch, T, H] contiguous = dL/d(key row t of sample b)
+ *   (rows t >= seq_len[b] exact zeros; every row written), and the nine weight gradients, shaped
+ *   like the weights (overwritten).  A sample with seq_len 0 has zero gradients.
+ * Key source: seq != NULL: keys = the table [key_rows, ld_key], ids seq [batch, ld_seq] (an
+ * out-of-range id at t < seq_len reads the zero row, as in the forward); seq == NULL: keys = the
+ * dense history, row t of sample b at keys + b*ld_keys_b + t*ld_key.
+ * seq_masked (NULL, or [batch, T] with seq): the ids with 0 at t >= seq_len[b], the index list
+ * for rk_embedding_backward of dkeys into the table's gradient.
+ * One chain launch (one 16-lane row per sample) that also writes the per-step pre-activation
+ * gradients and operand rows into the workspace; dkeys is two rk_gemm products and the weight
+ * gradients are rk_gemm_wgrad products over those rows: no float atomics, deterministic.
+ * workspace: rk_dien_interest_backward_workspace_floats(batch, T, H, nh) floats, 16-B aligned.
+ * Envelope and alignment as the forward (else RK_ERR_UNSUPPORTED).                              */
+int64_t rk_dien_interest_backward_workspace_floats(int64_t batch, int32_t T, int32_t H, int32_t nh);
+int rk_dien_interest_backward(const float* query, int64_t ld_query, const float* keys, int64_t key_rows,
+                              int64_t ld_key, const int64_t* seq, int64_t ld_seq, int64_t ld_keys_b,
+                              int32_t T, const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                              int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                              const float* bc, const float* A, const float* Vg, const float* vg,
+                              const float* Vc, const float* vc, const float* hs, const float* ss,
+                              const float* att, int64_t ld_att, const float* d_out, int64_t ld_dout,
+                              float* dquery, int64_t ld_dquery, int32_t accumulate_dquery, float* dkeys,
+                              float* dWg, float* dbg, float* dWc, float* dbc, float* dA, float* dVg,
+                              float* dvg, float* dVc, float* dvc, int64_t* seq_masked, float* workspace,
+                              int64_t workspace_floats, void* stream);
 
 /* Dice (din.py:26-36) in eval: p = sigmoid(x * bn_scale + bn_shift) with the BatchNorm folded
  * by rk_bn_fold, y = alpha * (1 - p) * x + p * x;  x, y: [rows, n].                          */

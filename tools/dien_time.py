@@ -1,7 +1,9 @@
 """DIEN at the reference shape (B 4096, T 50, H 16, nh 8, WeChat vocabulary), both cells: the time
 of one rk_dien_interest launch, of the whole rankops.DIEN eval forward, and — the baseline, what a
 user has without the kernel — of the same forward written as eager torch ops on the same GPU in
-the same process (the per-step loop of tests/dien_ref.py in fp32).
+the same process (the per-step loop of tests/dien_ref.py in fp32).  Then the train step of
+rankops.DIEN(trainable=True): forward + backward + rankops.Adam, eager and as one hipGraph, against
+that loop with a train-mode tail differentiated by torch autograd (torch.optim.Adam, fused).
 
 Device times are HIP events around hipGraph replays (the host's launch cost excluded); the eager
 loop is timed both as it runs (host clock around a synchronise: its ~1,300 launches are
@@ -37,8 +39,21 @@ def shader_clock():
     return None
 
 
-def graph_avg_ms(fn, iters=20):
-    g, _ = bench.graph_of(fn)
+def grad_graph_of(fn):
+    """bench.graph_of with grad mode left on (a whole train step: forward, backward, optimizer)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g
+
+
+def graph_avg_ms(fn, iters=20, grad=False):
+    g = grad_graph_of(fn) if grad else bench.graph_of(fn)[0]
     st = torch.cuda.current_stream()
     g.replay()
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -58,6 +73,64 @@ def host_avg_ms(fn, iters=5):
         fn()
     torch.cuda.synchronize()
     return 1e3 * (time.perf_counter() - t0) / iters
+
+
+def train_step_times(cell, inp):
+    """Engine train step (eager call and hipGraph replay) and the eager-autograd baseline, in us."""
+    import torch.nn.functional as F
+    args = (inp["dense"], inp["category"], inp["sequence"], inp["target"])
+    label = (torch.rand(B, device="cuda") < 0.3).float()
+    crit = torch.nn.BCELoss()
+    out = {}
+    for mode in ("eager", "graph"):
+        torch.manual_seed(0)
+        m = rankops.DIEN(None, custom_gru_type=cell, vocab_sizes=H.WECHAT_VOCAB, trainable=True).cuda().train()
+        opt = rankops.Adam(m.parameters(), lr=1e-3, capturable=(mode == "graph"))
+
+        def step():
+            opt.zero_grad(set_to_none=False)
+            prob, _ = m(*args)
+            crit(prob.squeeze(), label).backward()
+            opt.step()
+
+        step()  # allocates gradients and optimizer state
+        torch.cuda.synchronize()
+        if mode == "eager":
+            out["train_step_eager_us"] = 1e3 * host_avg_ms(step, iters=20)
+        else:
+            out["train_step_graph_us"] = 1e3 * graph_avg_ms(step, iters=20, grad=True)
+    # baseline: the dien_ref loop + a train-mode tail as torch ops, autograd, torch.optim.Adam
+    torch.manual_seed(0)
+    m = rankops.DIEN(None, custom_gru_type=cell, vocab_sizes=H.WECHAT_VOCAB).cuda().train()
+    p = dict(m.named_parameters())
+    opt = torch.optim.Adam(m.parameters(), lr=1e-3, fused=True)
+    seq = inp["sequence"]
+
+    def torch_step():
+        opt.zero_grad(set_to_none=False)
+        cols = [v.reshape(-1, 1) for v in inp["dense"].values()]
+        cols += [m.embeddings[f](inp["category"][f]) for f in dien_ref.CATEGORY if f in inp["category"]]
+        e_target = m.embeddings["feedid"](inp["target"]["feedid"])
+        state, _, _ = dien_ref.interest(e_target, m.embeddings["feedid"](seq[dien_ref.SEQ_KEY]),
+                                        seq[f"{dien_ref.SEQ_KEY}_length"], m.interest_weights(), cell,
+                                        dtype=torch.float32)
+        x = torch.cat(cols + [e_target, state], 1)
+        for layer in m.fcn:
+            if isinstance(layer, rankops.din.Dice):  # Dice with batch statistics as torch ops
+                g = torch.sigmoid(F.batch_norm(x, layer.bn.running_mean, layer.bn.running_var, None, None, True,
+                                               layer.bn.momentum, 1e-5))
+                x = layer.alpha * (1 - g) * x + g * x
+            else:
+                x = layer(x)
+        crit(torch.sigmoid(m.output_layer(x)).squeeze(), label).backward()
+        opt.step()
+
+    torch_step()
+    torch.cuda.synchronize()
+    out["torch_autograd_step_eager_us"] = 1e3 * host_avg_ms(torch_step, iters=3)
+    out["torch_step_over_train_step_eager"] = out["torch_autograd_step_eager_us"] / out["train_step_eager_us"]
+    out["torch_step_over_train_step_graph"] = out["torch_autograd_step_eager_us"] / out["train_step_graph_us"]
+    return out
 
 
 def main():
@@ -93,14 +166,34 @@ def main():
                                   pl["seq_len"], T, 16, 8, ops.DIEN_CELLS[cell], w,
                                   _lib.fptr(row, pl["state_col"]), pl["width"], None, B, row.device)
 
+            # the train forward and the backward of the recurrence alone (chain launch + its GEMMs)
+            f32 = dict(device="cuda", dtype=torch.float32)
+            att, hs, ss = torch.empty(B, T, **f32), torch.empty(B, T, 8, **f32), torch.empty(B, T, 8, **f32)
+            drow, dkeys = torch.randn(B, pl["width"], **f32), torch.empty(B, T, 16, **f32)
+
+            def launch_train():
+                ops.dien_interest_train(_lib.fptr(row, pl["q_col"]), pl["width"], m.embeddings["feedid"].weight,
+                                        pl["seq"], pl["seq_len"], T, 16, 8, ops.DIEN_CELLS[cell], w,
+                                        _lib.fptr(row, pl["state_col"]), pl["width"], att, hs, ss, B, row.device)
+
+            def launch_backward():
+                ops.dien_interest_backward(_lib.fptr(row, pl["q_col"]), pl["width"], m.embeddings["feedid"].weight,
+                                           pl["seq"], 0, pl["seq_len"], T, 16, 8, ops.DIEN_CELLS[cell], w, hs, ss, att,
+                                           _lib.fptr(drow, pl["state_col"]), pl["width"],
+                                           _lib.fptr(drow, pl["q_col"]), pl["width"], True, dkeys, B, row.device)
+
+            launch_train()
             r = {"logit_max_abs_diff_vs_eager_fp32": diff,
                  "interest_launch_us": 1e3 * bench.graph_kernel_avg_ms(launch),
+                 "interest_train_launch_us": 1e3 * bench.graph_kernel_avg_ms(launch_train),
+                 "interest_backward_us": 1e3 * bench.graph_kernel_avg_ms(launch_backward),
                  "forward_graph_us": 1e3 * graph_avg_ms(lambda: m(*args)),
                  "forward_eager_call_us": 1e3 * host_avg_ms(lambda: m(*args), iters=50),
                  "torch_loop_graph_us": 1e3 * graph_avg_ms(eager, iters=5),
                  "torch_loop_eager_us": 1e3 * host_avg_ms(eager)}
         r["torch_loop_graph_over_forward_graph"] = r["torch_loop_graph_us"] / r["forward_graph_us"]
         r["torch_loop_eager_over_forward_eager"] = r["torch_loop_eager_us"] / r["forward_eager_call_us"]
+        r.update(train_step_times(cell, inp))
         result[cell] = r
         print(f"{cell}: " + ", ".join(f"{k} {v:.4g}" for k, v in r.items()), flush=True)
     result["sclk_after"] = shader_clock()
