@@ -487,7 +487,8 @@ RK_API int rk_bn_act_backward(const float* dy, int64_t lddy, const float* z, int
                               const float* save_mean, const float* save_invstd, int32_t act, float slope,
                               double dropout_p, uint64_t seed, const int64_t* stream_slot, double* workspace, float* dz, int64_t lddz,
                               float* dgamma, float* dbeta, void* stream) {
-  if (!dy || !z || !dz || batch <= 0 || n <= 0 || (batch_norm && (!save_mean || !save_invstd || !workspace)) ||
+  if (!dy || !z || !dz || batch <= 0 || n <= 0 || lddy < n || ldz < n || lddz < n ||
+      (batch_norm && (!save_mean || !save_invstd || !workspace)) ||
       !(dropout_p >= 0.0 && dropout_p < 1.0) || (dropout_p > 0.0 && !stream_slot))
     return fail(RK_ERR_INVALID, "rk_bn_act_backward: bad arguments");
   hipStream_t st = (hipStream_t)stream;
@@ -555,7 +556,8 @@ RK_API int rk_dice_train_forward(const float* z, int64_t ldz, int64_t batch, int
 RK_API int rk_dice_backward(const float* dy, int64_t lddy, const float* z, int64_t ldz, int64_t batch, int32_t n,
                             const float* bias, const float* alpha, const float* save_mean, const float* save_invstd,
                             double* workspace, float* dz, int64_t lddz, float* dalpha, void* stream) {
-  if (!dy || !z || !dz || !alpha || !save_mean || !save_invstd || !workspace || batch <= 0 || n <= 0)
+  if (!dy || !z || !dz || !alpha || !save_mean || !save_invstd || !workspace || batch <= 0 || n <= 0 || lddy < n ||
+      ldz < n || lddz < n)
     return fail(RK_ERR_INVALID, "rk_dice_backward: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)((n + kBnCols - 1) / kBnCols), (unsigned)((batch + kBnRows - 1) / kBnRows));
