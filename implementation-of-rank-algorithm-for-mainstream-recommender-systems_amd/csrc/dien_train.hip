@@ -12,6 +12,8 @@
 //               d(A q) = sum_t dscore_t h_t;  dq = A^T d(A q)
 //   extractor step t (gates from (x_t, h_{t-1})):  du = dh (h_{t-1} - c);  dc = dh (1-u);  direct = u dh,
 //     then as above with Wg / Wc;  dx_t = Wg[:, :H]^T [dpr|dpu] + Wc[:, :H]^T dpc
+//   rk_dien_interest_backward_aux: dh_t also takes d_hs[b, t] (t < len), the gradient the auxiliary loss
+//     (dien_aux.hip) sends into the extractor states, and dkeys may be added to what that loss wrote
 //
 // Work split as in the forward: one DPP row (16 lanes) per sample, lane p holds unit p % nh.  The
 // gates of step t depend only on saved states, so they are recomputed with the forward's DienCell
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
     const int64_t* __restrict__ seq, int64_t ld_seq, int64_t ld_kb, int T, const int64_t* __restrict__ seq_len,
     int64_t batch, DienWeights w, int cell_type, int sample_stride, const float* __restrict__ hs,
     const float* __restrict__ ss, const float* __restrict__ att_in, int64_t ld_att, const float* d_out,
-    int64_t ld_dout, int64_t ld_dquery, int accumulate, DienGrads gr) {
+    int64_t ld_dout, int64_t ld_dquery, int accumulate, DienGrads gr, const float* __restrict__ d_hs) {
   constexpr int NG = NH / 8;
   constexpr int LO1 = H + 2 * NH, LG = 3 * NH;  // row widths of O1 and of G1 / G2 / O2
   extern __shared__ __attribute__((aligned(16))) float dien_bsm[];
@@ -166,6 +168,8 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
   __syncthreads();
   const float* hsb = hs + (live ? b : 0) * T * NH;
   const float* ssb = ss + (live ? b : 0) * T * NH;
+  // an extra dL/dh_t from outside the recurrence (the auxiliary loss), or null; rows t < len only
+  const float* dxb = d_hs ? d_hs + (live ? b : 0) * T * NH : nullptr;
 
   // ---- pass 1: interest evolution backward, t = len-1 ... 0
   {
@@ -266,10 +270,11 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
     gt.load(w.Wg, w.Wc, p);
     const float wj = wea[j];
     float dhc = 0.f;  // dL/dh_t carried down the chain
-    float r = 0.f, u = 0.f, c = 0.f, hp = 0.f;
+    float r = 0.f, u = 0.f, c = 0.f, hp = 0.f, dx = 0.f;
     const float* x = zero_row;
     if (len > 0) {
       const int t = len - 1;
+      if (dxb) dx = dxb[t * NH + j];
       const long long o = offs[t];
       x = o >= 0 ? key_table + o : zero_row;
       float gi[NG], ci;
@@ -278,9 +283,10 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
       g.gates(gi, ci, hp, half, r, u, c);
     }
     for (int t = len - 1; t >= 0; --t) {
-      float rn = 0.f, un = 0.f, cn = 0.f, hpn = 0.f;
+      float rn = 0.f, un = 0.f, cn = 0.f, hpn = 0.f, dxn = 0.f;
       const float* xn = zero_row;
       if (t > 0) {
+        if (dxb) dxn = dxb[(t - 1) * NH + j];  // loaded a step ahead, like the gates
         const long long o = offs[t - 1];
         xn = o >= 0 ? key_table + o : zero_row;
         float gi[NG], ci;
@@ -288,7 +294,8 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
         hpn = t > 1 ? hsb[(t - 2) * NH + j] : 0.f;
         g.gates(gi, ci, hpn, half, rn, un, cn);
       }
-      const float dht = dhc + fmaf(da[t], wj, dh[t * NH + j]);
+      float dht = dhc + fmaf(da[t], wj, dh[t * NH + j]);
+      if (dxb) dht += dx;  // a branch, not an added zero: without d_hs the arithmetic is unchanged
       const float dc = fmaf(-u, dht, dht);
       const float dpu = dht * (hp - c) * u * (1.0f - u);
       const float dpc = dc * fmaf(-c, c, 1.0f);
@@ -308,7 +315,7 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
         o1[H + NH + j] = r * hp;
       }
       for (int i = p; i < H; i += 16) o1[i] = x[i];
-      r = rn, u = un, c = cn, hp = hpn, x = xn;
+      r = rn, u = un, c = cn, hp = hpn, x = xn, dx = dxn;
     }
   }
 }
@@ -368,18 +375,19 @@ RK_API int64_t rk_dien_interest_backward_workspace_floats(int64_t batch, int32_t
   return dien_bwd_layout(batch, T, H, nh).total;
 }
 
-RK_API int rk_dien_interest_backward(const float* query, int64_t ld_query, const float* keys, int64_t key_rows,
-                                     int64_t ld_key, const int64_t* seq, int64_t ld_seq, int64_t ld_keys_b, int32_t T,
-                                     const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh, int32_t cell_type,
-                                     const float* Wg, const float* bg, const float* Wc, const float* bc,
-                                     const float* A, const float* Vg, const float* vg, const float* Vc,
-                                     const float* vc, const float* hs, const float* ss, const float* att,
-                                     int64_t ld_att, const float* d_out, int64_t ld_dout, float* dquery,
-                                     int64_t ld_dquery, int32_t accumulate_dquery, float* dkeys, float* dWg,
-                                     float* dbg, float* dWc, float* dbc, float* dA, float* dVg, float* dvg,
-                                     float* dVc, float* dvc, int64_t* seq_masked, float* workspace,
-                                     int64_t workspace_floats, void* stream) {
-  const char* who = "rk_dien_interest_backward";
+RK_API int rk_dien_interest_backward_aux(const float* query, int64_t ld_query, const float* keys, int64_t key_rows,
+                                         int64_t ld_key, const int64_t* seq, int64_t ld_seq, int64_t ld_keys_b,
+                                         int32_t T, const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                                         int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                                         const float* bc, const float* A, const float* Vg, const float* vg,
+                                         const float* Vc, const float* vc, const float* hs, const float* ss,
+                                         const float* att, int64_t ld_att, const float* d_out, int64_t ld_dout,
+                                         float* dquery, int64_t ld_dquery, int32_t accumulate_dquery, float* dkeys,
+                                         float* dWg, float* dbg, float* dWc, float* dbc, float* dA, float* dVg,
+                                         float* dvg, float* dVc, float* dvc, int64_t* seq_masked, const float* d_hs,
+                                         int32_t accumulate_dkeys, float* workspace, int64_t workspace_floats,
+                                         void* stream) {
+  const char* who = "rk_dien_interest_backward_aux";
   if (!query || !keys || !seq_len || !Wg || !bg || !Wc || !bc || !A || !Vg || !vg || !Vc || !vc || !hs || !ss ||
       !att || !d_out || !dquery || !dkeys || !dWg || !dbg || !dWc || !dbc || !dA || !dVg || !dvg || !dVc || !dvc)
     return fail(RK_ERR_INVALID, "%s: null pointer", who);
@@ -423,7 +431,7 @@ RK_API int rk_dien_interest_backward(const float* query, int64_t ld_query, const
     if (shm > 64 * 1024) raise_lds_limit((const void*)dien_interest_backward_kernel<HH, NN>, (int)shm);        \
     dien_interest_backward_kernel<HH, NN><<<blocks, 64, shm, st>>>(                                            \
         query, ld_query, keys, key_rows, ld_key, seq, ld_seq, ld_keys_b, T, seq_len, batch, w, cell_type,      \
-        stride, hs, ss, att, ld_att, d_out, ld_dout, ld_dquery, accumulate_dquery, gr);                        \
+        stride, hs, ss, att, ld_att, d_out, ld_dout, ld_dquery, accumulate_dquery, gr, d_hs);                  \
   }
   RK_DIEN_CASE(8, 8)
   RK_DIEN_CASE(16, 8)
@@ -438,8 +446,8 @@ RK_API int rk_dien_interest_backward(const float* query, int64_t ld_query, const
   const int lg = 3 * nh, lo1 = H + 2 * nh;
   float* ws = workspace + l.wgrad;
   const int64_t nws = l.wgrad_floats;
-  // dkeys = G1 . [Wg[:, :H]; Wc[:, :H]] (rows t >= len of G1 are zero, so are those of dkeys)
-  if ((rc = rk_gemm(0, 1, R, H, 2 * nh, g1, lg, nullptr, Wg, ldw, dkeys, H, nullptr, 0, 1, stream)) != RK_OK) return rc;
+  // dkeys (+)= G1 . [Wg[:, :H]; Wc[:, :H]] (rows t >= len of G1 are zero, so are those of the product)
+  if ((rc = rk_gemm(0, 1, R, H, 2 * nh, g1, lg, nullptr, Wg, ldw, dkeys, H, nullptr, accumulate_dkeys ? 1 : 0, 1, stream)) != RK_OK) return rc;
   if ((rc = rk_gemm(0, 1, R, H, nh, g1 + 2 * nh, lg, nullptr, Wc, ldw, dkeys, H, nullptr, 1, 1, stream)) != RK_OK) return rc;
   // One product per cell, P = G^T O [3nh, XW + 2nh] with its row sums (a call costs the same whatever
   // part of its 128 x 128 tile is used), then its blocks go to their places:
@@ -453,4 +461,22 @@ RK_API int rk_dien_interest_backward(const float* query, int64_t ld_query, const
   if ((rc = check_launch(who)) != RK_OK) return rc;
   // dA = d(A q)^T q
   return rk_gemm_wgrad(nh, H, batch, workspace + l.dwea, nh, nullptr, workspace + l.qc, H, dA, H, nullptr, 0, ws, nws, stream);
+}
+
+RK_API int rk_dien_interest_backward(const float* query, int64_t ld_query, const float* keys, int64_t key_rows,
+                                     int64_t ld_key, const int64_t* seq, int64_t ld_seq, int64_t ld_keys_b, int32_t T,
+                                     const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh, int32_t cell_type,
+                                     const float* Wg, const float* bg, const float* Wc, const float* bc,
+                                     const float* A, const float* Vg, const float* vg, const float* Vc,
+                                     const float* vc, const float* hs, const float* ss, const float* att,
+                                     int64_t ld_att, const float* d_out, int64_t ld_dout, float* dquery,
+                                     int64_t ld_dquery, int32_t accumulate_dquery, float* dkeys, float* dWg,
+                                     float* dbg, float* dWc, float* dbc, float* dA, float* dVg, float* dvg,
+                                     float* dVc, float* dvc, int64_t* seq_masked, float* workspace,
+                                     int64_t workspace_floats, void* stream) {
+  return rk_dien_interest_backward_aux(query, ld_query, keys, key_rows, ld_key, seq, ld_seq, ld_keys_b, T, seq_len,
+                                       batch, H, nh, cell_type, Wg, bg, Wc, bc, A, Vg, vg, Vc, vc, hs, ss, att, ld_att,
+                                       d_out, ld_dout, dquery, ld_dquery, accumulate_dquery, dkeys, dWg, dbg, dWc, dbc,
+                                       dA, dVg, dvg, dVc, dvc, seq_masked, nullptr, 0, workspace, workspace_floats,
+                                       stream);
 }

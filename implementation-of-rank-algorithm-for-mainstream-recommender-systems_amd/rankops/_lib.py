@@ -178,6 +178,30 @@ SIGNATURES = {
         + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]
         + [c_void_p] * 9 + [c_void_p, c_void_p, c_int64, c_void_p],
     ),
+    "rk_dien_interest_backward_aux": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+         c_int32, c_int32, c_int32] + [c_void_p] * 9
+        + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]
+        + [c_void_p] * 9 + [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p],
+    ),
+    "rk_dien_aux_loss": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+         c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "rk_dien_aux_loss_dense": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64,
+         c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "rk_dien_aux_loss_backward_workspace_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "rk_dien_aux_loss_backward": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+         c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
     "rk_dice_forward": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
     "rk_bst_attention": (

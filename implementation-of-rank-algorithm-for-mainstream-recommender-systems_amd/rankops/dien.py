@@ -6,8 +6,20 @@ custom_gru_type='AGRU', gru_output_units=8)` takes the reference's flags (dien.p
 `forward(dense, category, sequence, target) -> (probability, logit)` the input dictionaries of
 `rankops.DIN`.  Training is opt-in: `DIEN(..., trainable=True)` in `model.train()` returns outputs
 attached to `rankops.train._DIENTrain` (HIP backward of the recurrence, dien.py:314-334's loop works
-with `rankops.Adam`); a default-constructed model raises in train mode (common.check_eval).  The
-auxiliary loss is left out (the reference says it does not run, dien.py:256-300).
+with `rankops.Adam`); a default-constructed model raises in train mode (common.check_eval).
+
+The auxiliary loss (dien.py:256-300; flags `use_auxiliary_loss=False`, `negative_sample_number=3`,
+keyword-only here) supervises every extractor state h_t with the next behaviour and with sampled
+negatives.  With the flag on, a training forward takes the negatives' ids in
+`sequence['neg_his_read_comment_7d_seq']` [B, (T-1)*negative_sample_number] (entry t*T_neg+n pairs
+with step t; sampling is the caller's) and returns `(probability, logit, aux_loss)`; `loss = bce +
+aux_loss` trains through HIP kernels end to end (rk_dien_aux_loss, rk_dien_aux_loss_backward,
+rk_dien_interest_backward_aux).  The reference's block does not run; two of its defects are
+corrected, not ported: it slices the length tensor where the embedded history is meant
+(dien.py:265), and it adds mean(log sig(pos) + sum log(1 - sig(neg))) to the loss (dien.py:300,317),
+the negative of the paper's L_aux; here the paper's sign is used, and log sig is computed as
+min(x, 0) - log1p(exp(-|x|)).  Eval mode and a flag-off model are unchanged.  As functions:
+`dien_interest(..., return_states=True)` hands out the states, `dien_aux_loss(_gather)` is the loss.
 
 Parameters: `embeddings.*` as in DIN except that target and history share the one `feedid` table
 (shared_embedding_columns, dien.py:126); `gru.gates` / `gru.candidate` (TF GRUCell: Linear(H+nh, 2nh)
@@ -31,6 +43,7 @@ from . import common, ops, train
 from .common import EngineModule, Layer, check_eval, load_vocabulary, run_tail, table_rows
 from .din import FIELDS, SEQ_KEY, Dice
 
+NEG_SEQ_KEY = "neg_" + SEQ_KEY  # neg_his_read_comment_7d_seq: the auxiliary loss's sampled negatives
 ENVELOPE = "H (embedding width) in {8, 16, 32}, nh (gru_output_units) in {8, 16}, 1 <= T <= 256"
 WEIGHT_NAMES = ("Wg", "bg", "Wc", "bc", "A", "Vg", "vg", "Vc", "vc")
 
@@ -75,10 +88,14 @@ class _DIENInterest(torch.autograd.Function):
     """dien_interest / dien_interest_gather under autograd: rk_dien_interest_train(_dense) keeps the
     states, rk_dien_interest_backward gives dquery, dkeys and the nine weight gradients; the gather
     form scatters dkeys into a zeroed dense table gradient (rk_embedding_backward).  `keys` is the
-    history [B,T,H] (seq None) or the table [V,H] with ids seq [B,T]; inputs already validated."""
+    history [B,T,H] (seq None) or the table [V,H] with ids seq [B,T]; inputs already validated.
+    The extractor states hs are a differentiable output: a gradient that reaches them (the
+    auxiliary loss's) enters the extractor's chain through rk_dien_interest_backward_aux; none
+    (hs unused) is a null pointer there, and the call is rk_dien_interest_backward's."""
 
     @staticmethod
     def forward(ctx, query, keys, seq, keys_length, cell, nh, *ws):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
         dense = seq is None
         B, H = query.shape
         T = keys.shape[1] if dense else seq.shape[1]
@@ -99,10 +116,10 @@ class _DIENInterest(torch.autograd.Function):
         ctx.save_for_backward(query, keys, keys_length, att, hs, ss, *ws)
         ctx.seq, ctx.cell, ctx.nh = seq, cell, nh
         ctx.mark_non_differentiable(att)
-        return out, att
+        return out, att, hs
 
     @staticmethod
-    def backward(ctx, d_out, _d_att):
+    def backward(ctx, d_out, _d_att, d_hs):
         query, keys, keys_length, att, hs, ss, *ws = ctx.saved_tensors
         seq, cell, nh = ctx.seq, ctx.cell, ctx.nh
         dense = seq is None
@@ -113,15 +130,19 @@ class _DIENInterest(torch.autograd.Function):
         if B == 0:
             return (torch.zeros_like(query), torch.zeros_like(keys), None, None, None, None,
                     *[torch.zeros_like(w) for w in ws])
+        if d_out is None:  # only the states were used
+            d_out = torch.zeros(B, nh, **f32)
         d_out = d_out.to(torch.float32)
         if d_out.stride(1) != 1 or d_out.stride(0) < nh:
             d_out = d_out.contiguous()
+        if d_hs is not None:
+            d_hs = d_hs.to(torch.float32).contiguous()
         dq = torch.empty(B, H, **f32)
         dkeys = torch.empty(B, T, H, **f32)
         ids = None if dense else torch.empty_like(seq)
         wgrads = ops.dien_interest_backward(query.data_ptr(), query.stride(0), keys, seq, keys.stride(0) if dense else 0,
                                             keys_length, T, H, nh, cell, ws, hs, ss, att, d_out.data_ptr(),
-                                            d_out.stride(0), dq.data_ptr(), H, False, dkeys, B, dev, ids)
+                                            d_out.stride(0), dq.data_ptr(), H, False, dkeys, B, dev, ids, d_hs=d_hs)
         if dense:
             dk = dkeys
         elif ctx.needs_input_grad[1]:
@@ -136,15 +157,23 @@ def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
-def dien_interest(query, keys, keys_length, weights, cell_type="AGRU", return_attention=False):
+def _pack(out, att, hs, return_attention, return_states):
+    if not (return_attention or return_states):
+        return out
+    return (out,) + ((att,) if return_attention else ()) + ((hs,) if return_states else ())
+
+
+def dien_interest(query, keys, keys_length, weights, cell_type="AGRU", return_attention=False, return_states=False):
     """dien_interest(query[B,H], keys[B,T,H], keys_length[B], weights) -> final interest state [B,nh]
     (dien.py:198-229) on rk_dien_interest_dense: TF GRUCell over the keys, attention of the hidden
     states against `A . query` (softmax over all T positions, positions t >= keys_length masked
     with -2^32+1), then the AGRU / AUGRU cell over the hidden states for t < keys_length.
     `weights` = (Wg, bg, Wc, bc, A, Vg, vg, Vc, vc) device tensors (rankops.h);
-    `return_attention` adds the attention weights [B,T].  Differentiable w.r.t. query, keys and the
-    weights (the attention output is not): with grad mode on and any of them requiring grad the
-    call goes through rk_dien_interest_train_dense / rk_dien_interest_backward."""
+    `return_attention` adds the attention weights [B,T], `return_states` (after them) the extractor
+    states hs [B,T,nh] with rows t >= keys_length zero, what dien_aux_loss takes.  Differentiable
+    w.r.t. query, keys and the weights (the attention output is not; hs is): with grad mode on and
+    any of them requiring grad the call goes through rk_dien_interest_train_dense /
+    rk_dien_interest_backward(_aux).  Without grad, return_states runs the train forward kernel."""
     cell = _cell(cell_type)
     query = ops.as_f32(query, "query")
     keys = ops.as_f32(keys, "keys")
@@ -161,19 +190,26 @@ def dien_interest(query, keys, keys_length, weights, cell_type="AGRU", return_at
     if query.stride(1) != 1:
         query = query.contiguous()
     if _wants_grad(query, keys, *weights):
-        out, att = _DIENInterest.apply(query, keys, None, keys_length.contiguous(), cell, nh, *ws)
-        return (out, att) if return_attention else out
-    out = torch.empty(B, nh, device=keys.device, dtype=torch.float32)
-    att = torch.empty(B, T, device=keys.device, dtype=torch.float32) if return_attention else None
+        out, att, hs = _DIENInterest.apply(query, keys, None, keys_length.contiguous(), cell, nh, *ws)
+        return _pack(out, att, hs, return_attention, return_states)
+    f32 = dict(device=keys.device, dtype=torch.float32)
+    out = torch.empty(B, nh, **f32)
+    att = torch.empty(B, T, **f32) if return_attention or return_states else None
+    hs = torch.empty(B, T, nh, **f32) if return_states else None
     if B > 0:
         try:
-            ops.dien_interest_dense(query, keys, keys_length.contiguous(), nh, cell, ws, out, att)
+            if return_states:
+                ops.dien_interest_train_dense(query, keys, keys_length.contiguous(), nh, cell, ws, out, att, hs,
+                                              torch.empty(B, T, nh, **f32))
+            else:
+                ops.dien_interest_dense(query, keys, keys_length.contiguous(), nh, cell, ws, out, att)
         except ops._lib.RankOpsError as e:
             _convert(e, H, nh, T)
-    return (out, att) if return_attention else out
+    return _pack(out, att, hs, return_attention, return_states)
 
 
-def dien_interest_gather(query, table, seq, keys_length, weights, cell_type="AGRU", return_attention=False):
+def dien_interest_gather(query, table, seq, keys_length, weights, cell_type="AGRU", return_attention=False,
+                         return_states=False):
     """dien_interest with the history given as (embedding table [V,H], ids [B,T]): the gather
     happens inside the kernel (rk_dien_interest); ids at t >= keys_length are never read.
     Differentiable like dien_interest; the table's gradient is dense (nn.Embedding's)."""
@@ -197,17 +233,168 @@ def dien_interest_gather(query, table, seq, keys_length, weights, cell_type="AGR
     if query.stride(1) != 1:
         query = query.contiguous()
     if _wants_grad(query, table, *weights):
-        out, att = _DIENInterest.apply(query, table, seq.contiguous(), keys_length.contiguous(), cell, nh, *ws)
-        return (out, att) if return_attention else out
-    out = torch.empty(B, nh, device=query.device, dtype=torch.float32)
-    att = torch.empty(B, T, device=query.device, dtype=torch.float32) if return_attention else None
+        out, att, hs = _DIENInterest.apply(query, table, seq.contiguous(), keys_length.contiguous(), cell, nh, *ws)
+        return _pack(out, att, hs, return_attention, return_states)
+    f32 = dict(device=query.device, dtype=torch.float32)
+    out = torch.empty(B, nh, **f32)
+    att = torch.empty(B, T, **f32) if return_attention or return_states else None
+    hs = torch.empty(B, T, nh, **f32) if return_states else None
     if B > 0:
+        args = (query.data_ptr(), query.stride(0), table, seq.contiguous(), keys_length.contiguous(), T, H, nh, cell, ws,
+                out.data_ptr(), out.stride(0), att)
         try:
-            ops.dien_interest(query.data_ptr(), query.stride(0), table, seq.contiguous(), keys_length.contiguous(), T,
-                              H, nh, cell, ws, out.data_ptr(), out.stride(0), att, B, query.device)
+            if return_states:
+                ops.dien_interest_train(*args, hs, torch.empty(B, T, nh, **f32), B, query.device)
+            else:
+                ops.dien_interest(*args, B, query.device)
         except ops._lib.RankOpsError as e:
             _convert(e, H, nh, T)
-    return (out, att) if return_attention else out
+    return _pack(out, att, hs, return_attention, return_states)
+
+
+AUX_ENVELOPE = ENVELOPE + f", 1 <= T_neg (negatives per step) <= {ops.DIEN_AUX_MAX_NEG}"
+
+
+def _convert_aux(rc_error, H, nh, T, T_neg):
+    if getattr(rc_error, "code", None) == ops._lib.RK_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"rankops dien_aux_loss: H={H}, nh={nh}, T={T}, T_neg={T_neg}: {rc_error}; "
+                                  f"envelope: {AUX_ENVELOPE}") from rc_error
+    raise rc_error
+
+
+def _negatives_per_step(count: int, T: int, what: str) -> int:
+    """T_neg from the negatives' second dimension, (T-1) * T_neg entries (entry t * T_neg + n pairs with h_t)."""
+    if T == 1:
+        if count != 0:
+            raise ValueError(f"{what}: T = 1 leaves no step to supervise, the negatives must be empty, got {count}")
+        return 1
+    if count == 0 or count % (T - 1) != 0:
+        raise ValueError(f"{what}: the negatives' second dimension must be a positive multiple of T-1 = {T - 1} "
+                         f"(T_neg per step), got {count}")
+    return count // (T - 1)
+
+
+def _check_aux_envelope(H: int, nh: int, T: int, T_neg: int):
+    if H not in (8, 16, 32) or nh not in (8, 16) or not 1 <= T <= 256 or not 1 <= T_neg <= ops.DIEN_AUX_MAX_NEG:
+        raise NotImplementedError(f"rankops dien_aux_loss: H={H}, nh={nh}, T={T}, T_neg={T_neg} is outside the "
+                                  f"kernel's envelope: {AUX_ENVELOPE}")
+
+
+class _DIENAuxLoss(torch.autograd.Function):
+    """dien_aux_loss / dien_aux_loss_gather under autograd: rk_dien_aux_loss(_dense) forward,
+    rk_dien_aux_loss_backward (which recomputes the dots and reads the upstream scalar from device
+    memory).  `keys` is the history [B,T,H] with `neg` [B,(T-1)T_neg,H] (seq None), or the table
+    [V,H] with ids seq [B,T] and neg_seq [B,(T-1)T_neg] (neg None); inputs already validated.
+    Returns (mean loss, per-sample loss); only the mean is differentiable."""
+
+    @staticmethod
+    def forward(ctx, hs, keys, neg, w_aux, seq, neg_seq, keys_length, T_neg):
+        dense = seq is None
+        B, T, nh = hs.shape
+        H = w_aux.shape[0]
+        dev = hs.device
+        per_sample = torch.empty(B, device=dev, dtype=torch.float32)
+        mean = torch.empty(1, device=dev, dtype=torch.float32)
+        try:
+            ops.dien_aux_loss(hs, keys, seq, neg, neg_seq, keys_length, T, T_neg, H, nh, w_aux, per_sample, mean, B,
+                              dev)
+        except ops._lib.RankOpsError as e:
+            _convert_aux(e, H, nh, T, T_neg)
+        ctx.save_for_backward(hs, keys, w_aux, keys_length, *([neg] if dense else []))
+        ctx.seq, ctx.neg_seq, ctx.T_neg = seq, neg_seq, T_neg
+        ctx.mark_non_differentiable(per_sample)
+        return mean.reshape(()), per_sample
+
+    @staticmethod
+    def backward(ctx, d_mean, _d_per_sample):
+        hs, keys, w_aux, keys_length, *rest = ctx.saved_tensors
+        seq, neg_seq, T_neg = ctx.seq, ctx.neg_seq, ctx.T_neg
+        dense = seq is None
+        neg = rest[0] if dense else None
+        B, T, nh = hs.shape
+        H = w_aux.shape[0]
+        dev = hs.device
+        if B == 0:
+            return (torch.zeros_like(hs), torch.zeros_like(keys), None if neg is None else torch.zeros_like(neg),
+                    torch.zeros_like(w_aux), None, None, None, None)
+        d_loss = d_mean.to(torch.float32).reshape(1).contiguous()
+        ids = None if dense else torch.empty_like(seq)
+        neg_ids = None if dense else torch.empty_like(neg_seq)
+        d_hs, dkeys, dneg, dw = ops.dien_aux_loss_backward(hs, keys, seq, neg, neg_seq, keys_length, T, T_neg, H, nh,
+                                                           w_aux, d_loss, B, dev, ids, neg_ids)
+        if dense:
+            return d_hs, dkeys, dneg, dw, None, None, None, None
+        dk = None
+        if ctx.needs_input_grad[1]:  # the dense table gradient: positives and negatives into one buffer
+            dk = train.zero_grads([keys], dev)[0]
+            ops.embedding_backward([ops.table_segment(dk, ids.reshape(-1), 0)], B * T, dkeys.view(B * T, H))
+            if T > 1:
+                n = neg_ids.numel()
+                ops.embedding_backward([ops.table_segment(dk, neg_ids.reshape(-1), 0)], n, dneg.view(n, H))
+        return d_hs, dk, None, dw, None, None, None, None
+
+
+def _aux_common(hs, keys_length, w_aux, B, T, H, what):
+    hs = ops.as_f32(hs, "hs")
+    w_aux = ops.as_f32(w_aux, "w_aux")
+    keys_length = ops.as_index(keys_length, "keys_length")
+    if w_aux.dim() != 2 or w_aux.shape[0] != H:
+        raise ValueError(f"{what}: w_aux must be [{H}, nh], got {tuple(w_aux.shape)}")
+    nh = w_aux.shape[1]
+    if tuple(hs.shape) != (B, T, nh):
+        raise ValueError(f"{what}: hs must be [{B}, {T}, {nh}], got {tuple(hs.shape)}")
+    if keys_length.dim() != 1 or keys_length.shape[0] != B:
+        raise ValueError(f"{what}: keys_length must be [{B}], got {tuple(keys_length.shape)}")
+    return hs.contiguous(), keys_length.contiguous(), w_aux.contiguous(), nh
+
+
+def dien_aux_loss(hs, keys, neg_keys, keys_length, w_aux, return_per_sample=False):
+    """DIEN's auxiliary loss (dien.py:256-300 with the paper's sign) on rk_dien_aux_loss_dense:
+    hs [B,T,nh] the extractor states (dien_interest(..., return_states=True)), keys [B,T,H] the
+    history, neg_keys [B,(T-1)*T_neg,H] the sampled negatives (entry t*T_neg+n pairs with h_t; T_neg
+    is inferred), w_aux [H,nh].  With g_t = w_aux h_t, per sample
+    -sum_{t < len-1} [logsig(g_t . keys[t+1]) + sum_n logsig(-(g_t . neg[t,n]))]; returns the batch mean
+    (a 0-dim tensor), with `return_per_sample` also the [B] per-sample values (not differentiable).
+    Differentiable w.r.t. hs, keys, neg_keys and w_aux."""
+    what = "dien_aux_loss"
+    keys = ops.as_f32(keys, "keys")
+    neg_keys = ops.as_f32(neg_keys, "neg_keys")
+    if keys.dim() != 3 or neg_keys.dim() != 3 or neg_keys.shape[0] != keys.shape[0] or neg_keys.shape[2] != keys.shape[2]:
+        raise ValueError(f"{what}: keys {tuple(keys.shape)} and neg_keys {tuple(neg_keys.shape)} do not match")
+    B, T, H = keys.shape
+    hs, keys_length, w_aux, nh = _aux_common(hs, keys_length, w_aux, B, T, H, what)
+    T_neg = _negatives_per_step(neg_keys.shape[1], T, what)
+    _check_aux_envelope(H, nh, T, T_neg)
+    if keys.stride(2) != 1 or keys.stride(1) % 4 or keys.stride(0) % 4 or keys.data_ptr() % 16:
+        keys = keys.contiguous()
+    if neg_keys.stride(2) != 1 or neg_keys.stride(1) % 4 or neg_keys.stride(0) % 4 or neg_keys.data_ptr() % 16:
+        neg_keys = neg_keys.contiguous()
+    mean, per_sample = _DIENAuxLoss.apply(hs, keys, neg_keys, w_aux, None, None, keys_length, T_neg)
+    return (mean, per_sample) if return_per_sample else mean
+
+
+def dien_aux_loss_gather(hs, table, seq, neg_seq, keys_length, w_aux, return_per_sample=False):
+    """dien_aux_loss with the history and the negatives given as ids into one embedding table [V,H]:
+    seq [B,T], neg_seq [B,(T-1)*T_neg]; the gathers happen inside the kernel (rk_dien_aux_loss), ids
+    of masked steps are never read.  The table's gradient is dense (nn.Embedding's) and takes the
+    positives' and the negatives' rows."""
+    what = "dien_aux_loss_gather"
+    table = ops.as_f32(table, "table")
+    seq = ops.as_index(seq, "keys index")
+    neg_seq = ops.as_index(neg_seq, "negatives index")
+    if table.dim() != 2 or seq.dim() != 2 or neg_seq.dim() != 2 or neg_seq.shape[0] != seq.shape[0]:
+        raise ValueError(f"{what}: table {tuple(table.shape)}, ids {tuple(seq.shape)} and negative ids "
+                         f"{tuple(neg_seq.shape)} do not match")
+    B, T = seq.shape
+    H = table.shape[1]
+    hs, keys_length, w_aux, nh = _aux_common(hs, keys_length, w_aux, B, T, H, what)
+    T_neg = _negatives_per_step(neg_seq.shape[1], T, what)
+    _check_aux_envelope(H, nh, T, T_neg)
+    if table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
+        table = table.contiguous()
+    mean, per_sample = _DIENAuxLoss.apply(hs, table, None, w_aux, seq.contiguous(), neg_seq.contiguous(), keys_length,
+                                          T_neg)
+    return (mean, per_sample) if return_per_sample else mean
 
 
 def _tf_linear(in_features: int, out_features: int, bias_value: float = 0.0) -> nn.Linear:
@@ -221,8 +408,12 @@ def _tf_linear(in_features: int, out_features: int, bias_value: float = 0.0) -> 
 class DIEN(EngineModule):
     def __init__(self, vocab_dir, hidden_units=None, activation='dice', dropout_rate=0.1, batch_norm=True,
                  custom_gru_type='AGRU', gru_output_units=8, *, vocab_sizes=None, embedding_dim=16,
-                 trainable=False):
+                 trainable=False, use_auxiliary_loss=False, negative_sample_number=3):
         super().__init__()
+        self.use_auxiliary_loss = bool(use_auxiliary_loss)
+        self.negative_sample_number = int(negative_sample_number)
+        if self.use_auxiliary_loss and self.negative_sample_number < 1:
+            raise ValueError(f"rankops DIEN: negative_sample_number must be >= 1, got {negative_sample_number}")
         self.trainable = bool(trainable)  # train mode is opt-in; parameters and initialisation are the same
         self._dropout = train.DropoutStreams()
         if hidden_units is None:
@@ -272,6 +463,13 @@ class DIEN(EngineModule):
             self._tail.append(Layer(lin, act=kind, act_module=act, post_bn=bn))
             width = unit
         self.output_layer = _tf_linear(width, 1)
+        # last, and only with the flag: a default model's parameters, their order and the random
+        # numbers their initialisation draws are untouched (aux_project_matrix, dien.py:268)
+        if self.use_auxiliary_loss:
+            self.aux_project_matrix = nn.Parameter(nn.init.xavier_uniform_(torch.empty(H, nh)))
+
+    def _aux_active(self) -> bool:
+        return self.use_auxiliary_loss and self.training
 
     def _load_vocabulary(self, vocab_dir, filename):
         return load_vocabulary(vocab_dir, filename)
@@ -314,7 +512,8 @@ class DIEN(EngineModule):
         tgt = target.get("feedid", None) if isinstance(target, dict) else None
         if isinstance(tgt, torch.Tensor) and tgt.shape[0] == 0:  # an empty batch: nothing to launch
             dev = ops.require_gpu(tgt, "target['feedid']").device
-            return common.empty_rows(dev, 2)
+            out = common.empty_rows(dev, 2)
+            return out + (torch.zeros((), device=dev),) if self._aux_active() else out
         pl = self._plan(dense, category, sequence, target)
         B, dev, H, nh, width = pl["B"], pl["dev"], pl["H"], self.gru_output_units, pl["width"]
         if width != self._tail[0].linear.in_features:
@@ -322,13 +521,24 @@ class DIEN(EngineModule):
                              f"{self._tail[0].linear.in_features}")
         T = pl["seq"].shape[1]
         _check_envelope(H, nh, T)
+        if self._aux_active():  # the negatives of the auxiliary loss: ids into the feedid table
+            T_neg = self.negative_sample_number
+            if NEG_SEQ_KEY not in sequence:
+                raise ValueError(f"rankops DIEN: use_auxiliary_loss=True needs sequence[{NEG_SEQ_KEY!r}], the sampled "
+                                 f"negatives [B, (T-1)*negative_sample_number] (entry t*T_neg+n pairs with step t)")
+            neg = ops.as_index(sequence[NEG_SEQ_KEY], f"sequence[{NEG_SEQ_KEY!r}]")
+            if tuple(neg.shape) != (B, (T - 1) * T_neg):
+                raise ValueError(f"rankops DIEN: sequence[{NEG_SEQ_KEY!r}] must be [B, (T-1)*negative_sample_number] = "
+                                 f"[{B}, {(T - 1) * T_neg}], got {tuple(neg.shape)}")
+            _check_aux_envelope(H, nh, T, T_neg)
+            pl["neg_seq"] = neg.contiguous()
         if self.training:  # Dice / BatchNorm batch statistics, Dropout, HIP backward (rankops.train)
             grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             try:
-                prob, logit, att = train.dien_train_forward(self, pl, grad)
+                prob, logit, att, *aux = train.dien_train_forward(self, pl, grad)
             except ops._lib.RankOpsError as e:
                 _convert(e, H, nh, T)
-            return (prob, logit, att) if return_attention else (prob, logit)
+            return (prob, logit, att, *aux) if return_attention else (prob, logit, *aux)
         logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
         prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
         row = torch.empty(B, width, device=dev, dtype=torch.float32)

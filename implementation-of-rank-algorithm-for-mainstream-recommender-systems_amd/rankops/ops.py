@@ -324,28 +324,86 @@ def dien_interest_train_dense(query, keys, keys_length, nh, cell_type, weights, 
 
 def dien_interest_backward(query_ptr, ld_query, keys, seq, ld_keys_b, seq_len, T, H, nh, cell_type, weights, hs, ss,
                            att, d_out_ptr, ld_dout, dquery_ptr, ld_dquery, accumulate_dquery, dkeys, batch, device,
-                           seq_masked=None):
+                           seq_masked=None, d_hs=None, accumulate_dkeys=False):
     """rk_dien_interest_backward: backprop through time of the interest recurrence.  `keys` is the
     table [V, H] with ids `seq` [batch, T], or the dense history [batch, T, H] with seq None and
     ld_keys_b its batch stride; d_out / dquery are strided pointers (they may lie in one row-gradient
     buffer), dquery is added to when accumulate_dquery; dkeys [batch, T, H] is written (rows past the
     length zero); seq_masked [batch, T] int64, when given, receives the ids with 0 past the length
-    (what the embedding scatter of dkeys takes).  Returns the nine weight gradients (Wg, bg, Wc, bc, A, Vg, vg, Vc, vc)."""
+    (what the embedding scatter of dkeys takes).  d_hs [batch, T, nh] (contiguous) or accumulate_dkeys
+    send the call to rk_dien_interest_backward_aux: d_hs is an extra dL/dh_t (the auxiliary loss's),
+    accumulate_dkeys adds to a dkeys the caller has already written in full.
+    Returns the nine weight gradients (Wg, bg, Wc, bc, A, Vg, vg, Vc, vc)."""
     lib = _lib.load()
     _lib.ensure_device(device)
     grads = [torch.empty_like(w) for w in weights]
     nws = lib.rk_dien_interest_backward_workspace_floats(batch, T, H, nh)
     ws = torch.empty(max(nws, 1), device=device, dtype=torch.float32)
     dense = seq is None
-    check(lib.rk_dien_interest_backward(query_ptr, ld_query, ptr(keys), 0 if dense else keys.shape[0],
-                                        keys.stride(1) if dense else keys.stride(0), ptr(seq),
-                                        0 if dense else seq.stride(0), ld_keys_b, T, ptr(seq_len), batch, H, nh,
-                                        cell_type, *[ptr(w) for w in weights], ptr(hs), ptr(ss), ptr(att),
-                                        att.stride(0), d_out_ptr, ld_dout, dquery_ptr, ld_dquery,
-                                        int(accumulate_dquery), ptr(dkeys), *[ptr(g) for g in grads], ptr(seq_masked),
-                                        ptr(ws), nws,
-                                        _lib.raw_stream(device)), "rk_dien_interest_backward")
+    head = (query_ptr, ld_query, ptr(keys), 0 if dense else keys.shape[0], keys.stride(1) if dense else keys.stride(0),
+            ptr(seq), 0 if dense else seq.stride(0), ld_keys_b, T, ptr(seq_len), batch, H, nh, cell_type,
+            *[ptr(w) for w in weights], ptr(hs), ptr(ss), ptr(att), att.stride(0), d_out_ptr, ld_dout, dquery_ptr,
+            ld_dquery, int(accumulate_dquery), ptr(dkeys), *[ptr(g) for g in grads], ptr(seq_masked))
+    if d_hs is None and not accumulate_dkeys:
+        check(lib.rk_dien_interest_backward(*head, ptr(ws), nws, _lib.raw_stream(device)),
+              "rk_dien_interest_backward")
+    else:
+        if d_hs is not None and (not d_hs.is_contiguous() or tuple(d_hs.shape) != (batch, T, nh)):
+            raise ValueError(f"rankops: d_hs must be a contiguous [{batch}, {T}, {nh}] tensor")
+        check(lib.rk_dien_interest_backward_aux(*head, ptr(d_hs), int(bool(accumulate_dkeys)), ptr(ws), nws,
+                                                _lib.raw_stream(device)), "rk_dien_interest_backward_aux")
     return grads
+
+
+DIEN_AUX_MAX_NEG = 8
+
+
+def dien_aux_loss(hs, keys, seq, neg, neg_seq, seq_len, T, T_neg, H, nh, w_aux, per_sample, mean, batch, device):
+    """rk_dien_aux_loss / rk_dien_aux_loss_dense: the auxiliary loss of the extractor states hs
+    [batch, T, nh] against the next behaviour and T_neg negatives per step.  Gather form: keys = the
+    table [V, H], seq [batch, T], neg_seq [batch, (T-1) T_neg], neg None; dense form: keys [batch, T, H],
+    neg [batch, (T-1) T_neg, H], seq / neg_seq None.  Writes per_sample [batch] and mean [1]."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    st = _lib.raw_stream(device)
+    if seq is not None:
+        check(lib.rk_dien_aux_loss(ptr(hs), ptr(keys), keys.shape[0], keys.stride(0), ptr(seq), seq.stride(0),
+                                   ptr(neg_seq) if T > 1 else None, neg_seq.stride(0), T, T_neg, ptr(seq_len), batch,
+                                   H, nh, ptr(w_aux), ptr(per_sample), ptr(mean), st), "rk_dien_aux_loss")
+    else:
+        check(lib.rk_dien_aux_loss_dense(ptr(hs), ptr(keys), keys.stride(0), keys.stride(1),
+                                         ptr(neg) if T > 1 else None, neg.stride(0), neg.stride(1), T, T_neg,
+                                         ptr(seq_len), batch, H, nh, ptr(w_aux), ptr(per_sample), ptr(mean), st),
+              "rk_dien_aux_loss_dense")
+
+
+def dien_aux_loss_backward(hs, keys, seq, neg, neg_seq, seq_len, T, T_neg, H, nh, w_aux, d_loss, batch, device,
+                           seq_masked=None, neg_masked=None):
+    """rk_dien_aux_loss_backward: sources as dien_aux_loss; d_loss is a one-element device tensor
+    (dL/d(mean), read by the kernel).  Returns (d_hs [batch, T, nh], dkeys [batch, T, H], dneg
+    [batch, (T-1) T_neg, H], dW_aux [H, nh]), every element written; in the gather form seq_masked
+    [batch, T] / neg_masked [batch, (T-1) T_neg] int64, when given, receive the ids with 0 wherever
+    dkeys / dneg is zero by masking (the index lists of their embedding scatters)."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    f32 = dict(device=device, dtype=torch.float32)
+    nneg = (T - 1) * T_neg
+    d_hs, dkeys = torch.empty(batch, T, nh, **f32), torch.empty(batch, T, H, **f32)
+    dneg, dw = torch.empty(batch, nneg, H, **f32), torch.empty(H, nh, **f32)
+    nws = lib.rk_dien_aux_loss_backward_workspace_floats(batch, T, H, nh)
+    ws = torch.empty(max(nws, 1), **f32)
+    dense = seq is None
+    live = T > 1
+    check(lib.rk_dien_aux_loss_backward(ptr(hs), ptr(keys), 0 if dense else keys.shape[0],
+                                        keys.stride(1) if dense else keys.stride(0), ptr(seq),
+                                        0 if dense else seq.stride(0), keys.stride(0) if dense else 0,
+                                        ptr(neg) if dense and live else None, neg.stride(0) if dense else 0,
+                                        neg.stride(1) if dense else 0, None if dense or not live else ptr(neg_seq),
+                                        0 if dense else neg_seq.stride(0), T, T_neg, ptr(seq_len), batch, H, nh,
+                                        ptr(w_aux), ptr(d_loss), ptr(d_hs), ptr(dkeys), ptr(dneg) if live else None,
+                                        ptr(seq_masked), ptr(neg_masked) if live else None, ptr(dw), ptr(ws), nws,
+                                        _lib.raw_stream(device)), "rk_dien_aux_loss_backward")
+    return d_hs, dkeys, dneg, dw
 
 
 def dice_forward(x, scale, shift, alpha, y):

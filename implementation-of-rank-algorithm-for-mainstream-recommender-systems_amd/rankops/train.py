@@ -669,12 +669,29 @@ def dien_tail_forward(model, pl, x, att, hs=None, ss=None):
     return units, seed, slot, saved, prob, logit
 
 
+def dien_aux_forward(model, pl, hs):
+    """The auxiliary loss of the kept extractor states (rk_dien_aux_loss over the feedid table, the
+    history ids and pl["neg_seq"]): a 0-dim tensor."""
+    B, dev, H, nh = pl["B"], pl["dev"], pl["H"], model.gru_output_units
+    T = pl["seq"].shape[1]
+    per_sample = torch.empty(B, device=dev, dtype=torch.float32)
+    mean = torch.empty(1, device=dev, dtype=torch.float32)
+    ops.dien_aux_loss(hs, model.embeddings["feedid"].weight, pl["seq"], None, pl["neg_seq"], pl["seq_len"], T,
+                      model.negative_sample_number, H, nh, model.aux_project_matrix, per_sample, mean, B, dev)
+    return mean.reshape(())
+
+
 class _DIENTrain(torch.autograd.Function):
     """DIEN forward + backward in train mode (dien.py:166-254,314-334): rk_concat_gather, the train
     interest forward (GRU, attention, AGRU / AUGRU, states kept), DIN's tail with batch statistics
     and Dropout; backward: head, units, rk_dien_interest_backward reading d(state) from the row
     gradient's state columns and adding dquery into its target columns, then the embedding scatters.
-    Inputs after the fixed arguments: the distinct tables, the nine interest weights, `_din_params`."""
+    Inputs after the fixed arguments: the distinct tables, the nine interest weights, `_din_params`,
+    and with the auxiliary loss (pl["neg_seq"] set) aux_project_matrix last.  Then the forward also
+    returns the auxiliary loss of the kept states (dien.py:256-300), and the backward, if that loss
+    received a gradient, runs rk_dien_aux_loss_backward first: its d_hs enters the extractor's chain
+    and its dkeys is added to (rk_dien_interest_backward_aux), and its dneg is one more scatter
+    into the feedid table's gradient."""
 
     @staticmethod
     def forward(ctx, model, pl, emb_plan, *params):
@@ -689,10 +706,13 @@ class _DIENTrain(torch.autograd.Function):
         ctx.model, ctx.pl, ctx.units, ctx.seed, ctx.emb_plan = model, pl, units, seed, emb_plan
         ctx.save_for_backward(x, att, hs, ss, prob, slot, *[t for s in saved for t in s])
         ctx.mark_non_differentiable(att)
-        return prob, logit, att
+        if "neg_seq" not in pl:
+            return prob, logit, att
+        ctx.set_materialize_grads(False)  # an unused aux loss arrives as None and costs nothing
+        return prob, logit, att, dien_aux_forward(model, pl, hs)
 
     @staticmethod
-    def backward(ctx, dprob, dlogit, _datt):
+    def backward(ctx, dprob, dlogit, _datt, daux=None):
         from .dien import _cell
         model, pl, units = ctx.model, ctx.pl, ctx.units
         x, att, hs, ss, prob, slot, *flat = ctx.saved_tensors
@@ -700,35 +720,61 @@ class _DIENTrain(torch.autograd.Function):
         B, dev, H, nh, width = pl["B"], pl["dev"], pl["H"], model.gru_output_units, pl["width"]
         seq = pl["seq"]
         T = seq.shape[1]
+        if dprob is None:  # only the auxiliary loss's gradients are left unmaterialised
+            dprob = torch.zeros_like(prob)
+        if dlogit is None:
+            dlogit = torch.zeros_like(prob)
         dxr, unit_grads, dw_out, db_out = din_tail_backward(model, dprob, dlogit, prob, x, units, saved, ctx.seed, slot)
         # dxr = dL/d[dense | category | target | state]: d(state) is read in place, dquery added in place
         weights, looks = ctx.emb_plan
         table = model.embeddings["feedid"].weight
-        dkeys = torch.empty(B, T, H, device=dev, dtype=torch.float32)
+        aux = "neg_seq" in pl
+        d_hs = dneg = neg_ids = daux_w = None
+        if aux and daux is not None:  # the auxiliary loss first: it writes dkeys in full, the recurrence adds
+            neg_ids = torch.empty_like(pl["neg_seq"])
+            d_hs, dkeys, dneg, daux_w = ops.dien_aux_loss_backward(
+                hs, table, seq, None, pl["neg_seq"], pl["seq_len"], T, model.negative_sample_number, H, nh,
+                model.aux_project_matrix, daux.to(torch.float32).reshape(1).contiguous(), B, dev, None, neg_ids)
+        else:
+            dkeys = torch.empty(B, T, H, device=dev, dtype=torch.float32)
         ids = torch.empty_like(seq)  # the history ids with 0 past the length (poisoned tails never scatter)
         wgrads = ops.dien_interest_backward(ops._lib.fptr(x, pl["q_col"]), width, table, seq, 0, pl["seq_len"], T, H,
                                             nh, _cell(model.custom_gru_type), model.interest_weights(), hs, ss, att,
                                             ops._lib.fptr(dxr, pl["state_col"]), width,
-                                            ops._lib.fptr(dxr, pl["q_col"]), width, True, dkeys, B, dev, ids)
+                                            ops._lib.fptr(dxr, pl["q_col"]), width, True, dkeys, B, dev, ids,
+                                            d_hs=d_hs, accumulate_dkeys=d_hs is not None)
         # one zeroed buffer per distinct table; feedid takes the target lookup and the history scatter
         # (key rows past the length are exact zeros: the zero-skipping scatter stays contention-free)
         grads = zero_grads(weights, dev)
         ops.embedding_backward([ops.table_segment(grads[k], i, col) for k, i, col in looks], B, dxr)
         ops.embedding_backward([ops.table_segment(grads[pl["seq_slot"]], ids.reshape(-1), 0)], B * T,
                                dkeys.view(B * T, H))
-        return (None, None, None, *grads, *wgrads, *[t for g in unit_grads for t in g], dw_out, db_out)
+        if dneg is not None and dneg.numel():
+            n = neg_ids.numel()
+            ops.embedding_backward([ops.table_segment(grads[pl["seq_slot"]], neg_ids.reshape(-1), 0)], n,
+                                   dneg.view(n, H))
+        return (None, None, None, *grads, *wgrads, *[t for g in unit_grads for t in g], dw_out, db_out,
+                *([daux_w] if aux else []))
 
 
 def dien_train_forward(model, pl, grad: bool):
     """DIEN train-mode forward (rankops.DIEN.forward in model.train()): (prob, logit, attention),
-    attached to _DIENTrain when `grad`; otherwise the same launches with nothing kept."""
+    and the auxiliary loss when pl carries the negatives, attached to _DIENTrain when `grad`;
+    otherwise the same launches with nothing kept."""
+    aux = "neg_seq" in pl
     if not grad:
         B, dev = pl["B"], pl["dev"]
-        x = torch.empty(B, pl["width"], device=dev, dtype=torch.float32)
+        T, nh = pl["seq"].shape[1], model.gru_output_units
+        f32 = dict(device=dev, dtype=torch.float32)
+        x = torch.empty(B, pl["width"], **f32)
         ops.concat_gather(pl["segs"], B, x)
-        att = torch.empty(B, pl["seq"].shape[1], device=dev, dtype=torch.float32)
-        _, _, _, _, prob, logit = dien_tail_forward(model, pl, x, att)
-        return prob, logit, att
+        att = torch.empty(B, T, **f32)
+        if not aux:
+            _, _, _, _, prob, logit = dien_tail_forward(model, pl, x, att)
+            return prob, logit, att
+        hs = torch.empty(B, T, nh, **f32)  # the train forward kernel, for the states the loss reads
+        _, _, _, _, prob, logit = dien_tail_forward(model, pl, x, att, hs, torch.empty(B, T, nh, **f32))
+        return prob, logit, att, dien_aux_forward(model, pl, hs)
     units = din_units(model)
     weights, looks = [], []
 
@@ -743,7 +789,7 @@ def dien_train_forward(model, pl, grad: bool):
         looks.append((slot_of(w), idx, col))
     pl = dict(pl, seq_slot=slot_of(model.embeddings["feedid"].weight))
     return _DIENTrain.apply(model, pl, (weights, looks), *weights, *model.interest_weights(),
-                            *_din_params(model, units))
+                            *_din_params(model, units), *([model.aux_project_matrix] if aux else []))
 
 
 # ---------------------------------------------------------------- AFM

@@ -30,6 +30,8 @@
  *   rk_dien_interest_dense  the same over a dense history tensor keys[B,T,H]
  *   rk_dien_interest_train(_dense), rk_dien_interest_backward  the train forward that keeps the
  *                      states, and backprop through time of the recurrence   DIEN/dien.py:314-334
+ *   rk_dien_aux_loss(_dense), rk_dien_aux_loss_backward, rk_dien_interest_backward_aux  the auxiliary
+ *                      loss over the extractor states and its gradients      DIEN/dien.py:256-300
  *   rk_dice_forward    Dice.forward() in eval (BatchNorm running statistics)           din.py:26-36
  *   rk_row_l2norm_mean DIN mini-batch-aware l2 term          din.py:318-322
  *   rk_afm_forward     AFM.forward()                         afm.py:92-119
@@ -326,6 +328,79 @@ int rk_dien_interest_backward(const float* query, int64_t ld_query, const float*
                               float* dWg, float* dbg, float* dWc, float* dbc, float* dA, float* dVg,
                               float* dvg, float* dVc, float* dvc, int64_t* seq_masked, float* workspace,
                               int64_t workspace_floats, void* stream);
+
+/* rk_dien_interest_backward with a second source of dL/dh_t and an accumulating dkeys, for a loss
+ * that reads the extractor states themselves (rk_dien_aux_loss):
+ *   d_hs (NULL, or [batch, T, nh] contiguous): added to dL/dh_t inside the extractor's backward
+ *   chain for t < seq_len[b]; rows t >= seq_len[b] are never read.
+ *   accumulate_dkeys: the history-row gradients are added to dkeys (every row of which the caller
+ *   has written, e.g. rk_dien_aux_loss_backward) instead of overwriting it.
+ * With d_hs == NULL and accumulate_dkeys == 0 this is rk_dien_interest_backward, bit for bit (that
+ * entry point forwards here).  Same workspace query.                                            */
+int rk_dien_interest_backward_aux(const float* query, int64_t ld_query, const float* keys, int64_t key_rows,
+                                  int64_t ld_key, const int64_t* seq, int64_t ld_seq, int64_t ld_keys_b,
+                                  int32_t T, const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                                  int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                                  const float* bc, const float* A, const float* Vg, const float* vg,
+                                  const float* Vc, const float* vc, const float* hs, const float* ss,
+                                  const float* att, int64_t ld_att, const float* d_out, int64_t ld_dout,
+                                  float* dquery, int64_t ld_dquery, int32_t accumulate_dquery, float* dkeys,
+                                  float* dWg, float* dbg, float* dWc, float* dbc, float* dA, float* dVg,
+                                  float* dvg, float* dVc, float* dvc, int64_t* seq_masked, const float* d_hs,
+                                  int32_t accumulate_dkeys, float* workspace, int64_t workspace_floats,
+                                  void* stream);
+
+/* DIEN auxiliary loss (DIEN/dien.py:256-300, with the paper's sign): every extractor state h_t is
+ * scored against the next behaviour e_{t+1} and against T_neg sampled negatives n_{t,k}:
+ *   g_t = W_aux h_t (W_aux [H, nh] row-major);  pos_t = g_t . e_{t+1};  neg_{t,k} = g_t . n_{t,k}
+ *   per_sample[b] = - sum_{t < seq_len[b]-1} [ logsig(pos_t) + sum_k logsig(-neg_{t,k}) ]
+ *   mean[0]       = (1 / batch) sum_b per_sample[b]
+ * with logsig(x) = min(x, 0) - log1p(exp(-|x|)).  A sample with seq_len <= 1 (or T == 1) gives 0.
+ * hs [batch, T, nh] contiguous: the states rk_dien_interest_train keeps.  History rows as
+ * rk_dien_interest takes them (key_table, seq [batch, ld_seq]); the negatives are rows of the same
+ * table, ids neg_seq [batch, ld_neg_seq], entry t * T_neg + k pairs with h_t (ld_neg_seq >=
+ * (T-1) T_neg; neg_seq may be NULL when T == 1).  seq_len is clamped to [0, T]; ids of masked
+ * steps (history t+1 >= seq_len, negatives of t >= seq_len-1) are never read; an out-of-range id at
+ * a live step reads a zero row and raises RK_FLAG_INDEX_OOB.  hs and table rows 16-B aligned.
+ * Envelope: H in {8,16,32}, nh in {8,16}, 1 <= T <= 256, 1 <= T_neg <= 8 (else RK_ERR_UNSUPPORTED,
+ * before any launch).  One wave per sample, H/4 lanes per (b, t) item; fixed-order sums, no atomics:
+ * two launches on the same inputs are bit-equal.                                                 */
+int rk_dien_aux_loss(const float* hs, const float* key_table, int64_t key_rows, int64_t ld_key,
+                     const int64_t* seq, int64_t ld_seq, const int64_t* neg_seq, int64_t ld_neg_seq,
+                     int32_t T, int32_t T_neg, const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                     const float* W_aux, float* per_sample, float* mean, void* stream);
+
+/* rk_dien_aux_loss over dense tensors: history row t of sample b at keys + b*ld_keys_b + t*ld_keys_t,
+ * negative row i (= t * T_neg + k) at neg + b*ld_neg_b + i*ld_neg_r (16-B aligned rows; rows of
+ * masked steps are never read).  Bit-equal to rk_dien_aux_loss on the same data.                 */
+int rk_dien_aux_loss_dense(const float* hs, const float* keys, int64_t ld_keys_b, int64_t ld_keys_t,
+                           const float* neg, int64_t ld_neg_b, int64_t ld_neg_r, int32_t T, int32_t T_neg,
+                           const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh, const float* W_aux,
+                           float* per_sample, float* mean, void* stream);
+
+/* Backward of the auxiliary loss given d_loss[0] = dL/d(mean), read on the device (the call is
+ * graph-capturable); the dots are recomputed.  With k = d_loss[0] / batch, cpos = -k sig(-pos_t),
+ * cneg_k = k sig(neg_{t,k}), dg_t = cpos e_{t+1} + sum_k cneg_k n_{t,k}:
+ *   d_hs  [batch, T, nh]          = W_aux^T dg_t        (rows t >= seq_len-1 exact zeros)
+ *   dkeys [batch, T, H]           row t+1 = cpos g_t    (row 0 and rows >= seq_len exact zeros)
+ *   dneg  [batch, (T-1) T_neg, H] row t*T_neg+k = cneg_k g_t (exact zeros for t >= seq_len-1)
+ *   dW_aux [H, nh]                = sum_{b,t} dg_t h_t^T
+ * all contiguous, 16-B aligned, every element written.  Sources: seq != NULL: keys = the table,
+ * ids seq / neg_seq as in the forward, neg ignored; neg_masked (NULL or [batch, (T-1) T_neg])
+ * receives the negative ids with 0 at masked steps and seq_masked (NULL or [batch, T]) the history
+ * ids with 0 wherever dkeys is zero (t == 0, t >= seq_len), the index lists for
+ * rk_embedding_backward of dneg and of dkeys.  seq == NULL: keys / neg dense as in
+ * rk_dien_aux_loss_dense (ld_key = the history's row stride), neg_seq and both masked lists NULL.  One item kernel writes dg rows to the workspace; d_hs is
+ * one rk_gemm and dW_aux one rk_gemm_wgrad over them: fixed-order sums, no float atomics.
+ * workspace: rk_dien_aux_loss_backward_workspace_floats(batch, T, H, nh) floats, 16-B aligned.   */
+int64_t rk_dien_aux_loss_backward_workspace_floats(int64_t batch, int32_t T, int32_t H, int32_t nh);
+int rk_dien_aux_loss_backward(const float* hs, const float* keys, int64_t key_rows, int64_t ld_key,
+                              const int64_t* seq, int64_t ld_seq, int64_t ld_keys_b, const float* neg,
+                              int64_t ld_neg_b, int64_t ld_neg_r, const int64_t* neg_seq, int64_t ld_neg_seq,
+                              int32_t T, int32_t T_neg, const int64_t* seq_len, int64_t batch, int32_t H,
+                              int32_t nh, const float* W_aux, const float* d_loss, float* d_hs, float* dkeys,
+                              float* dneg, int64_t* seq_masked, int64_t* neg_masked, float* dW_aux,
+                              float* workspace, int64_t workspace_floats, void* stream);
 
 /* Dice (din.py:26-36) in eval: p = sigmoid(x * bn_scale + bn_shift) with the BatchNorm folded
  * by rk_bn_fold, y = alpha * (1 - p) * x + p * x;  x, y: [rows, n].                          */

@@ -4,6 +4,9 @@ user has without the kernel — of the same forward written as eager torch ops o
 the same process (the per-step loop of tests/dien_ref.py in fp32).  Then the train step of
 rankops.DIEN(trainable=True): forward + backward + rankops.Adam, eager and as one hipGraph, against
 that loop with a train-mode tail differentiated by torch autograd (torch.optim.Adam, fused).
+`--aux` runs only the auxiliary-loss leg: the graph-replayed train step without and with
+use_auxiliary_loss (3 negatives per step), and the rk_dien_aux_loss / rk_dien_aux_loss_backward
+launches alone.
 
 Device times are HIP events around hipGraph replays (the host's launch cost excluded); the eager
 loop is timed both as it runs (host clock around a synchronise: its ~1,300 launches are
@@ -133,6 +136,49 @@ def train_step_times(cell, inp):
     return out
 
 
+def aux_step_times(cell, inp, T_neg=3):
+    """The graph-replayed train step without and with the auxiliary loss (loss = bce + aux_loss,
+    T_neg negatives per step drawn once), and the auxiliary forward / backward launches alone, in us."""
+    label = (torch.rand(B, device="cuda") < 0.3).float()
+    crit = torch.nn.BCELoss()
+    seq = dict(inp["sequence"])
+    seq["neg_" + dien_ref.SEQ_KEY] = torch.randint(0, H.WECHAT_VOCAB["feedid"], (B, (T - 1) * T_neg), device="cuda")
+    out = {"T_neg": T_neg}
+    for aux in (False, True):
+        torch.manual_seed(0)
+        m = rankops.DIEN(None, custom_gru_type=cell, vocab_sizes=H.WECHAT_VOCAB, trainable=True,
+                         use_auxiliary_loss=aux, negative_sample_number=T_neg).cuda().train()
+        opt = rankops.Adam(m.parameters(), lr=1e-3, capturable=True)
+
+        def step():
+            opt.zero_grad(set_to_none=False)
+            res = m(inp["dense"], inp["category"], seq, inp["target"])
+            loss = crit(res[0].squeeze(), label)
+            (loss + res[2] if aux else loss).backward()
+            opt.step()
+
+        step()  # allocates gradients and optimizer state
+        torch.cuda.synchronize()
+        out["train_step_aux_graph_us" if aux else "train_step_graph_us"] = 1e3 * graph_avg_ms(step, iters=20, grad=True)
+    out["aux_over_plain"] = out["train_step_aux_graph_us"] / out["train_step_graph_us"]
+    # the two auxiliary launches alone, on the states of one train forward
+    with torch.no_grad():
+        table = m.embeddings["feedid"].weight
+        ids, lens = seq[dien_ref.SEQ_KEY], seq[f"{dien_ref.SEQ_KEY}_length"]
+        _, hs = rankops.dien_interest_gather(table[inp["target"]["feedid"]], table, ids, lens, m.interest_weights(),
+                                             cell, return_states=True)
+        neg = seq["neg_" + dien_ref.SEQ_KEY]
+        per, mean = torch.empty(B, device="cuda"), torch.empty(1, device="cuda")
+        one = torch.ones(1, device="cuda")
+        w_aux = m.aux_project_matrix.detach()
+        out["aux_forward_us"] = 1e3 * bench.graph_kernel_avg_ms(
+            lambda: ops.dien_aux_loss(hs, table, ids, None, neg, lens, T, T_neg, 16, 8, w_aux, per, mean, B, hs.device))
+        out["aux_backward_us"] = 1e3 * bench.graph_kernel_avg_ms(
+            lambda: ops.dien_aux_loss_backward(hs, table, ids, None, neg, lens, T, T_neg, 16, 8, w_aux, one, B,
+                                               hs.device))
+    return out
+
+
 def main():
     assert torch.cuda.is_available(), "dien_time needs a ROCm GPU"
     rankops.load_library()
@@ -140,6 +186,14 @@ def main():
               "max_clock_khz": getattr(torch.cuda.get_device_properties(0), "clock_rate", None),
               "sclk_before": shader_clock()}
     inp = H.to_device(H.din_inputs(B, T, H.WECHAT_VOCAB, seed=1), "cuda")
+    if "--aux" in sys.argv[1:]:  # only the auxiliary-loss leg
+        for cell in ("AGRU", "AUGRU"):
+            result[cell] = aux_step_times(cell, inp)
+            print(f"{cell}: " + ", ".join(f"{k} {v:.4g}" for k, v in result[cell].items()), flush=True)
+        result["sclk_after"] = shader_clock()
+        assert rankops.error_flags() == 0
+        print(json.dumps(result))
+        return
     for cell in ("AGRU", "AUGRU"):
         torch.manual_seed(0)
         m = rankops.DIEN(None, custom_gru_type=cell, vocab_sizes=H.WECHAT_VOCAB)
