@@ -17,7 +17,8 @@ all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) 
 reference's Dataset bucketing + collate with C++ column bucketing and one H2D copy per batch;
 `rankops.metrics` (EvalAccumulator, roc_auc) computes evaluate()'s loss / accuracy / AUC on the GPU;
 `rankops.train` holds the HIP backward (train-mode forwards return autograd-connected outputs)
-and `rankops.Adam`, a one-launch torch.optim.Adam.
+and `rankops.Adam`, a one-launch torch.optim.Adam; with `sparse_grad=True` a model's tables get
+sparse gradients and `rankops.SparseAdam` (torch.optim.SparseAdam / LazyAdam) updates only their rows.
 Import order matters: torch first, so librankops binds to torch's HIP runtime.
 """
 import torch  # noqa: F401
@@ -33,12 +34,12 @@ from .dien import DIEN, dien_aux_loss, dien_aux_loss_gather, dien_interest, dien
 from .fwfm import FwFM  # noqa: F401
 from .loader import BatchAssembler, Vocabulary, label_encode, wechat_vocabularies  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
-from .train import Adam  # noqa: F401
+from .train import Adam, SparseAdam  # noqa: F401
 
 __all__ = [
     "AFM", "BSTModel", "BSTTransformer", "BatchAssembler", "DCNModel", "DIN", "DeepCrossingModel", "DeepFM",
     "Dice", "FwFM", "RankOpsError", "Vocabulary", "create_feature_columns", "cross_layer", "din_attention", "din_attention_gather",
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
-    "dien_aux_loss", "dien_aux_loss_gather",
+    "dien_aux_loss", "dien_aux_loss_gather", "SparseAdam",
 ]

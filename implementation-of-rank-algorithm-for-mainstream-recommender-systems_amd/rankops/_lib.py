@@ -103,6 +103,17 @@ class AdamTensor(ctypes.Structure):
                 ("numel", c_int64), ("step", c_void_p)]
 
 
+class SparseAdamTensor(ctypes.Structure):
+    _fields_ = [("param", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("rows", c_int64),
+                ("ld", c_int64), ("idx", c_void_p), ("idx_stride", c_int64), ("nnz", c_int64), ("values", c_void_p),
+                ("ld_values", c_int64), ("dim", c_int32), ("coalesced", c_int32)]
+
+
+class PackBlock(ctypes.Structure):
+    _fields_ = [("src", c_void_p), ("add", c_void_p), ("dst", c_void_p), ("ld_src", c_int64), ("ld_add", c_int64),
+                ("rows", c_int64), ("dim", c_int32), ("reserved", c_int32)]
+
+
 RK_MLP_MAX_LAYERS = 8
 _SEG_P = POINTER(Segment)
 _EPI_P = POINTER(Epilogue)
@@ -351,6 +362,11 @@ SIGNATURES = {
     "rk_embedding_backward": (ctypes.c_int, [_SEG_P, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
     "rk_adam_step": (ctypes.c_int, [POINTER(AdamTensor), c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                     ctypes.c_double, ctypes.c_double, c_int64, c_void_p]),
+    "rk_sparse_adam_step_workspace_size": (ctypes.c_int, [POINTER(SparseAdamTensor), c_int32, POINTER(c_int64)]),
+    "rk_sparse_adam_step": (ctypes.c_int, [POINTER(SparseAdamTensor), c_int32, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_double, c_int64, c_void_p, c_void_p, c_int64,
+                                           c_void_p]),
+    "rk_pack_blocks": (ctypes.c_int, [POINTER(PackBlock), c_int32, c_void_p]),
     "rk_eval_batch": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_int32, c_void_p, c_void_p, c_void_p]),
     "rk_auc_workspace_size": (ctypes.c_int, [c_int64, POINTER(c_int64)]),
     "rk_auc": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -42,8 +42,9 @@ def create_feature_columns(vocabulary_dir):
 
 
 class AFM(EngineModule):
-    def __init__(self, feature_columns, embedding_dim, attention_factor):
+    def __init__(self, feature_columns, embedding_dim, attention_factor, *, sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         self.feature_columns = feature_columns
         self.embedding_dim = embedding_dim
         self.attention_factor = attention_factor

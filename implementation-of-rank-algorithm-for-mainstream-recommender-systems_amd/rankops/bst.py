@@ -157,8 +157,9 @@ class BSTTransformer(EngineModule):
 class BSTModel(EngineModule):
     def __init__(self, vocab_dir, hidden_units=[512, 256, 128], dropout_rate=0.1, batch_norm=True, d_model=16,
                  nhead=4, num_transformer_blocks=1, max_seq_length=50, pooling_method='sum', *,
-                 vocab_sizes=None):
+                 vocab_sizes=None, sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         self.vocab_sizes = {f: table_rows(vocab_dir, f, vocab_sizes) for f in FIELDS}
         self.num_dense_features = 16
         self.d_model = d_model

@@ -42,8 +42,9 @@ def cross_layer(x0: torch.Tensor, xl: torch.Tensor, index: int) -> torch.Tensor:
 
 class DCNModel(EngineModule):
     def __init__(self, vocab_dir, hidden_units=[512, 256, 128], num_cross_layer=1, *, vocab_sizes=None,
-                 interaction_weights="per_call"):
+                 interaction_weights="per_call", sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         fields = ("userid", "feedid", "device", "authorid", "bgm_song_id", "bgm_singer_id", "manual_tag_list")
         self.vocab_sizes = {f: table_rows(vocab_dir, f, vocab_sizes) for f in fields}
         self.num_dense_features = 16

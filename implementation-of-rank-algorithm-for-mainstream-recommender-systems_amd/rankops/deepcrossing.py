@@ -37,8 +37,9 @@ def residual_unit(input_tensor, internal_dim, index, weights=None):
 
 class DeepCrossingModel(common.EngineModule):
     def __init__(self, vocab_dir, residual_internal_dim=128, residual_network_num=1, *, vocab_sizes=None,
-                 interaction_weights="per_call"):
+                 interaction_weights="per_call", sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         fields = ("userid", "feedid", "device", "authorid", "bgm_song_id", "bgm_singer_id", "manual_tag_list")
         self.vocab_sizes = {f: table_rows(vocab_dir, f, vocab_sizes) for f in fields}
         self.num_dense_features = 16

@@ -45,8 +45,9 @@ FUSED_WHOLE = True
 
 class DeepFM(EngineModule):
     def __init__(self, vocab_dir, embedding_dim=8, hidden_units=None, dropout_rate=0.1, batch_norm=True, *,
-                 vocab_sizes=None):
+                 vocab_sizes=None, sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         if hidden_units is None:
             hidden_units = [512, 256, 128]
         if vocab_sizes is not None and any(f not in WECHAT_FIELDS for f in vocab_sizes):

@@ -408,8 +408,9 @@ def _tf_linear(in_features: int, out_features: int, bias_value: float = 0.0) -> 
 class DIEN(EngineModule):
     def __init__(self, vocab_dir, hidden_units=None, activation='dice', dropout_rate=0.1, batch_norm=True,
                  custom_gru_type='AGRU', gru_output_units=8, *, vocab_sizes=None, embedding_dim=16,
-                 trainable=False, use_auxiliary_loss=False, negative_sample_number=3):
+                 trainable=False, use_auxiliary_loss=False, negative_sample_number=3, sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         self.use_auxiliary_loss = bool(use_auxiliary_loss)
         self.negative_sample_number = int(negative_sample_number)
         if self.use_auxiliary_loss and self.negative_sample_number < 1:

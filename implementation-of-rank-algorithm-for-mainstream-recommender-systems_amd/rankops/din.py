@@ -133,8 +133,9 @@ def din_attention_gather(query, keys_table, seq, keys_length, is_softmax=False, 
 class DIN(EngineModule):
     def __init__(self, vocab_dir, hidden_units=None, activation='dice', dropout_rate=0.1, batch_norm=True,
                  use_softmax=False, l2_lambda=0.2, mini_batch_aware_regularization=True, *, vocab_sizes=None,
-                 embedding_dim=16, interaction_weights="per_call"):
+                 embedding_dim=16, interaction_weights="per_call", sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         if hidden_units is None:
             hidden_units = [512, 256, 128]
         self.activation = activation

@@ -24,8 +24,9 @@ FWFM_FIELDS = ("userid", "feedid", "device", "authorid", "bgm_song_id", "bgm_sin
 
 
 class FwFM(EngineModule):
-    def __init__(self, field_dims, embed_dim, *, field_names=FWFM_FIELDS):
+    def __init__(self, field_dims, embed_dim, *, field_names=FWFM_FIELDS, sparse_grad=False):
         super().__init__()
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         self.field_dims = field_dims
         self.num_fields = len(field_dims)
         self.embed_dim = embed_dim

@@ -884,6 +884,79 @@ def adam_step(entries, lr, beta1, beta2, eps, weight_decay, step, stream):
     check(lib.rk_adam_step(arr, len(entries), lr, beta1, beta2, eps, weight_decay, step, stream), "rk_adam_step")
 
 
+def sparse_adam_tensors(entries):
+    """rk_sparse_adam_tensor array of entries (param, exp_avg, exp_avg_sq, idx, values, coalesced):
+    [rows, dim] float32 tables with unit column stride, idx an int64 vector (any stride), values
+    [nnz, dim] float32 rows with unit column stride."""
+    arr = (_lib.SparseAdamTensor * max(1, len(entries)))()
+    for a, (p, m, v, idx, val, coalesced) in zip(arr, entries):
+        rows, dim = p.shape
+        nnz = idx.numel()
+        if any(t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 for t in (p, m, v)) \
+                or m.shape != p.shape or v.shape != p.shape or m.stride() != p.stride() or v.stride() != p.stride():
+            raise ValueError("rankops sparse_adam_step: param / exp_avg / exp_avg_sq must be float32 [rows, dim] "
+                             "tensors of one layout")
+        if idx.dtype != torch.int64 or idx.dim() != 1 or val.dtype != torch.float32 \
+                or tuple(val.shape) != (nnz, dim) or (nnz and dim > 1 and val.stride(1) != 1):
+            raise ValueError("rankops sparse_adam_step: idx must be an int64 vector and values float32 [nnz, dim]")
+        a.param, a.exp_avg, a.exp_avg_sq = p.data_ptr(), m.data_ptr(), v.data_ptr()
+        a.rows, a.ld, a.dim = rows, p.stride(0) if rows > 1 else dim, dim
+        a.idx, a.idx_stride, a.nnz = idx.data_ptr(), idx.stride(0) if nnz > 1 else 1, nnz
+        a.values, a.ld_values = val.data_ptr(), val.stride(0) if nnz > 1 else dim
+        a.coalesced = int(bool(coalesced))
+    return arr
+
+
+def sparse_adam_workspace_size(arr, n) -> int:
+    nbytes = ctypes.c_int64()
+    check(_lib.load().rk_sparse_adam_step_workspace_size(arr, n, ctypes.byref(nbytes)),
+          "rk_sparse_adam_step_workspace_size")
+    return nbytes.value
+
+
+_SPARSE_ADAM_ARRAYS = {}
+
+
+def sparse_adam_step(entries, lr, beta1, beta2, eps, step, stream, device_step=None, workspace=None):
+    """rk_sparse_adam_step over entries (see sparse_adam_tensors); `workspace` a uint8 tensor of at
+    least the needed size, or None to allocate one.  Returns the workspace used."""
+    if not entries:
+        return workspace
+    # the marshalled array and its workspace size are memoized on every field of the structs, as
+    # table_seg_array's are: a repeated step, whose tables, ids and value buffers come back at the
+    # same addresses, plans nothing again on the host
+    key = tuple((p.data_ptr(), p.shape, p.stride(), m.data_ptr(), v.data_ptr(), i.data_ptr(), i.shape, i.stride(),
+                 x.data_ptr(), x.shape, x.stride(), x.dtype, bool(c)) for p, m, v, i, x, c in entries)
+    hit = _SPARSE_ADAM_ARRAYS.get(key)
+    if hit is None:
+        arr = sparse_adam_tensors(entries)
+        hit = (arr, sparse_adam_workspace_size(arr, len(entries)))
+        if len(_SPARSE_ADAM_ARRAYS) >= 64:
+            _SPARSE_ADAM_ARRAYS.clear()
+        _SPARSE_ADAM_ARRAYS[key] = hit
+    arr, need = hit
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=entries[0][0].device, dtype=torch.uint8)
+    check(_lib.load().rk_sparse_adam_step(arr, len(entries), lr, beta1, beta2, eps, int(step), ptr(device_step),
+                                          ptr(workspace), workspace.numel(), stream), "rk_sparse_adam_step")
+    return workspace
+
+
+def pack_blocks(blocks, stream):
+    """rk_pack_blocks: blocks (src tensor, first column, dst [rows, dim] contiguous[, add tensor]) —
+    dst = the dim columns of src's rows from that column on (plus the same columns of add's rows
+    when given), every block in one launch."""
+    if not blocks:
+        return
+    arr = (_lib.PackBlock * len(blocks))()
+    for a, (src, col, dst, *add) in zip(arr, blocks):
+        a.src, a.dst = fptr(src, col), dst.data_ptr()
+        a.ld_src, a.rows, a.dim = src.stride(0), dst.shape[0], dst.shape[1]
+        if add and add[0] is not None:
+            a.add, a.ld_add = fptr(add[0], col), add[0].stride(0)
+    check(_lib.load().rk_pack_blocks(arr, len(blocks), stream), "rk_pack_blocks")
+
+
 def rng_next(counter: torch.Tensor, slot: torch.Tensor):
     lib = _lib.load()
     check(lib.rk_rng_next(ptr(counter), ptr(slot), _lib.stream_of(counter)), "rk_rng_next")

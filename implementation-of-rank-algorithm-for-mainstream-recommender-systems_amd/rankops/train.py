@@ -20,6 +20,11 @@ BatchNorm batch statistics, Dropout, attention backward, l2 term), BSTModel (`bs
 Dropout inside the transformer blocks, LayerNorm, attention backward) and FwFM (`fwfm.py:87-139`).
 Dropout masks are a counter hash on the device (train_common.h): a random choice like torch's own
 masks, so parity tests hand the engine's masks to the oracle.
+
+Embedding gradients are dense by default (`nn.Embedding(sparse=False)`).  A model built with
+`sparse_grad=True` hands every table a sparse COO gradient instead (`sparse_embedding_grads`), and
+`rankops.SparseAdam` (`rk_sparse_adam_step`: torch.optim.SparseAdam / LazyAdam, `DIEN/dien.py:328`)
+updates only the rows of the batch: the step then scales with the batch, not with the tables.
 """
 from __future__ import annotations
 
@@ -99,16 +104,46 @@ def zero_grads(weights, device):
     return [flat[o:o + w.numel()].view(w.shape) for o, w in zip(offs, weights)]
 
 
-def embedding_grads(weights, idx, col0, dx, cols=None):
+def sparse_embedding_grads(weights, sources):
+    """nn.Embedding(sparse=True) gradients (model(..., sparse_grad=True)): per table one
+    torch.sparse_coo_tensor [V, D] whose indices are the looked-up ids as given (unsorted, with
+    duplicates, padded positions included) and whose values are the matching rows of the backward's
+    dx, nnz = the number of lookups (static for a fixed batch shape, so the step stays capturable).
+    sources[k] lists the (ids, matrix, first column[, second matrix]) lookups that feed table k (the
+    value rows are the matrix's, plus the second matrix's where a gradient is kept as two summands); a table fed from
+    several places gets their entries concatenated (its id lists by one torch.cat; a table with a
+    single lookup keeps the caller's id tensor).  The value rows of all tables are packed into
+    one flat buffer by one rk_pack_blocks launch; nothing of a table's size is allocated."""
+    dev = weights[0].device
+    counts = [sum(look[0].numel() for look in src) for src in sources]
+    flat = torch.empty(max(1, sum(n * w.shape[1] for n, w in zip(counts, weights))), device=dev, dtype=torch.float32)
+    blocks, grads, o = [], [], 0
+    for w, src, n in zip(weights, sources, counts):
+        D = w.shape[1]
+        vals = flat[o:o + n * D].view(n, D)
+        o += n * D
+        r = 0
+        for ids, mat, col, *add in src:
+            blocks.append((mat, col, vals[r:r + ids.numel()], *add))
+            r += ids.numel()
+        ids = src[0][0].reshape(-1) if len(src) == 1 else torch.cat([look[0].reshape(-1) for look in src])
+        grads.append(torch.sparse_coo_tensor(ids.unsqueeze(0), vals, w.shape, check_invariants=False))
+    ops.pack_blocks(blocks, ops._lib.raw_stream(dev))
+    return grads
+
+
+def embedding_grads(weights, idx, col0, dx, cols=None, sparse=False):
     """Dense nn.Embedding gradients of the tables whose rows sit side by side in dx from column
     col0 on (or at the given `cols`): one zero-filled flat buffer for all tables (one fill),
-    then rk_embedding_backward."""
-    grads = zero_grads(weights, dx.device)
+    then rk_embedding_backward.  sparse: sparse_embedding_grads of the same lookups instead."""
     if cols is None:
         cols, col = [], col0
-        for g in grads:
+        for w in weights:
             cols.append(col)
-            col += g.shape[1]
+            col += w.shape[1]
+    if sparse:
+        return sparse_embedding_grads(weights, [[(i, dx, c)] for i, c in zip(idx, cols)])
+    grads = zero_grads(weights, dx.device)
     ops.embedding_backward(ops.table_seg_array(grads, idx, cols), dx.shape[0], dx)
     return grads
 
@@ -163,7 +198,7 @@ class _DCNTrain(torch.autograd.Function):
         dx0, lin_grads = mlp_relu_backward(dh, hs, linears)
         ops.dcn_cross_backward(x0, cw, cb, model.num_cross_layer, dxl, dx0, accumulate=True)
         emb_grads = embedding_grads([e.weight for e in model.embeddings.values()], ctx.idx,
-                                    model.num_dense_features, dx0)
+                                    model.num_dense_features, dx0, sparse=model.sparse_grad)
         flat = [t for pair in lin_grads for t in pair]
         return (None, None, None, None, None, *emb_grads, *flat, dw_out, db_out)
 
@@ -257,7 +292,7 @@ class _DeepCrossingTrain(torch.autograd.Function):
             ops.gemm(False, True, B, d, I, dh, I, w1, d, dx, A_mask=h, accumulate=True)  # + dz1 W1
             dy = dx
         emb_grads = embedding_grads([e.weight for e in model.embeddings.values()], ctx.idx,
-                                    model.num_dense_features, dy)
+                                    model.num_dense_features, dy, sparse=model.sparse_grad)
         return (None, None, None, None, *emb_grads, dw_out, db_out)
 
 
@@ -421,9 +456,15 @@ class _DeepFMTrain(torch.autograd.Function):
         d_deep_in, unit_grads = deep_stack_backward(dy, deep_in, units, saved, ctx.seed, slot)
         d_second = torch.empty(B, F * D, device=dev, dtype=torch.float32)
         ops.fm_backward(deep_in, d_deep_in, dfm2, F, D, d_second)
-        g2 = embedding_grads([model.second_order_embeddings[n].weight for n in ctx.names], ctx.idx, 0, d_second)
-        g1 = embedding_grads([model.first_order_embeddings[n].weight for n in ctx.names], ctx.idx, 0, dfm1,
-                             cols=[0] * F)
+        w2 = [model.second_order_embeddings[n].weight for n in ctx.names]
+        w1 = [model.first_order_embeddings[n].weight for n in ctx.names]
+        if model.sparse_grad:  # both table sets in one packing launch
+            g = sparse_embedding_grads(w1 + w2, [[(i, dfm1, 0)] for i in ctx.idx]
+                                       + [[(i, d_second, f * D)] for f, i in enumerate(ctx.idx)])
+            g1, g2 = g[:F], g[F:]
+        else:
+            g2 = embedding_grads(w2, ctx.idx, 0, d_second)
+            g1 = embedding_grads(w1, ctx.idx, 0, dfm1, cols=[0] * F)
         flat_g = [t for g in unit_grads for t in g if t is not None]
         return (None, None, None, *g1, *g2, *flat_g, dw_do, db_do, dfinal_w, dfinal_b)
 
@@ -605,6 +646,13 @@ class _DINTrain(torch.autograd.Function):
         del dcross
         # nn.Embedding gradients: one zeroed buffer per distinct table, every lookup scattered into it
         weights, looks = ctx.emb_plan
+        flat = [t for g in unit_grads for t in g]
+        if model.sparse_grad:  # the shared feedid table: target lookup + every history position
+            sources = [[] for _ in weights]
+            for k, i, col in looks:
+                sources[k].append((i, dxr, col))
+            sources[pl["seq_slot"]].append((pl["seq"].reshape(-1), dkeys.view(M, H), 0))
+            return (None, None, None, None, *sparse_embedding_grads(weights, sources), *flat, dw_out, db_out)
         grads = zero_grads(weights, dev)
         segs = [ops.table_segment(grads[k], i, col) for k, i, col in looks]
         ops.embedding_backward(segs, B, dxr)
@@ -616,7 +664,6 @@ class _DINTrain(torch.autograd.Function):
         # weights are 1/T, is still exact, only slower).
         ops.embedding_backward([ops.table_segment(grads[pl["seq_slot"]], pl["seq"].reshape(-1), 0)], M,
                                dkeys.view(M, H))
-        flat = [t for g in unit_grads for t in g]
         return (None, None, None, None, *grads, *flat, dw_out, db_out)
 
 
@@ -745,6 +792,15 @@ class _DIENTrain(torch.autograd.Function):
                                             d_hs=d_hs, accumulate_dkeys=d_hs is not None)
         # one zeroed buffer per distinct table; feedid takes the target lookup and the history scatter
         # (key rows past the length are exact zeros: the zero-skipping scatter stays contention-free)
+        if model.sparse_grad:  # feedid: target lookup + history (+ the auxiliary loss's negatives)
+            sources = [[] for _ in weights]
+            for k, i, col in looks:
+                sources[k].append((i, dxr, col))
+            sources[pl["seq_slot"]].append((ids.reshape(-1), dkeys.view(B * T, H), 0))
+            if dneg is not None and dneg.numel():
+                sources[pl["seq_slot"]].append((neg_ids.reshape(-1), dneg.view(neg_ids.numel(), H), 0))
+            return (None, None, None, *sparse_embedding_grads(weights, sources), *wgrads,
+                    *[t for g in unit_grads for t in g], dw_out, db_out, *([daux_w] if aux else []))
         grads = zero_grads(weights, dev)
         ops.embedding_backward([ops.table_segment(grads[k], i, col) for k, i, col in looks], B, dxr)
         ops.embedding_backward([ops.table_segment(grads[pl["seq_slot"]], ids.reshape(-1), 0)], B * T,
@@ -844,7 +900,7 @@ class _AFMTrain(torch.autograd.Function):
         ops.gemm(False, True, M, D, A, da1, A, w1, D, d_pairs, accumulate=True)
         d_emb = torch.empty(B, F * D, **f32)
         ops.afm_pair_fold(d_pairs, emb, F, D, d_emb)
-        g_emb = embedding_grads(list(tables), idx, 0, d_emb)
+        g_emb = embedding_grads(list(tables), idx, 0, d_emb, sparse=model.sparse_grad)
         o = 0
         dwd, dbd = acc[o:o + nd].view(1, nd), acc[o + nd:o + nd + 1]
         o += nd + 1
@@ -911,6 +967,23 @@ def _lin_grads(dy, x, w, need_dx=True, dx=None, accumulate=False):
             dx = torch.empty(M, K, device=dy.device, dtype=torch.float32)
         ops.gemm(False, True, M, K, N, dy, dy.stride(0), w, w.stride(0), dx, accumulate=accumulate)
     return dW, db, dx
+
+
+_POSITION_IDS = {}
+
+
+def _position_ids(B, T, device):
+    """The position lookups of a [B, T] batch, 0..T-1 per sample, flattened; kept per (B, T, device)
+    (a tensor made while a graph is being captured belongs to that graph and is not kept)."""
+    key = (B, T, device)
+    ids = _POSITION_IDS.get(key)
+    if ids is None:
+        ids = torch.arange(T, device=device).repeat(B)
+        if not torch.cuda.is_current_stream_capturing():
+            if len(_POSITION_IDS) >= 64:
+                _POSITION_IDS.clear()
+            _POSITION_IDS[key] = ids
+    return ids
 
 
 class _BSTTrain(torch.autograd.Function):
@@ -1017,8 +1090,9 @@ class _BSTTrain(torch.autograd.Function):
         mean_pool = model.pooling_method != "sum"
         dx = None  # the last block's LN2 backward reads the pooling gradient d_row directly
         tables, looks = plan["tables"], plan["looks"]
-        tgrads = zero_grads(tables, dev)
+        tgrads = None if model.sparse_grad else zero_grads(tables, dev)
         block_grads = [None] * nb
+        pos_looks = []  # sparse_grad: (position table, its value rows) per block, last block first
         for i in range(nb - 1, -1, -1):
             blk = model.transformer_blocks[i]
             x, xp, qkv, probs, cx, r1, out1, m1, s1, f1, a, r2, m2, s2 = saves[i]
@@ -1052,16 +1126,39 @@ class _BSTTrain(torch.autograd.Function):
             dWq, dbq, _ = _lin_grads(dQ, xp, blk.w_q.weight, dx=dxp, accumulate=True)
             dWk, dbk, _ = _lin_grads(dK, xp, blk.w_k.weight, dx=dxp, accumulate=True)
             # position embedding: every row m adds into pos[m % T]
-            gpos = torch.zeros_like(blk.position_embedding.weight)
-            ops.bst_pos_backward(dxp, B, T, gpos)
             # keys/queries carry x + pos, values carry x: dL/dx = dL/dxp + dV Wv
-            dWv, dbv, _ = _lin_grads(dV, x, blk.w_v.weight, dx=dxp, accumulate=True)
+            if model.sparse_grad:
+                # the position table's value rows are dL/dxp itself (the lookups of positions 0..T-1
+                # per sample): dxp stays as it is until the one packing launch at the end, and dV Wv
+                # goes to a buffer of its own
+                gpos = None
+                pos_looks.append((blk.position_embedding.weight, dxp))
+                dWv, dbv, dxv = _lin_grads(dV, x, blk.w_v.weight)
+                dx = (dxp, dxv) if i == 0 else torch.add(dxp, dxv)
+            else:
+                gpos = torch.zeros_like(blk.position_embedding.weight)
+                ops.bst_pos_backward(dxp, B, T, gpos)
+                dWv, dbv, _ = _lin_grads(dV, x, blk.w_v.weight, dx=dxp, accumulate=True)
+                dx = dxp
             block_grads[i] = [gpos, dWq, dbq, dWk, dbk, dWv, dbv, dWo, dbo, dg1, dbe1, dg2, dbe2, dW1, db1, dW2, db2]
-            dx = dxp
         if nb == 0:  # no blocks: the pooling gradient goes straight to the gathered sequence rows
             dx = torch.empty(M, d, **f32)
             ops.bst_pool_backward(d_row, col, B, T, d, seq_len, mean_pool, dx)
         # embedding tables: the category lookups from the dnn input row, the behaviour sequence from dx
+        flat_units = [t for g in unit_grads for t in g if t is not None]
+        if model.sparse_grad:  # padded positions stay in the list with the gradient sum pooling gives them
+            sources = [[] for _ in tables]
+            for k, idx, c in looks:
+                sources[k].append((idx, d_row, c))
+            # block 0's dL/dx arrives as its two summands (dL/dxp, dV Wv), added while packing
+            sources[plan["feed_slot"]].append((seq.reshape(-1), *((dx[0], 0, dx[1]) if nb else (dx, 0))))
+            pos_ids = _position_ids(B, T, dev)
+            grads = sparse_embedding_grads(list(tables) + [w for w, _ in pos_looks],
+                                           sources + [[(pos_ids, vals, 0)] for _, vals in pos_looks])
+            for i, g in zip(range(nb - 1, -1, -1), grads[len(tables):]):
+                block_grads[i][0] = g
+            return (None, None, *grads[:len(tables)], *[t for g in block_grads for t in g], *flat_units, dw_last,
+                    db_last)
         segs = [ops.table_segment(tgrads[k], idx, c) for k, idx, c in looks]
         if segs:
             ops.embedding_backward(segs, B, d_row)
@@ -1069,7 +1166,6 @@ class _BSTTrain(torch.autograd.Function):
         # pre-summed per sample (rk_embedding_backward_seq), else the sorted segment-reduce
         if not ops.embedding_backward_seq(tgrads[plan["feed_slot"]], seq, dx):
             ops.embedding_backward_sorted(ops.table_segment(tgrads[plan["feed_slot"]], seq.view(-1), 0), M, dx)
-        flat_units = [t for g in unit_grads for t in g if t is not None]
         return (None, None, *tgrads, *[t for g in block_grads for t in g], *flat_units, dw_last, db_last)
 
 
@@ -1146,8 +1242,13 @@ class _FwFMTrain(torch.autograd.Function):
         d_b = torch.empty(1, **f32)
         ops.fwfm_backward(ops.table_seg_array(emb_w, idx, [0] * F), D, B, field_weight, prob,
                           _grad_out(dprob, prob), d_emb, dz, d_r, d_b)
-        g_emb = embedding_grads(list(emb_w), idx, 0, d_emb)
-        g_lin = embedding_grads(list(lin_w), idx, 0, dz, cols=[0] * F)
+        if model.sparse_grad:  # both table sets in one packing launch
+            g = sparse_embedding_grads(list(lin_w) + list(emb_w), [[(i, dz, 0)] for i in idx]
+                                       + [[(i, d_emb, f * D)] for f, i in enumerate(idx)])
+            g_lin, g_emb = g[:F], g[F:]
+        else:
+            g_emb = embedding_grads(list(emb_w), idx, 0, d_emb)
+            g_lin = embedding_grads(list(lin_w), idx, 0, dz, cols=[0] * F)
         return (None, None, None, *g_lin, *g_emb, d_r, d_b)
 
 
@@ -1263,7 +1364,7 @@ class Adam(torch.optim.Optimizer):
         counts) takes the general path, which rebuilds the block next time."""
         params = group["params"]
         grads = [p.grad for p in params]
-        if not params or any(g is None for g in grads):
+        if not params or any(g is None or g.is_sparse for g in grads):  # sparse: the general path raises
             return False
         cache = self.__dict__.setdefault("_fast", {})
         key = tuple(p.data_ptr() for p in params)
@@ -1323,10 +1424,157 @@ class Adam(torch.optim.Optimizer):
     def state_dict(self):
         """Optimizer.state_dict with a step tensor of its own per parameter (the fast path shares
         one per group; another optimizer loading the dict must not see them aliased)."""
+        sd = super().state_dict()  # its per-parameter dicts are the live ones: hand out copies
+        sd["state"] = {k: ({**st, "step": st["step"].clone()} if "step" in st else dict(st))
+                       for k, st in sd["state"].items()}
+        return sd
+
+
+class SparseAdam(torch.optim.Optimizer):
+    """torch.optim.SparseAdam (= TF LazyAdamOptimizer's arithmetic, DIEN/dien.py:328) with the update
+    of all tables of a group as one rk_sparse_adam_step call: only the rows in a table's sparse
+    gradient are read and written, whatever the table's size.  Same constructor arguments and
+    state layout (`step`, `exp_avg`, `exp_avg_sq`), so state dicts move between this class and
+    torch.optim.SparseAdam.  It takes any sparse COO gradient of a [V, D] float32 table: the
+    engine's (model(..., sparse_grad=True)) or nn.Embedding(sparse=True)'s under torch autograd;
+    a gradient for which is_coalesced() holds skips the sort.  maximize is not implemented and
+    raises; dense gradients raise as torch's do.
+
+    capturable=True keeps the step count on the device, so a whole step can be captured with
+    torch.cuda.graph and replayed.  The parameters of a group that are at the same count share
+    one float32 counter (one rk_sparse_adam_step call per counter): new parameters and counts
+    loaded from a state dict join the group's counter at their count, and a parameter without a
+    gradient in a step leaves the shared counter, as torch counts a parameter's steps only when it
+    has a gradient (it is then stepped by a call of its own).  state_dict() hands out torch's int
+    per parameter and leaves the live counters alone.  Take one eager step before capturing: it
+    creates the state and the workspace."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, maximize=False, *, capturable=False):
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 < lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if maximize:
+            raise NotImplementedError("rankops.SparseAdam: maximize is not implemented")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, maximize=maximize, capturable=bool(capturable)))
+        bad = [[gi, pi] for gi, group in enumerate(self.param_groups) for pi, p in enumerate(group["params"])
+               if p.is_sparse or p.is_complex()]
+        if bad:
+            raise ValueError(f"Sparse or complex params at indices {bad}: SparseAdam requires dense real "
+                             "parameter tensors")
+        self._workspace = {}  # device -> uint8 tensor, allocated on first use and reused
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("_workspace", {})
+        for group in self.param_groups:
+            group.setdefault("capturable", False)
+
+    @staticmethod
+    def _count(step) -> int:
+        return int(step.item()) if isinstance(step, torch.Tensor) else int(step)
+
+    @staticmethod
+    def _is_counter(step, p) -> bool:
+        return isinstance(step, torch.Tensor) and step.device == p.device and step.dtype == torch.float32
+
+    def _group_counters(self, group):
+        """(device, count) -> the device counter the group's parameters already hold at that count
+        (reads the counters: only when a parameter has to be given one)."""
+        found = {}
+        for p in group["params"]:
+            st = self.state.get(p)
+            if st and self._is_counter(st.get("step"), p):
+                found.setdefault((p.device, self._count(st["step"])), st["step"])
+        return found
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            capturable = group.get("capturable", False)
+            calls = {}      # step count, or id of the device counter -> [counter, entries]
+            counters = None  # (device, count) -> device counter, filled when a parameter needs one
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not g.is_sparse:
+                    raise RuntimeError("SparseAdam does not support dense gradients, please consider Adam instead")
+                if p.device.type != "cuda" or p.dtype != torch.float32 or p.dim() != 2 or not p.is_contiguous():
+                    raise RuntimeError("rankops.SparseAdam: parameters must be contiguous 2-D float32 ROCm tensors")
+                if g.sparse_dim() != 1 or g.dense_dim() != 1 or g.shape != p.shape or g.device != p.device:
+                    raise RuntimeError("rankops.SparseAdam: a gradient must be a sparse COO tensor of its "
+                                       "parameter's shape with one sparse dimension (rows)")
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = 0
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                idx, val = g._indices()[0], g._values()
+                if val.dtype != torch.float32:
+                    val = val.to(torch.float32)
+                if val.dim() == 2 and val.shape[1] > 1 and val.stride(1) != 1:
+                    val = val.contiguous()
+                entry = (p, state["exp_avg"], state["exp_avg_sq"], idx, val, g.is_coalesced())
+                if capturable:
+                    st = state["step"]
+                    if not self._is_counter(st, p):
+                        # a new parameter, or a loaded int: join the group's counter at that count
+                        if counters is None:
+                            counters = self._group_counters(group)
+                        key = (p.device, self._count(st))
+                        st = counters.get(key)
+                        if st is None:
+                            st = counters[key] = torch.full((), float(key[1]), dtype=torch.float32, device=p.device)
+                        state["step"] = st
+                    calls.setdefault(id(st), [st, []])[1].append(entry)
+                else:
+                    n = state["step"] = self._count(state["step"]) + 1
+                    calls.setdefault(n, [None, []])[1].append(entry)
+            if capturable:
+                # torch counts a parameter's steps only when it has a gradient: one that misses this
+                # step leaves the shared counter and keeps its count in a counter of its own
+                left = {}
+                for p in group["params"]:
+                    st = self.state.get(p) if p.grad is None else None
+                    if st and id(st.get("step")) in calls:
+                        st["step"] = left.setdefault(id(st["step"]), st["step"].clone())
+            for key, (counter, entries) in calls.items():
+                dev = entries[0][0].device
+                self._workspace[dev] = ops.sparse_adam_step(
+                    entries, float(group["lr"]), beta1, beta2, group["eps"], 0 if counter is not None else key,
+                    ops._lib.raw_stream(dev), device_step=counter, workspace=self._workspace.get(dev))
+                # the kernel wrote through raw pointers: bump the version counters as torch's in-place
+                # ops would, so weight-derived caches (packed weight images) are rebuilt
+                torch.autograd.graph.increment_version([t for e in entries for t in e[:3]])
+        return loss
+
+    def load_state_dict(self, state_dict):
+        """Optimizer.load_state_dict; a dict written by torch.optim.SparseAdam has no `capturable`
+        entry, so every group keeps its own."""
+        keep = [group.get("capturable", False) for group in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, capturable in zip(self.param_groups, keep):
+            group["capturable"] = capturable
+
+    def state_dict(self):
+        """Optimizer.state_dict with torch.optim.SparseAdam's int step per parameter.  The returned
+        per-parameter dicts are copies: the optimizer's own state (the shared device counters a
+        captured step writes to) is left as it is."""
         sd = super().state_dict()
-        for st in sd["state"].values():
-            if "step" in st:
-                st["step"] = st["step"].clone()
+        sd["state"] = {k: ({**st, "step": self._count(st["step"])} if "step" in st else dict(st))
+                       for k, st in sd["state"].items()}
         return sd
 
 

@@ -56,6 +56,9 @@
  *   rk_embedding_backward_sorted  the same for long, skewed index lists (behaviour sequences)
  *                      as a sorted segment-reduce                din.py:300-303, bst.py:224
  *   rk_adam_step       torch.optim.Adam step (all tensors, one launch)  dcn.py:275
+ *   rk_sparse_adam_step  torch.optim.SparseAdam / LazyAdam step over sparse table gradients
+ *                      (all tables of a step in one call)         dien.py:328
+ *   rk_pack_blocks     the value rows of sparse table gradients out of dx, all tables in one launch
  *   rk_bn_act_train_forward / rk_bn_act_backward  Linear -> BatchNorm1d (train) -> ReLU -> Dropout
  *                      and its backward                       deepfm.py:100-109
  *   rk_fm_backward, rk_fm_combine_backward  FM and final_layer + sigmoid backward  deepfm.py:122-151
@@ -931,6 +934,62 @@ typedef struct rk_adam_tensor {
  * double and rounded to float once, as torch does.                                            */
 int rk_adam_step(const rk_adam_tensor* tensors, int32_t n, double lr, double beta1, double beta2,
                  double eps, double weight_decay, int64_t step, void* stream);
+
+typedef struct rk_sparse_adam_tensor {
+  float* param;       /* [rows, dim] table, row stride ld (floats) */
+  float* exp_avg;     /* same shape and stride */
+  float* exp_avg_sq;
+  int64_t rows;
+  int64_t ld;
+  const int64_t* idx; /* nnz row ids of the sparse gradient, element i at idx[i * idx_stride]; any
+                         order, duplicates allowed */
+  int64_t idx_stride;
+  int64_t nnz;
+  const float* values; /* [nnz, dim] gradient rows, row stride ld_values (floats) */
+  int64_t ld_values;
+  int32_t dim;         /* any dim >= 1 */
+  int32_t coalesced;   /* non-zero: idx is ascending without duplicates (a coalesced COO tensor);
+                          such tables skip the sort.  A list flagged wrongly gives wrong sums for
+                          its duplicated rows, never a fault */
+} rk_sparse_adam_tensor;
+
+/* One torch.optim.SparseAdam step (= TF LazyAdamOptimizer's arithmetic, DIEN/dien.py:328) for
+ * every table in the list: for each distinct row r of a table's gradient, g = the sum of the
+ * row's entries (in list order: no float atomics, equal inputs give equal bits), then
+ *   m += (1 - beta1) (g - m);  v += (1 - beta2) (g^2 - v);
+ *   p -= lr sqrt(1 - beta2^t) / (1 - beta1^t) * m / (sqrt(v) + eps)
+ * Rows that are not in the gradient are neither read nor written.  `step` is the 1-based count t
+ * after increment; when device_step is given (a float counter in device memory, torch's
+ * capturable layout) it is incremented on the device instead, t is read from it and `step` is
+ * ignored: the call is then graph-capturable.  Scalars are doubles, derived values are formed in
+ * double and rounded to float once, as in rk_adam_step.
+ * An id outside [0, rows) never faults: its entry contributes nothing and RK_FLAG_INDEX_OOB is
+ * raised (rk_error_flags).  A table of 2^32 rows or more, or of more than 2^32 - 513 entries, is
+ * RK_ERR_UNSUPPORTED.  Launches per call do not depend on the number of tables while they fit one
+ * group: up to 64 tables whose rows together fit 32-bit keys (the radix sort runs over the bits
+ * the group needs); more tables or rows make further groups.  Tables with nnz 0 are skipped.
+ * workspace: rk_sparse_adam_step_workspace_size bytes of device memory for the same list, owned
+ * by the caller and free for reuse once the call's work on `stream` has run.                    */
+int rk_sparse_adam_step_workspace_size(const rk_sparse_adam_tensor* tensors, int32_t n, int64_t* bytes);
+int rk_sparse_adam_step(const rk_sparse_adam_tensor* tensors, int32_t n, double lr, double beta1, double beta2,
+                        double eps, int64_t step, float* device_step, void* workspace, int64_t ws_bytes,
+                        void* stream);
+
+/* Packs column blocks of row-major matrices into contiguous buffers, all blocks in one launch
+ * (the value rows of sparse embedding gradients out of a backward's dx): for block k,
+ * dst[k][b * dim[k] + c] = src[k][b * ld_src[k] + c] (+ add[k][b * ld_add[k] + c] when add is
+ * given: a gradient kept as two summands) for b < rows[k], c < dim[k].                          */
+typedef struct rk_pack_block {
+  const float* src;
+  const float* add; /* optional second summand, NULL for a plain copy */
+  float* dst;
+  int64_t ld_src;
+  int64_t ld_add;
+  int64_t rows;
+  int32_t dim;
+  int32_t reserved;
+} rk_pack_block;
+int rk_pack_blocks(const rk_pack_block* blocks, int32_t n, void* stream);
 
 /* ---- evaluation metrics (the reference's evaluate(): dcn.py:214-239, same in every model) ---- */
 /* One batch into accum (3 x 8 bytes, zero it first): [0] double sum over batches of the batch's
