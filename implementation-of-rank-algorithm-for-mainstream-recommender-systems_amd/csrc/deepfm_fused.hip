@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kMlpThreads) void deepfm_fused_kernel(std::conditio
       }
     }
   };
-  mlp_stream_rows<P, RK_STREAM_EPI, RT, (RT > 1)>(a.L, buf0, a.ld0, buf1, a.ld1, nullptr, m0, rows, a.head, tid,
+  mlp_stream_rows<P, kEpiRegs, RT, (RT > 1)>(a.L, buf0, a.ld0, buf1, a.ld1, nullptr, m0, rows, a.head, tid,
                                     ring_early<RK_DEEPFM_RING_EARLY>(side_at<0>(staged(st_index, st_issue, st_store, st_fm))), nullptr, nullptr,
                                     fm_lds);
   MLP_MARK(4 * RK_MLP_MAX_LAYERS + 1, k_t0);

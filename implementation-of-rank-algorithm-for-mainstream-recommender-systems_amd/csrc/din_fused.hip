@@ -37,10 +37,6 @@ typedef __attribute__((address_space(1))) void glb_void;
 typedef __attribute__((address_space(1))) float glb_float;
 typedef __attribute__((address_space(1))) unsigned glb_uint;
 
-#ifndef RK_DIN_HOIST  // experiment (phase A's layer-1 operand per sample): see the tile loop
-#define RK_DIN_HOIST 0
-#endif
-
 constexpr int kDinSegs = 32;
 constexpr int kDinSegLdsOff = 528;  // bytes past the column map: 256 + 256 map bytes, l2_last int, pad to 16
 struct DinSegs {
@@ -166,11 +162,6 @@ template <int H>
 constexpr int din_pre_chunks() {
   return (16 + 34 + H) / 16 < 7 ? (16 + 34 + H) / 16 : 7;
 }
-// Phase B's last layer (128 wide: waves 8..15 own no tile of it) without its one lockstep barrier, as
-// it ran while the l2 hand-off sat beside it (round 7); measured both ways (mlp_stream.h kSync)
-#ifndef RK_DIN_FREE_LAST
-#define RK_DIN_FREE_LAST 1
-#endif
 // balanced launches gather each wave's row inside phase A: the waves count their rows in here
 static __shared__ unsigned s_din_rows_ready;
 // The l2 hand-off: the last workgroup to publish its partial finishes the mean.  By atomic
@@ -260,9 +251,11 @@ static __shared__ DinL2Args s_din_l2;
 // next launch's start after this kernel's end.
 template <class P, int H, bool WAIT, bool DMA>
 struct DinRowsReady {
-#if RK_DIN_FREE_LAST
+  // Phase B's last layer (128 wide: waves 8..15 own no tile of it) without its one lockstep barrier,
+  // as it ran while the l2 hand-off sat beside it (round 7).  Measured both ways in round 8: with the
+  // barrier restored the prepared launch takes 35.56 / 35.50 / 35.48 us against 35.55 / 35.55 /
+  // 35.47 us without it (profiles/r08/l2_cost_new_sync_*.log; mlp_stream.h kSync)
   static constexpr int kFreeLayer = P::NL - 1;
-#endif
   static constexpr int kSideSteps = 4, kSideWave = kMlpWaves - 1;
   static constexpr int kHeld = 4;  // partials per lane the reader holds between steps 2 and 3
   static constexpr int side_step_layer(int s) { return s == 0 ? 0 : 1; }
@@ -450,15 +443,11 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
   using Epi = std::conditional_t<std::is_void_v<P>, NoStage, StreamEpi<std::conditional_t<std::is_void_v<P>, StreamPlanK128, P>>>;
   Epi epi_img;
   const bool epi_dma = a.epi_image != nullptr;  // copied after phase A instead (see DinArgs)
-#ifndef RK_DIN_EXP_NOEPI  // timing experiment only: phase B without its epilogue parameters (wrong outputs)
   if constexpr (!std::is_void_v<P>)
     if (!epi_dma) epi_img.load(a.L, tid);
-#endif
   auto image_to_lds = [&]() {
-#ifndef RK_DIN_EXP_NOEPI
     if constexpr (!std::is_void_v<P>)
       if (!epi_dma) epi_img.store(sm + a.epi_off, tid);
-#endif
     if (a.att_image) {
 #pragma unroll
       for (int r = 0; r < kPer; ++r) {
@@ -674,9 +663,6 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
         krow = a.key_table + r * a.ld_key + HG * g;
       else
         flag_oob(flags);
-#ifdef RK_DIN_NO_GATHER  // timing experiment only: the keys come from 16 cache-resident rows
-      krow = a.key_table + (int64_t)p16 * a.ld_key + HG * g;
-#endif
     }
     if constexpr (HG >= 4) {
 #pragma unroll
@@ -738,22 +724,13 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
     float o[HG];
 #pragma unroll
     for (int e = 0; e < HG; ++e) o[e] = 0.f;
-    // RK_DIN_HOIST (experiment, off): layer 1's A operand Weff built once per sample in 32 VGPRs
-    // instead of per tile from LDS (118 VGPRs, no spill; half the tile's LDS reads and 32 fewer FMAs
-    // per tile) measured flat (42.0 / 42.7 us against 41.8 / 42.7 us per launch,
-    // profiles/r04/ab_hoist*.json): phase A is not bound by the operand's LDS reads
-#if RK_DIN_HOIST
-    float weff[4][HG];
-#pragma unroll
-    for (int jt = 0; jt < 4; ++jt) {
-      const float* wk = sm + Ly::WK + (16 * jt + p16) * Ly::LDH + HG * g;
-      const float* wqk = sm + Ly::WQK + (16 * jt + p16) * Ly::LDH + HG * g;
-#pragma unroll
-      for (int e = 0; e < HG; ++e) weff[jt][e] = fmaf(wqk[e], qv[e], wk[e]);
-    }
-#endif
+    // Layer 1's A operand Weff is built per tile from LDS.  Built once per sample in 32 VGPRs instead
+    // (118 VGPRs, no spill; half the tile's LDS reads and 32 fewer FMAs per tile) it measured flat
+    // (42.0 / 42.7 us against 41.8 / 42.7 us per launch, profiles/r04/ab_hoist*.json): phase A is not
+    // bound by the operand's LDS reads
     for (int tt = 0; tt < ntiles; ++tt) {
-      // the weight LDS reads below are loop-invariant (kept in the loop: see RK_DIN_HOIST above)
+      // the weight LDS reads below are loop-invariant; this keeps them in the loop (the per-sample
+      // operand measured flat, see above)
       asm volatile("" ::: "memory");
       const int t = 16 * tt + p16;
       const bool in_seq = t < a.T;
@@ -765,13 +742,6 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt) acc1[jt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
       // layer 1's A operand, Weff[16 jt + p16][HG g + e] = Wk + Wqk q (rows of the LDS image)
-#if RK_DIN_HOIST
-#pragma unroll
-      for (int e = 0; e < HG; ++e) {
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) acc1[jt] = mfma16(weff[jt][e], kk[e], acc1[jt]);
-      }
-#else
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt) {
         const float* wk = sm + Ly::WK + (16 * jt + p16) * Ly::LDH + HG * g;
@@ -779,7 +749,6 @@ __global__ __launch_bounds__(kMlpThreads) void din_forward_kernel(DinArgs a) {
 #pragma unroll
         for (int e = 0; e < HG; ++e) acc1[jt] = mfma16(fmaf(wqk[e], qv[e], wk[e]), kk[e], acc1[jt]);
       }
-#endif
       // ReLU(layer 1 + u) in place, then layer 2 with the accumulators as its B operands
       f32x4_t acc2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll

@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_stream_kernel(MlpArgs a) {
   const unsigned long long k_t0 = clock64();
   MLP_WALL(4 * RK_MLP_MAX_LAYERS + 2);
 #endif
-  mlp_stream_rows<P, RK_STREAM_EPI, RT>(a.L, buf0, a.ld0, buf1, a.ld1, sm + a.off_epi, m0, rows, a.head, tid,
+  mlp_stream_rows<P, kEpiRegs, RT>(a.L, buf0, a.ld0, buf1, a.ld1, sm + a.off_epi, m0, rows, a.head, tid,
                                         finish_only(stage));
   MLP_MARK(4 * RK_MLP_MAX_LAYERS + 1, k_t0);
   MLP_WALL(4 * RK_MLP_MAX_LAYERS + 3);
@@ -573,7 +573,7 @@ __global__ __launch_bounds__(kMlpThreads) void dcn_fused_kernel(DcnArgs a) {
                  }),
              part);
   else
-    mlp_stream_rows<P, RK_STREAM_EPI, RT>(a.m.L, buf0, a.m.ld0, buf1, a.m.ld1, sm + a.m.off_epi, m0, rows, a.m.head,
+    mlp_stream_rows<P, kEpiRegs, RT>(a.m.L, buf0, a.m.ld0, buf1, a.m.ld1, sm + a.m.off_epi, m0, rows, a.m.head,
                                           tid, side_at<2>(staged(stage_index, stage_issue, stage_store, side_cross)),
                                           part);
   MLP_MARK(4 * RK_MLP_MAX_LAYERS + 1, k_t0);  // whole workgroup (incl. stage and head)

@@ -12,6 +12,12 @@
 // epilogue parameters sit in registers: read after the LDS stores they were re-fetched per
 // element behind the whole weight-load queue (tools/mlp_phases.hip: DeepFM layer-0 epilogue
 // 38k -> 8k cycles; DIN 48.8 -> 51.4 M samples/s).
+//
+// Tried here, measured and removed again (numbers in profiles/r03/NOTES.md; the code is in the
+// history): the next layer's weight ring issued right after a wave's last MFMA, ahead of its
+// epilogue (no gain: DIN kernel 51.1 -> 51.9-53.0 us); one prepare() code path for both layer shapes
+// (DCN 130.2 -> 128.4 M); epilogue parameters fetched by lanes 0..15 only and broadcast in the
+// epilogue (DCN 130.4 -> 127.8 M, DIN / DeepFM -1 %).
 #pragma once
 
 #include <type_traits>
@@ -20,39 +26,16 @@
 
 namespace rk {
 
-#ifndef RK_MLP_EPI_PRIO
-#define RK_MLP_EPI_PRIO 1
-#endif
-// Lockstep within a layer: every kMlpSyncChunks K-chunks all waves meet at a barrier.  Without it
-// the SIMD's matrix pipe serves its 4 waves oldest-first: in DCN's 512 -> 256 layer wave w
-// finished its MFMAs at 10.2k / 13.5k / 17.6k / 21.5k cycles for w = 0..3 / 4..7 / 8..11 /
-// 12..15 (tools/dcn_phases.py), and the last wave of each SIMD, running alone, could not cover
-// the L2 latency of its weight ring with its own 8 chunks of MFMAs.
-#ifndef RK_MLP_SYNC
-#define RK_MLP_SYNC 1
-#endif
-// RK_MLP_EARLY_RING=1: the next layer's weight ring goes out right after a wave's last MFMA of the
-// current layer, ahead of its epilogue (the epilogue parameters after it).  Measured no gain (DIN
-// kernel 51.1 -> 51.9-53.0 us, DCN / DeepFM within noise: profiles/r03/NOTES.md), so off.
-#ifndef RK_MLP_EARLY_RING
-#define RK_MLP_EARLY_RING 0
-#endif
-// RK_MLP_UNIFORM_PREP=1: one prepare() code path for both layer shapes (LayerPipe::prepare_any).
-// Measured DCN 130.2 -> 128.4 M, DIN / DeepFM within noise (profiles/r03/NOTES.md), so off.
-// RK_MLP_EP_LANES16=1: epilogue parameters fetched by lanes 0..15 only and broadcast in the
-// epilogue (ep_bcast).  Measured DCN 130.4 -> 127.8 M, DIN / DeepFM -1 % (profiles/r03/NOTES.md): off.
-#ifndef RK_MLP_EP_LANES16
-#define RK_MLP_EP_LANES16 0
-#endif
-#ifndef RK_MLP_UNIFORM_PREP
-#define RK_MLP_UNIFORM_PREP 0
-#endif
-
 constexpr int kMlpRows = 16;
 constexpr int kMlpWaves = 16;
 constexpr int kMlpThreads = 64 * kMlpWaves;
 constexpr int kMlpPD = 4;    // prefetch depth (chunks)
-constexpr int kMlpSyncChunks = 8;  // RK_MLP_SYNC barrier interval (K-chunks of 16)
+// Lockstep within a layer: every kMlpSyncChunks K-chunks (of 16) all waves meet at a barrier.
+// Without it the SIMD's matrix pipe serves its 4 waves oldest-first: in DCN's 512 -> 256 layer wave w
+// finished its MFMAs at 10.2k / 13.5k / 17.6k / 21.5k cycles for w = 0..3 / 4..7 / 8..11 /
+// 12..15 (tools/dcn_phases.py), and the last wave of each SIMD, running alone, could not cover
+// the L2 latency of its weight ring with its own 8 chunks of MFMAs.
+constexpr int kMlpSyncChunks = 8;
 
 // A bare s_barrier: no wait on this wave's memory counters (the weight ring stays in flight).
 __device__ __forceinline__ void mlp_sync_barrier() { asm volatile("s_barrier"); }
@@ -194,14 +177,6 @@ struct LayerPipe {
   ColEpi ep[2];
   template <int TPW, int PD>
   __device__ __forceinline__ void prepare(const rk_mlp_layer& L, int kchunks, int wave, int lane) {
-    prepare_ring<TPW, PD>(L, kchunks, wave, lane);
-    prepare_ep<TPW>(L, wave, lane);
-  }
-  // The two halves of prepare(): the weight ring may go out as soon as the previous layer's last
-  // MFMA is issued (its last ring cycle issues no refill, so the registers and wrow are free); the
-  // epilogue parameters only after that layer's epilogue has consumed ep.
-  template <int TPW, int PD>
-  __device__ __forceinline__ void prepare_ring(const rk_mlp_layer& L, int kchunks, int wave, int lane) {
     static_assert(TPW * PD <= kMlpRing, "ring overflow");
 #pragma unroll
     for (int j = 0; j < TPW; ++j) wrow[j] = wfrag(L, wave + kMlpWaves * j, lane);
@@ -217,73 +192,21 @@ struct LayerPipe {
         ring[s * TPW + j] = *reinterpret_cast<const f32x4_t*>(wrow[j] + kFragStep * min(s, kchunks - 1));
         __builtin_amdgcn_sched_barrier(0);
       }
-  }
-  // Both layer shapes in one code path (`two`: the wave owns two column tiles): slot k holds chunk
-  // k >> 1 of tile k & 1 (two tiles) or chunk k (one tile), the order the two mlp_layer variants
-  // consume.  With a prepare per variant the ring values met at a join after it, and the compiler
-  // copied them into one register set there — copies that wait for each load to land, i.e. a full
-  // vmcnt(0) drain of the ring right after issuing it, before the layer barrier.
-  __device__ __forceinline__ void prepare_any(const rk_mlp_layer& L, int kchunks, bool two, int wave, int lane) {
-    wrow[0] = wfrag(L, wave, lane);
-    wrow[1] = wfrag(L, wave + kMlpWaves, lane);  // dereferenced only when two
-#pragma unroll
-    for (int k = 0; k < kMlpRing; ++k) {
-      const float* p = two ? wrow[k & 1] + kFragStep * min(k >> 1, kchunks - 1) : wrow[0] + kFragStep * min(k, kchunks - 1);
-      ring[k] = *reinterpret_cast<const f32x4_t*>(p);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     const int li = lane & 15;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < TPW; ++j) {
       const int n = 16 * (wave + kMlpWaves * j) + li;
       ep[j] = col_epi(L, n < L.n ? n : 0);
     }
   }
-  template <int TPW>
-  __device__ __forceinline__ void prepare_ep(const rk_mlp_layer& L, int wave, int lane) {
-    const int li = lane & 15;
-#if RK_MLP_EP_LANES16
-    // the 4 lane groups of a column tile need the same 16 columns: only lanes 0..15 fetch them
-    // (a quarter of the address/data work in the shared TA path, which every wave's prepare
-    // otherwise saturates at the layer boundary), the epilogue broadcasts them (ep_bcast)
-    if (lane < 16)
-#endif
-#pragma unroll
-      for (int j = 0; j < TPW; ++j) {
-        const int n = 16 * (wave + kMlpWaves * j) + li;
-        ep[j] = col_epi(L, n < L.n ? n : 0);
-      }
-  }
 };
-
-// Lanes 0..15's epilogue parameters to every lane of the column tile (ds_bpermute; in the
-// epilogue, where waiting for the loads is free).
-__device__ __forceinline__ ColEpi ep_bcast(const ColEpi& e, int lane) {
-#if RK_MLP_EP_LANES16
-  const int src = lane & 15;
-  ColEpi o;
-  o.bias = __shfl(e.bias, src, 64);
-  o.pre_s = __shfl(e.pre_s, src, 64);
-  o.pre_b = __shfl(e.pre_b, src, 64);
-  o.act_s = __shfl(e.act_s, src, 64);
-  o.act_b = __shfl(e.act_b, src, 64);
-  o.alpha = __shfl(e.alpha, src, 64);
-  o.post_s = __shfl(e.post_s, src, 64);
-  o.post_b = __shfl(e.post_b, src, 64);
-  return o;
-#else
-  (void)lane;
-  return e;
-#endif
-}
 
 // One layer (weights already in flight in P) over RT row tiles of 16 rows: each weight float4
 // feeds RT x 4 MFMAs.  kchunks = Kp / 16 (a multiple of 4).
-// `next` runs right after the last MFMA is issued (mlp_rows: the next layer's weight ring).
-template <int TPW, int RT, int PD, bool STORE, class Next>
+template <int TPW, int RT, int PD, bool STORE>
 __device__ __forceinline__ void mlp_layer(LayerPipe& P, const rk_mlp_layer& L, const float* __restrict__ in,
                                           int ldin, float* __restrict__ out, int ldout, int Kp, int wave, int lane,
-                                          int64_t m0, int rows, Next next, int dbg_mark = 0,
+                                          int64_t m0, int rows, int dbg_mark = 0,
                                           unsigned long long dbg_t0 = 0) {
   const int li = lane & 15, kq = 4 * (lane >> 4);
   const int kchunks = Kp / 16;
@@ -337,9 +260,7 @@ __device__ __forceinline__ void mlp_layer(LayerPipe& P, const rk_mlp_layer& L, c
   int c0 = 0;
   for (; c0 + PD < kchunks; c0 += PD) {
     cycle(c0, PD, std::true_type{});
-#if RK_MLP_SYNC
-    if ((c0 + PD) % kMlpSyncChunks == 0) mlp_sync_barrier();
-#endif
+    if ((c0 + PD) % kMlpSyncChunks == 0) mlp_sync_barrier();  // lockstep (kMlpSyncChunks)
   }
   if (kchunks - c0 == PD) {
     cycle(c0, PD, std::false_type{});
@@ -350,18 +271,15 @@ __device__ __forceinline__ void mlp_layer(LayerPipe& P, const rk_mlp_layer& L, c
     // prepare() to wait behind)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only (lgkmcnt / expcnt at their maximum)
   }
-  next();
 
 #ifdef RK_MLP_PHASES
   if (wave == 0 && lane == 0) s_mlp_marks[dbg_mark] = clock64() - dbg_t0;
   if (lane == 0 && dbg_mark / 4 < 4) s_mlp_wave_marks[dbg_mark / 4][wave][0] = (unsigned)(clock64() - dbg_t0);
 #endif
-#if RK_MLP_EPI_PRIO
   // this wave's MFMAs are all issued: its epilogue and the next layer's prepare are on the
   // layer boundary's critical path, so let them win issue arbitration against the waves of the
   // SIMD still in their MFMA loops (reset to 0 after the barrier)
   __builtin_amdgcn_s_setprio(2);
-#endif
   float* const store = STORE ? L.store : nullptr;  // eval kernels compile the store path out
   const int64_t ld_store = L.ld_store;
   // The two wave-uniform switches (Dice, residual) are taken once for the whole epilogue: inside
@@ -373,7 +291,7 @@ __device__ __forceinline__ void mlp_layer(LayerPipe& P, const rk_mlp_layer& L, c
     for (int j = 0; j < TPW; ++j) {
       const int n = 16 * (wave + kMlpWaves * j) + li;
       const bool real = n < L.n;
-      const ColEpi ep = ep_bcast(P.ep[j], lane);
+      const ColEpi ep = P.ep[j];  // (a copy: through a reference hipcc allocates mlp_kernel's registers differently)
       // x + f(x): the previous layer's input still sits in `out` (read all, then write: same lane)
       float res[RT][4];
 #pragma unroll
@@ -568,32 +486,11 @@ __device__ __forceinline__ void mlp_rows(const rk_mlp_layer* __restrict__ layers
   auto prepare = [&](int l) {
     const int nt = pad64(layers[l].n) / 16;  // multiple of 4
     const int kch = pad64(l ? layers[l - 1].n : K0) / 16;
-#if RK_MLP_UNIFORM_PREP
-    if (wave < nt) pipe.prepare_any(layers[l], kch, wave + kMlpWaves < nt, wave, lane);
-#else
     if (wave + kMlpWaves < nt)
       pipe.prepare<2, 4>(layers[l], kch, wave, lane);
     else if (wave < nt)
       pipe.prepare<1, 8>(layers[l], kch, wave, lane);
-#endif
   };
-#if RK_MLP_EARLY_RING
-  auto prepare_ring = [&](int l) {
-    const int nt = pad64(layers[l].n) / 16;
-    const int kch = pad64(layers[l - 1].n) / 16;
-    if (wave + kMlpWaves < nt)
-      pipe.prepare_ring<2, 4>(layers[l], kch, wave, lane);
-    else if (wave < nt)
-      pipe.prepare_ring<1, 8>(layers[l], kch, wave, lane);
-  };
-  auto prepare_ep = [&](int l) {
-    const int nt = pad64(layers[l].n) / 16;
-    if (wave + kMlpWaves < nt)
-      pipe.prepare_ep<2>(layers[l], wave, lane);
-    else if (wave < nt)
-      pipe.prepare_ep<1>(layers[l], wave, lane);
-  };
-#endif
   // The head's operands (head_w for this lane's columns, this wave's row scalars) are loaded while
   // the last layer runs: fetched after the final barrier they put two dependent L2 round trips
   // (~10k cycles at 256 busy CUs, tools/mlp_phases.hip) between the last MFMA and the logits.
@@ -632,36 +529,20 @@ __device__ __forceinline__ void mlp_rows(const rk_mlp_layer* __restrict__ layers
     const float* in = (l & 1) ? buf1 : buf0;
     float* out = (l & 1) ? buf0 : buf1;
     const int ldin = (l & 1) ? ld1 : ld0, ldout = (l & 1) ? ld0 : ld1;
-#if RK_MLP_EARLY_RING
-    auto next = [&] {
-      if (l + 1 < nl) prepare_ring(l + 1);
-    };
-#else
-    auto next = [] {};
-#endif
     if (wave + kMlpWaves < ntiles) {
-      mlp_layer<2, RT, 4, STORE>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, m0, rows, next, 4 * l, t0);
+      mlp_layer<2, RT, 4, STORE>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, m0, rows, 4 * l, t0);
     } else if (wave < ntiles) {
-      mlp_layer<1, RT, 8, STORE>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, m0, rows, next, 4 * l, t0);
+      mlp_layer<1, RT, 8, STORE>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, m0, rows, 4 * l, t0);
     } else {
-#if RK_MLP_SYNC
       // no tile in this layer: take part in the active waves' lockstep barriers
       for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
-#endif
-      next();
     }
     MLP_MARK(4 * l + 1, t0);
-#if RK_MLP_EARLY_RING
-    if (l + 1 < nl) prepare_ep(l + 1);
-#else
     if (l + 1 < nl) prepare(l + 1);
-#endif
     if (l + 2 == nl) head_prefetch();
     MLP_MARK(4 * l + 2, t0);
     mlp_lds_barrier();
-#if RK_MLP_EPI_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     MLP_MARK(4 * l + 3, t0);
     Kp = pad64(L.n);
   }

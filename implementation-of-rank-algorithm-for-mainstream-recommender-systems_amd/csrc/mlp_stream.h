@@ -43,38 +43,20 @@ namespace rk {
 #ifndef RK_STREAM_RING
 #define RK_STREAM_RING 8
 #endif
-// epilogue parameters of the rk_mlp_forward / DCN streamed tails (StreamEpiMode below)
-#ifndef RK_STREAM_EPI
-#define RK_STREAM_EPI 2
-#endif
-// experiment: single-tile layers accumulate odd K-steps into a second register set (two
-// independent MFMA chains per wave), summed before the epilogue — not bit-identical to mlp_rows.
-// A compute-and-stream probe gains 12 % from two chains (tools/stream_probe.hip,
-// profiles/r04/stream_probe3.log), but this form makes hipcc spill ~400 VGPRs (DCN 3x slower,
-// profiles/r04/ab_split_*.json), and alternating the chains per K-chunk instead is within noise
-// (ab_split2_*.json).  Off.
-#ifndef RK_STREAM_SPLITACC
-#define RK_STREAM_SPLITACC 0
-#endif
-// Layer hand-off by per-tile ready flags instead of a workgroup barrier: after its epilogue a wave
-// sets the bits of its output tiles in an LDS word (rk_stream_ready[l]); a wave of layer l+1 waits
-// for bit c only before it reads K-chunk c (= layer l's tile c).  The matrix pipe serves a SIMD's
-// waves oldest-first, so waves 0-3 finish a layer first and, with a barrier, idled through the
-// younger waves' last MFMAs and epilogues (DCN 512->256 boundary: waves 0-3 done at 4.9k, barrier
-// at 7.4k cycles, tools/dcn_phases.py); with the flags they start the next layer's chunks in the
-// order the older waves produce them.  The accumulation order is unchanged (bit-identical to
-// mlp_rows).  The barrier before the head stays.  Measured no gain (DIN 88.1 / 88.0 M against
-// 89.3 / 89.9 M with the barrier, DCN and DeepFM within noise: profiles/r04/ab_flags_*.json): the
-// lockstep barriers 8 chunks into the next layer pull the early waves back, so off.
-#ifndef RK_STREAM_FLAGS
-#define RK_STREAM_FLAGS 0
-#endif
-// Weight-stream loads with the nontemporal hint (experiment): every weight element is read once
-// per CU, so its L1 line is never reused; the memory-pipe counters show the CU's TCP stalled on
-// pending requests 32-43 % of the kernel (profiles/r04/ta).
-#ifndef RK_STREAM_NT
-#define RK_STREAM_NT 0
-#endif
+// Tried here, measured and removed again (the code is in the history):
+//  * single-tile layers accumulating odd K-steps into a second register set (two independent MFMA
+//    chains per wave, not bit-identical to mlp_rows): a compute-and-stream probe gains 12 % from two
+//    chains (tools/stream_probe.hip, profiles/r04/stream_probe3.log), but hipcc spilled ~400 VGPRs
+//    (DCN 3x slower, profiles/r04/ab_split_*.json); alternating the chains per K-chunk was within
+//    noise (ab_split2_*.json);
+//  * the layer hand-off by per-tile ready flags in LDS instead of the workgroup barrier, so that a
+//    SIMD's oldest waves start the next layer's chunks as they are produced: no gain (DIN 88.1 /
+//    88.0 M against 89.3 / 89.9 M with the barrier, DCN and DeepFM within noise:
+//    profiles/r04/ab_flags_*.json), the lockstep barriers 8 chunks into the next layer pull the
+//    early waves back;
+//  * weight-stream loads with the nontemporal hint (every weight element is read once per CU; the
+//    memory-pipe counters show the CU's TCP stalled on pending requests 32-43 % of the kernel:
+//    profiles/r04/ta): flat.
 // Ring refills in groups: a layer's chunks refill their slots RK_STREAM_REFILL_GROUP loads at a time
 // (the loads of max(1, GROUP / T) consecutive chunks back to back after the last of them's MFMAs)
 // instead of T loads after every chunk: the same loads, issued in bursts.  The layout probe
@@ -89,12 +71,10 @@ namespace rk {
 #ifndef RK_STREAM_RING_EARLY
 #define RK_STREAM_RING_EARLY 2
 #endif
-// LDS that the streamed tail adds to its kernel beyond the caller's carve (the ready words); host
-// LDS budgets leave room for it
+// Bytes of LDS that host LDS budgets leave free beyond the caller's carve, for static __shared__
+// data of a kernel around the streamed tail (DIN's row counter and hand-off arguments; the tail has
+// none of its own).  Plan selection at the LDS limit depends on the value.
 constexpr int kStreamStaticLds = 64;
-#if RK_STREAM_FLAGS
-static __shared__ unsigned rk_stream_ready[RK_MLP_MAX_LAYERS];
-#endif
 
 // Timing build of the DIN forward (RK_DIN_PHASES, tools/din_phases.py): wall-clock marks of the
 // last wave (lane 0), kept in LDS and flushed by the kernel: [0] layer 0 opened (the barrier that
@@ -194,7 +174,6 @@ __device__ __forceinline__ float apply_epi(const ColEpi& e, float z) {
 
 // Where a streamed tail finds its per-column epilogue parameters.
 enum StreamEpiMode {
-  kEpiLdsHere = 0,    // LDS image, loaded and stored by mlp_stream_rows in its prologue
   kEpiLdsCaller = 1,  // LDS image stored by the caller before the barrier that opens layer 0 (DIN)
   kEpiRegs = 2,       // registers: layer 0's after the ring in the prologue, layer l+1's after layer l's epilogue
 };
@@ -273,8 +252,9 @@ constexpr bool side_steps_placed() {
 }
 
 // One wave class W (P::rep(W) == W) of the streamed tail.  `epi` is the LDS parameter image
-// (stored before the barrier that opens layer 0); `stage` as in mlp_rows (issue() before the ring,
-// operator() after it, before that barrier).  EPI: StreamEpiMode.
+// (kEpiLdsCaller: stored by the caller before the barrier that opens layer 0; not read with
+// kEpiRegs); `stage` as in mlp_rows (issue() before the ring, operator() after it, before that
+// barrier).  EPI: StreamEpiMode.
 template <class P, int W, int EPI, int RT, bool IP0, class Stage>
 __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict__ layers, float* buf0, int ld0,
                                                  float* buf1, int ld1, float* epi, int64_t m0, int rows,
@@ -296,11 +276,7 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
       constexpr int i = g - P::base(l, W), c = i / T, j = i % T;
       const rk_mlp_layer& L = layers[l];
       const float* p = L.w + ((int64_t)(wave + kMlpWaves * j) * (L.ldw / 16) + c) * kFragStep;
-#if RK_STREAM_NT
-      ring[g % R] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p + 4 * lane));
-#else
       ring[g % R] = *reinterpret_cast<const f32x4_t*>(p + 4 * lane);
-#endif
     }
   };
 
@@ -319,7 +295,6 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
 #ifdef RK_MLP_PHASES
   const unsigned long long t_start = clock64();
 #endif
-  StreamEpi<P> ep_stage;
   constexpr bool kEarly = stage_has_early<Stage>::value;
   // the layer whose MFMAs the stage's side work runs beside: the stage's choice, else the second
   // (a stage with side steps has no side(): no layer, and none of the staggered call sites)
@@ -343,8 +318,7 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
     __builtin_amdgcn_sched_barrier(0);
   } else {
     stage.issue();
-    if constexpr (EPI == kEpiLdsHere) ep_stage.load(layers, tid);
-    __builtin_amdgcn_sched_barrier(0);  // the stage's and the parameters' loads stay ahead of the ring
+    __builtin_amdgcn_sched_barrier(0);  // the stage's loads stay ahead of the ring
   }
   // kEarly stages: only the first R0 ring loads go out before the stage's dependent loads (DCN /
   // DeepFM: the row gather), so those queue behind R0 KiB per wave in the CU's memory pipe instead
@@ -357,7 +331,6 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
   });
   if constexpr (kEarly) {
     stage.issue();
-    if constexpr (EPI == kEpiLdsHere) ep_stage.load(layers, tid);
     __builtin_amdgcn_sched_barrier(0);
     static_for<R0, R>([&](auto G) {
       issue(G);
@@ -373,8 +346,7 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
   // already), accumulated in order into the accumulators layer 0 continues from — bit-identical
   constexpr int KS = stage_pre_chunks<Stage>::value;
   constexpr int T0 = P::tpw(0, W);
-  static_assert(KS == 0 || (KS < kMlpSyncChunks && KS < P::kc(0) && kSideL != 0 && !(RK_STREAM_SPLITACC && T0 == 1) &&
-                            RT == 1 && !IP0),
+  static_assert(KS == 0 || (KS < kMlpSyncChunks && KS < P::kc(0) && kSideL != 0 && RT == 1 && !IP0),
                 "pre-barrier chunks: no lockstep barrier or side work among them");
   static_assert(RT == 1 || RT == 2, "one or two 16-row tiles");
   f32x4_t acc0[T0 > 0 ? T0 : 1];
@@ -402,10 +374,6 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
       __builtin_amdgcn_sched_barrier(0);
     });
   }
-  if constexpr (EPI == kEpiLdsHere) ep_stage.store(epi, tid);
-#if RK_STREAM_FLAGS
-  if (tid < NL) rk_stream_ready[tid] = 0u;  // read only after the barrier below
-#endif
   mlp_lds_barrier();
   MLP_MARK(4 * RK_MLP_MAX_LAYERS, t_start);  // prologue done
   STREAM_LAST_TS(0);
@@ -443,9 +411,8 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
     const rk_mlp_layer& L = layers[l];
     // lockstep barriers, except in a layer the stage chose for side work that leaves waves without
     // a tile: those waves do the side work instead, and a barrier would make the others wait for it;
-    // and except in a layer the stage wants free of them (DIN's 128-wide last layer, as it ran in
-    // round 7: with its one barrier restored the prepared launch measures the same, 35.56 / 35.50 /
-    // 35.48 us against 35.55 / 35.55 / 35.47: profiles/r08/l2_cost_new_sync_*.log)
+    // and except in a layer the stage wants free of them (DIN's 128-wide last layer: the numbers are
+    // at din_fused.hip's kFreeLayer)
     constexpr bool kSync = !(stage_side_layer<Stage>::value == l && P::nt(l) < kMlpWaves) &&
                            stage_free_layer<Stage>::value != l;
     // IP0: layer 0 in place in buf0, then the ping-pong one step behind
@@ -456,11 +423,9 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
     const int ldin = kIn1 ? ld1 : ld0, ldout = kOut1 ? ld1 : ld0;
     if constexpr (T == 0) {
       if constexpr (l == kSideL) stage.side();  // (no tile here: the side work all the same)
-#if RK_MLP_SYNC
       // no tile in this layer: take part in the active waves' lockstep barriers
       if constexpr (kSync)
         static_for<0, (KC - 1) / kMlpSyncChunks>([&](auto) { mlp_sync_barrier(); });
-#endif
       if constexpr (IP0 && l == 0) mlp_lds_barrier();
     } else {
       constexpr int CB = l == 0 ? KS : 0;  // first chunk of this section (layer 0: after the pre-chunks)
@@ -475,34 +440,14 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
             acc[j][t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         }
       }
-      constexpr bool kSplit = RK_STREAM_SPLITACC && T == 1 && RT == 1;
-      f32x4_t acc_odd = {0.f, 0.f, 0.f, 0.f};
       const float* arow = in + li * ldin + kq;
-      // layer l > 0, flag hand-off: K-chunk c is layer l-1's output tile c; `ready` caches the bits
-      // seen set (wave-uniform), the LDS word is re-read only for a chunk not seen yet
-      unsigned ready = 0u;
-      auto wait_chunk = [&](int c) {
-#if RK_STREAM_FLAGS
-        if constexpr (l > 0) {
-          if (!((ready >> c) & 1u)) {
-            do {
-              ready = __builtin_amdgcn_readfirstlane(
-                  __hip_atomic_load(&rk_stream_ready[l - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-            } while (!((ready >> c) & 1u));
-            asm volatile("" ::: "memory");  // the chunk's activation reads stay behind the flag
-          }
-        }
-#endif
-      };
       // A float4s one chunk ahead in two register sets (see mlp_layer)
       f32x4_t ab[2][RT];
-      wait_chunk(CB);
 #pragma unroll
       for (int t = 0; t < RT; ++t) ab[CB & 1][t] = *reinterpret_cast<const f32x4_t*>(arow + 16 * t * ldin + 16 * CB);
       static_for<CB, KC>([&](auto CI) {
         constexpr int c = CI;
         if constexpr (c + 1 < KC) {
-          wait_chunk(c + 1);
 #pragma unroll
           for (int t = 0; t < RT; ++t)
             ab[(c + 1) & 1][t] = *reinterpret_cast<const f32x4_t*>(arow + 16 * t * ldin + 16 * (c + 1));
@@ -514,10 +459,7 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
             constexpr int j = JI;
             static_for<0, RT>([&](auto TI) {
               constexpr int t = TI;
-              if constexpr (kSplit && (e & 1))
-                acc_odd = mfma16(ab[c & 1][t][e], ring[(B0 + c * T + j) % R][e], acc_odd);
-              else
-                acc[j][t] = mfma16(ab[c & 1][t][e], ring[(B0 + c * T + j) % R][e], acc[j][t]);
+              acc[j][t] = mfma16(ab[c & 1][t][e], ring[(B0 + c * T + j) % R][e], acc[j][t]);
             });
           });
         });
@@ -550,19 +492,14 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-#if RK_MLP_SYNC
         if constexpr (kSync && (c + 1) % kMlpSyncChunks == 0 && c + 1 < KC) mlp_sync_barrier();
-#endif
       });
-      if constexpr (kSplit) acc[0][0] += acc_odd;
       if constexpr (IP0 && l == 0) mlp_lds_barrier();  // every wave's layer-0 reads of buf0 are done
       MLP_MARK(4 * l, t0);
 #ifdef RK_MLP_PHASES
       if (lane == 0 && l < 4) s_mlp_wave_marks[l][wave][0] = (unsigned)(clock64() - t0);
 #endif
-#if RK_MLP_EPI_PRIO
-      __builtin_amdgcn_s_setprio(2);
-#endif
+      __builtin_amdgcn_s_setprio(2);  // the epilogue ahead of the SIMD's MFMA loops (see mlp_layer)
       const float* img = epi + P::epi_off(l);
       auto epilogue = [&](auto DICE) {
 #pragma unroll
@@ -599,16 +536,6 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
         epilogue(std::true_type{});
       else
         epilogue(std::false_type{});
-#if RK_STREAM_FLAGS
-      if constexpr (l + 1 < NL) {
-        // this wave's output tiles are in LDS (its own LDS ops complete in order): publish them
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        unsigned bits = 0u;
-#pragma unroll
-        for (int j = 0; j < T; ++j) bits |= 1u << (wave + kMlpWaves * j);
-        if (lane == 0) __hip_atomic_fetch_or(&rk_stream_ready[l], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-#endif
 #ifdef RK_MLP_PHASES
       if (lane == 0 && l < 4) s_mlp_wave_marks[l][wave][1] = (unsigned)(clock64() - t0);
 #endif
@@ -620,11 +547,9 @@ __device__ __forceinline__ void mlp_stream_class(const rk_mlp_layer* __restrict_
     if constexpr (l + 2 == NL) head_prefetch();
     MLP_MARK(4 * l + 2, t0);
     if constexpr (l == NL - 1) STREAM_LAST_TS(2);
-    if constexpr (!RK_STREAM_FLAGS || l + 1 == NL) mlp_lds_barrier();  // (flags: only before the head)
+    mlp_lds_barrier();
     MLP_MARK(4 * l + 3, t0);
-#if RK_MLP_EPI_PRIO
     if constexpr (T > 0) __builtin_amdgcn_s_setprio(0);
-#endif
   });
 
   // head: one wave per row, as mlp_rows
