@@ -17,6 +17,9 @@ constexpr int kWave = 64;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Fields per owner of the table-sharded DeepFM's local steps (shard.hip, shard_train.hip).
+constexpr int kShardMaxFields = 32;
+
 // 16-B alignment of a device pointer (float4 / dwordx4 paths are chosen on the host).
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 

@@ -20,8 +20,6 @@
 
 namespace rk {
 
-constexpr int kShardMaxFields = 32;
-
 struct ShardPackArgs {
   const int64_t* idx[kShardMaxFields];
   int64_t base[kShardMaxFields];  // B * start_r + j

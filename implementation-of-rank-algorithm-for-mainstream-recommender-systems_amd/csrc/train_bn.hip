@@ -196,11 +196,10 @@ __global__ __launch_bounds__(256) void fm_backward_kernel(const float* __restric
   const int64_t b = i / D;
   const int d = (int)(i - b * D);
   const float* e = deep_in + b * ld_in + d;
-  float S = 0.f;
-  for (int f = 0; f < F; ++f) S += e[f * D];
+  const float S = fm_field_sum(e, F, D);  // train_common.h: shared with rk_shard_fm_backward_pack
   const float g2 = dfm2 ? dfm2[b] : 0.f;
   for (int f = 0; f < F; ++f)
-    out[b * ld_out + f * D + d] = (d_deep ? d_deep[b * ld_d + f * D + d] : 0.f) + g2 * (S - e[f * D]);
+    out[b * ld_out + f * D + d] = fm_grad(d_deep ? d_deep[b * ld_d + f * D + d] : 0.f, g2, S, e[f * D]);
 }
 
 // final_layer (Linear(3, 1) over [fm1, fm2, deep]) + sigmoid backward, with the incoming grads of

@@ -24,4 +24,19 @@ static inline uint32_t dropout_threshold(double p) {
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
 }
 
+// DeepFM's FM backward per embedding element (deepfm.py:135-140), shared by rk_fm_backward (V =
+// float) and rk_shard_fm_backward_pack (V = f32x4, the same operations per component):
+//   S = sum_f e_f, the fields in order (e[f * stride]);  d e_f = d_deep_f + dfm2 * (S - e_f)
+template <class V>
+__device__ __forceinline__ V fm_field_sum(const V* __restrict__ e, int F, int64_t stride) {
+  V S = {};
+  for (int f = 0; f < F; ++f) S += e[f * stride];
+  return S;
+}
+
+template <class V>
+__device__ __forceinline__ V fm_grad(V d_deep, float g2, V S, V e) {
+  return d_deep + g2 * (S - e);
+}
+
 }  // namespace rk

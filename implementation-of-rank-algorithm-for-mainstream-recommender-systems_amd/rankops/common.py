@@ -546,8 +546,8 @@ def check_eval(module: nn.Module):
     if module.training:
         raise NotImplementedError(
             f"{type(module).__name__}: the rankops engine implements the eval-mode forward "
-            f"(BatchNorm running stats, Dropout identity); call .eval() first. "
-            f"Training (backward) is the next row of the build plan (DESIGN.md).")
+            f"(BatchNorm running stats, Dropout identity) on this path; call .eval() first, or "
+            f"run the train-mode forward with autograd enabled (rankops.train).")
 
 
 def sqrt_f32(x: float) -> float:

@@ -1228,6 +1228,31 @@ def fm_backward(deep_in, d_deep, dfm2, num_fields, dim, out):
                              _lib.stream_of(deep_in)), "rk_fm_backward")
 
 
+def shard_fm_assemble(recv, num_fields, num_owners, dim, deep_in, fm1, fm2):
+    """rk_shard_fm_assemble: the received split-wire blocks of all owners -> deep_in [B, F * dim], fm1, fm2."""
+    lib = _lib.load()
+    check(lib.rk_shard_fm_assemble(ptr(recv), num_fields, num_owners, dim, deep_in.shape[0], ptr(deep_in),
+                                   deep_in.stride(0), ptr(fm1), ptr(fm2), _lib.stream_of(deep_in)),
+          "rk_shard_fm_assemble")
+
+
+def shard_fm_backward_pack(deep_in, d_deep, dfm2, dfm1, scale, num_fields, num_owners, dim, out):
+    """rk_shard_fm_backward_pack: scale * the FM backward, written into the gradient send blocks `out`."""
+    lib = _lib.load()
+    check(lib.rk_shard_fm_backward_pack(ptr(deep_in), deep_in.stride(0), ptr(d_deep),
+                                        d_deep.stride(0) if d_deep is not None else 0, ptr(dfm2), ptr(dfm1),
+                                        float(scale), deep_in.shape[0], num_fields, num_owners, dim, ptr(out),
+                                        _lib.stream_of(deep_in)), "rk_shard_fm_backward_pack")
+
+
+def shard_unpack_grads(recv, idx, num_fields, dim, num_sources, source_batch, ids, values2, values1):
+    """rk_shard_unpack_grads: the received gradient blocks + kept indices -> ids [F, N], values2 [F, N, dim],
+    values1 [N] (N = num_sources * source_batch)."""
+    lib = _lib.load()
+    check(lib.rk_shard_unpack_grads(ptr(recv), ptr(idx), num_fields, dim, num_sources, source_batch, ptr(ids),
+                                    ptr(values2), ptr(values1), _lib.stream_of(recv)), "rk_shard_unpack_grads")
+
+
 def fm_combine_backward(dprob, dtotal, dfm1_in, dfm2_in, ddeep_in, prob, fm1, fm2, deep, final_w, dfm1, dfm2, ddeep,
                         dfinal_w, dfinal_b):
     lib = _lib.load()

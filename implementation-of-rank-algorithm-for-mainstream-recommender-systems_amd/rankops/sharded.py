@@ -33,6 +33,28 @@ nn.Embedding weight plus one first-order partial sum per (sample, owner): B_l * 
 reads them in place with 16-B loads, which a 132-B stride would misalign for three rows in four,
 and the row exchange overlaps the next chunk's gather.  Reference: DeepFM.forward, deepfm.py:121-151 (the reference is single-device; the
 sharding is the MI355X build's own).
+
+Training (model.train()): hybrid parallel — the tables stay model-parallel on their
+owners, the dense layers are data-parallel replicas, and a step optimises the mean over ranks of the
+local mean losses (the DDP convention).
+
+    dense_opt, table_opt = model.optimizers(lr=1e-3)
+    loss = model.train_step(category, label, (dense_opt, table_opt))
+
+or, spelled out: zero_grad; prob = model(category)[0]; BCELoss()(prob.squeeze(), label).backward();
+model.sync_gradients(); both optimizers' step().  The train forward is one chunk (no pipeline, no
+capture) over the split wire whatever split_wire() says, world == 1 included (its exchanges are
+copies): index all-to-all, rk_shard_gather_rows_split, row all-to-all, rk_shard_fm_assemble, then
+DeepFM's train tail (BatchNorm with local batch statistics, Dropout from this rank's stream).
+loss.backward() is local: the dense parameters' local .grads, and the table gradients packed for
+the wire by rk_shard_fm_backward_pack (scaled by 1/P) and kept on the module — autograd runs backward
+on its own thread, where a collective would meet neither the caller's stream nor, with emulated
+ranks, the other ranks.  sync_gradients() then runs the collectives from the caller: the gradient
+all-to-all (the row exchange reversed), rk_shard_unpack_grads (every local table's .grad becomes an
+uncoalesced sparse COO tensor of P * B_l entries in (source, sample) order, for rankops.SparseAdam),
+and one flat bucket of all dense .grads and BatchNorm running statistics summed over ranks
+(`reduce_fn`, else all_reduce) and scaled by 1/P, so the replicas stay bit-identical.  One step may be
+outstanding: a second train backward before sync_gradients() raises.
 """
 from __future__ import annotations
 
@@ -40,7 +62,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import ops
+from . import ops, train
 from .common import EngineModule, Layer, PackedFMTable, check_eval, run_tail
 
 
@@ -115,6 +137,13 @@ class ShardedDeepFM(EngineModule):
         self.deep_output_layer = nn.Linear(width, 1)
         self.final_layer = nn.Linear(3, 1)
         self._fm_packs = {f: PackedFMTable() for f in self.local_fields}
+        # training (module docstring, "Training"): the dense gradients' all-reduce transport — None =
+        # torch.distributed.all_reduce(SUM) on `group`; otherwise a callable on the flat bucket, in
+        # place (tests bind an in-process reducer) — the dropout streams, and the one outstanding
+        # backward's (gradient send buffer, received indices, B_l) until sync_gradients() takes it
+        self.reduce_fn = None
+        self._dropout = train.DropoutStreams()
+        self._pending = None
 
     def packed_table(self, f):
         """This rank's packed [V_f, RS] table of field f (cached per weight version)."""
@@ -126,10 +155,20 @@ class ShardedDeepFM(EngineModule):
         rows = {f: e.num_embeddings for f, e in model.second_order_embeddings.items()}
         hidden = [l.out_features for l in model.deep_layers if isinstance(l, nn.Linear)]
         bn = any(isinstance(l, nn.BatchNorm1d) for l in model.deep_layers)
-        drop = any(isinstance(l, nn.Dropout) for l in model.deep_layers)
+        drops = [l.p for l in model.deep_layers if isinstance(l, nn.Dropout)]
         with torch.device("meta"):
-            sh = cls(rows, model.embedding_dim, hidden, 0.1 if drop else 0.0, bn, group=group, rank=rank,
+            sh = cls(rows, model.embedding_dim, hidden, drops[0] if drops else 0.0, bn, group=group, rank=rank,
                      world_size=world_size)
+        if [type(l) for l in sh.deep_layers] != [type(l) for l in model.deep_layers]:
+            raise ValueError("ShardedDeepFM.from_deepfm: the model's deep_layers are not DeepFM's "
+                             "Linear / [BatchNorm1d] / ReLU / [Dropout] units")
+        # the hyperparameters the state_dict does not carry: each Dropout's rate, each BatchNorm's
+        # eps and momentum (training reads them from the shard's own layers)
+        for mine, src in zip(sh.deep_layers, model.deep_layers):
+            if isinstance(src, nn.Dropout):
+                mine.p = src.p
+            elif isinstance(src, nn.BatchNorm1d):
+                mine.eps, mine.momentum = src.eps, src.momentum
         sd = model.state_dict()
         mine = {k: v for k, v in sd.items()
                 if not k.startswith(("first_order_embeddings.", "second_order_embeddings."))
@@ -228,24 +267,7 @@ class ShardedDeepFM(EngineModule):
         one rk_shard_gather_rows launch; int64: rk_concat_gather over the chunk's copy."""
         RS, F_me = row_stride(self.embedding_dim), len(self.local_fields)
         if self.split_wire() and F_me > 0:
-            # [s]: [bc][F_me][D] second-order rows, then pad4(bc) first-order partial sums
-            out = torch.empty(self.world * self._block(bc, F_me), device=recv_idx.device, dtype=torch.float32)
-            if bc == 0:
-                return out
-            from ._lib import Segment
-            second = [Segment(self.second_order_embeddings[f].weight.data_ptr(), None, 0,
-                              self.second_order_embeddings[f].weight.stride(0), self.field_rows[f],
-                              self.embedding_dim, 0) for f in self.local_fields]
-            first = [Segment(self.first_order_embeddings[f].weight.data_ptr(), None, 0,
-                             self.first_order_embeddings[f].weight.stride(0), self.field_rows[f], 1, 0)
-                     for f in self.local_fields]
-            lib = ops._lib.load()
-            ops._lib.ensure_device(out.device)
-            ops.check(lib.rk_shard_gather_rows_split(ops._seg_array(second), ops._seg_array(first), F_me,
-                                                     self.embedding_dim, recv_idx.data_ptr(), self.world, B_src, b0,
-                                                     bc, out.data_ptr(), ops._lib.stream_of(out)),
-                      "rk_shard_gather_rows_split")
-            return out
+            return self._gather_split(recv_idx, B_src, b0, bc)
         if recv_idx.dtype == torch.int32 and F_me > 0:
             out = torch.empty(self.world * bc, F_me * RS, device=recv_idx.device, dtype=torch.float32)
             if bc == 0:
@@ -262,6 +284,32 @@ class ShardedDeepFM(EngineModule):
             return self.gather_local(recv_idx, self.world * B_src)
         sel = recv_idx.view(self.world, B_src, F_me)[:, b0:b0 + bc].reshape(-1)
         return self.gather_local(sel, self.world * bc)
+
+    def _split_block(self, B: int, F_r: int) -> int:
+        """Floats of one owner's split-format block: [B][F_r][D] rows, then pad4(B) first-order floats."""
+        return B * F_r * self.embedding_dim + (B + 3) // 4 * 4 if F_r else 0
+
+    def _gather_split(self, recv_idx: torch.Tensor, B_src: int, b0: int, bc: int) -> torch.Tensor:
+        """rk_shard_gather_rows_split: per source [bc][F_me][D] second-order rows straight from the
+        nn.Embedding weights, then pad4(bc) first-order partial sums."""
+        F_me = len(self.local_fields)
+        out = torch.empty(self.world * self._split_block(bc, F_me), device=recv_idx.device, dtype=torch.float32)
+        if bc == 0 or F_me == 0:
+            return out
+        from ._lib import Segment
+        second = [Segment(self.second_order_embeddings[f].weight.data_ptr(), None, 0,
+                          self.second_order_embeddings[f].weight.stride(0), self.field_rows[f],
+                          self.embedding_dim, 0) for f in self.local_fields]
+        first = [Segment(self.first_order_embeddings[f].weight.data_ptr(), None, 0,
+                         self.first_order_embeddings[f].weight.stride(0), self.field_rows[f], 1, 0)
+                 for f in self.local_fields]
+        lib = ops._lib.load()
+        ops._lib.ensure_device(out.device)
+        ops.check(lib.rk_shard_gather_rows_split(ops._seg_array(second), ops._seg_array(first), F_me,
+                                                 self.embedding_dim, recv_idx.data_ptr(), self.world, B_src, b0,
+                                                 bc, out.data_ptr(), ops._lib.stream_of(out)),
+                  "rk_shard_gather_rows_split")
+        return out
 
     def gather_local(self, recv_idx: torch.Tensor, rows_total: int) -> torch.Tensor:
         """Step 2: rows [s*B_l + b][f_me][RS] from this rank's tables (rk_concat_gather)."""
@@ -402,13 +450,142 @@ class ShardedDeepFM(EngineModule):
         return self.deep_output_layer.weight.device
 
     def forward(self, category: dict):
-        """category: {field: [B_l] int64} for every field, this rank's samples."""
-        check_eval(self)
+        """category: {field: [B_l] int64} for every field, this rank's samples.  In train mode the
+        outputs are attached to autograd (train_forward)."""
+        if self.training and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.dense_parameters())):
+            # the train forward hangs on autograd through the dense parameters (the tables get their
+            # gradients from sync_gradients): without a dense parameter that requires grad it has no backward
+            raise NotImplementedError(
+                "ShardedDeepFM: the train-mode forward needs autograd enabled and at least one dense "
+                "(non-table) parameter that requires grad; call .eval() for the eval-mode forward")
         missing = [f for f in self.fields if f not in category]
         if missing:
             raise KeyError(f"ShardedDeepFM.forward: category features missing: {missing}")
         cat = {f: ops.as_index(category[f], f"category[{f!r}]") for f in self.fields}
+        if self.training:
+            return self.train_forward(cat)
         return self.run_steps(cat)
+
+    # ------------------------------------------------------------------ training
+
+    def train_row_splits(self, B_l: int):
+        """(output_split_sizes, input_split_sizes) of the train-mode row all-to-all, in floats: always
+        the split format.  The gradient all-to-all runs the other way with the two lists swapped."""
+        F_me = len(self.local_fields)
+        return ([self._split_block(B_l, len(self.fields_of[r])) for r in range(self.world)],
+                [self._split_block(B_l, F_me)] * self.world)
+
+    def _check_trainable(self):
+        D = self.embedding_dim
+        if self.index_dtype != torch.int32:
+            raise NotImplementedError("ShardedDeepFM training: int32 indices on the wire (every table < 2^31 rows)")
+        if D < 4 or D % 4:
+            raise NotImplementedError(f"ShardedDeepFM training: embedding_dim % 4 == 0 (got {D})")
+        if max(len(fr) for fr in self.fields_of) > 32:
+            raise NotImplementedError("ShardedDeepFM training: at most 32 fields per owner "
+                                      f"(got {max(len(fr) for fr in self.fields_of)})")
+        if len(self.fields) > 32:  # rk_shard_pack_indices packs one rank's index columns: 32 in all
+            raise NotImplementedError("ShardedDeepFM training: at most 32 fields in all, the limit of the index "
+                                      f"pack kernel (got {len(self.fields)})")
+
+    def train_forward(self, cat: dict):
+        """One chunk, no pipeline, no capture: index all-to-all, rk_shard_gather_rows_split, row
+        all-to-all (the split wire whatever split_wire() says; world == 1 copies), then
+        rk_shard_fm_assemble and DeepFM's train tail under autograd (train._ShardedDeepFMTrain)."""
+        self._check_trainable()
+        B_l = cat[self.fields[0]].shape[0]
+        with torch.no_grad():
+            recv_idx = self.exchange_indices(cat, B_l)
+            rows = self._gather_split(recv_idx, B_l, 0, B_l)
+            out_s, in_s = self.train_row_splits(B_l)
+            recv_rows = self._exchange(torch.empty(sum(out_s), device=rows.device, dtype=torch.float32), rows,
+                                       out_s, in_s)
+        return train.sharded_deepfm_train_forward(self, recv_rows, recv_idx, B_l)
+
+    def tables(self):
+        """This rank's table weights: first-order then second-order, each in local field order."""
+        return ([self.first_order_embeddings[f].weight for f in self.local_fields]
+                + [self.second_order_embeddings[f].weight for f in self.local_fields])
+
+    def dense_parameters(self):
+        """The replicated parameters (every rank holds and updates a copy)."""
+        mine = {id(w) for w in self.tables()}
+        return [p for p in self.parameters() if id(p) not in mine]
+
+    def sync_gradients(self):
+        """The collective half of a train backward; call it from the rank's own thread / process
+        after loss.backward().  (1) gradient all-to-all: the packed send buffer of the backward goes
+        to the owners (the forward's row exchange reversed).  (2) rk_shard_unpack_grads: every local
+        table's .grad becomes an uncoalesced sparse COO tensor of nnz = P * B_l entries in (source,
+        sample) order; the first-order gradients share one values vector.  (3) the dense .grads and
+        the BatchNorm running statistics, as one flat bucket, are summed over the ranks (reduce_fn,
+        else all_reduce) and scaled by 1 / P; the .grads become views of the bucket."""
+        if self._pending is None:
+            raise RuntimeError("ShardedDeepFM.sync_gradients: no train backward is outstanding")
+        send, recv_idx, B_l = self._pending
+        self._pending = None
+        P, D, F_me = self.world, self.embedding_dim, len(self.local_fields)
+        out_s, in_s = self.train_row_splits(B_l)
+        recv = self._exchange(torch.empty(sum(in_s), device=send.device, dtype=torch.float32), send, in_s, out_s)
+        N = P * B_l
+        if F_me and N:
+            # one allocation: ids int64 [F_me, N] | values2 float32 [F_me, N, D] | values1 float32 [N]
+            n_ids, n_v2 = 8 * F_me * N, 4 * F_me * N * D
+            o_v2 = (n_ids + 15) // 16 * 16
+            flat = torch.empty(o_v2 + n_v2 + 4 * N, dtype=torch.uint8, device=send.device)
+            ids = flat[:n_ids].view(torch.int64).view(F_me, N)
+            values2 = flat[o_v2:o_v2 + n_v2].view(torch.float32).view(F_me, N, D)
+            values1 = flat[o_v2 + n_v2:].view(torch.float32).view(N, 1)
+            ops.shard_unpack_grads(recv, recv_idx, F_me, D, P, B_l, ids, values2, values1)
+            for j, f in enumerate(self.local_fields):
+                w1, w2 = self.first_order_embeddings[f].weight, self.second_order_embeddings[f].weight
+                if w1.requires_grad:  # a frozen table gets no gradient, as under autograd
+                    w1.grad = torch.sparse_coo_tensor(ids[j].unsqueeze(0), values1, w1.shape, check_invariants=False)
+                if w2.requires_grad:
+                    w2.grad = torch.sparse_coo_tensor(ids[j].unsqueeze(0), values2[j], w2.shape,
+                                                      check_invariants=False)
+        if P > 1:
+            self._reduce_dense()
+
+    def _reduce_dense(self):
+        params = [p for p in self.dense_parameters() if p.grad is not None]
+        stats = [b for m in self.deep_layers if isinstance(m, nn.BatchNorm1d) and m.track_running_stats
+                 for b in (m.running_mean, m.running_var)]
+        with torch.no_grad():
+            bucket = torch.cat([p.grad.reshape(-1) for p in params] + [b.reshape(-1) for b in stats])
+            if self.reduce_fn is not None:
+                self.reduce_fn(bucket)
+            else:
+                dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group)
+            bucket.mul_(1.0 / self.world)
+            views = bucket.split([t.numel() for t in params + stats])
+            for p, v in zip(params, views):
+                p.grad = v.view(p.shape)
+            if stats:
+                torch._foreach_copy_(stats, [v.view(b.shape) for b, v in zip(stats, views[len(params):])])
+
+    def optimizers(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        """(rankops.Adam over the dense replicas, rankops.SparseAdam over this rank's tables); the
+        second is None on a rank that owns no table (world > fields)."""
+        dense = train.Adam(self.dense_parameters(), lr=lr, betas=betas, eps=eps)
+        tables = self.tables()
+        return dense, (train.SparseAdam(tables, lr=lr, betas=betas, eps=eps) if tables else None)
+
+    def train_step(self, category: dict, label: torch.Tensor, opts):
+        """zero_grad, forward, the local mean BCE (deepfm.py:168), backward, sync_gradients and both
+        optimizer steps; returns the detached local loss."""
+        dense_opt, table_opt = opts
+        dense_opt.zero_grad()
+        if table_opt is not None:
+            table_opt.zero_grad()
+        prob = self(category)[0]
+        loss = nn.functional.binary_cross_entropy(prob.reshape(label.shape), label)
+        loss.backward()
+        self.sync_gradients()
+        dense_opt.step()
+        if table_opt is not None:
+            table_opt.step()
+        return loss.detach()
 
     def chunk_bounds(self, B_l: int, chunks: int = None):
         """Sample ranges of the exchange pipeline (overlap the row all-to-all with

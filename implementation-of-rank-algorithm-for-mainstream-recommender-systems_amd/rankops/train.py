@@ -402,6 +402,60 @@ def _unit_params(units):
     return out
 
 
+def deepfm_tail_forward(ctx, model, deep_in, fm1, fm2):
+    """The train forward after the FM front end, shared by DeepFM and ShardedDeepFM (deepfm.py:142-151):
+    the Linear -> BN -> ReLU -> Dropout units, deep_output_layer, final_layer + sigmoid.  Saves on ctx
+    what deepfm_tail_backward reads; returns (prob, total, deep)."""
+    B, dev = deep_in.shape[0], deep_in.device
+    units = deep_units(model.deep_layers)
+    seed, slot = model._dropout.next(dev)
+    saved = deep_stack_forward(deep_in, units, seed, slot)
+    last = saved[-1][1] if saved else deep_in
+    deep = torch.empty(B, 1, device=dev, dtype=torch.float32)
+    total = torch.empty(B, 1, device=dev, dtype=torch.float32)
+    prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
+    ep = ops.make_epilogue(head_w=model.deep_output_layer.weight, head_b=model.deep_output_layer.bias, fm1=fm1,
+                           fm2=fm2, final_w=model.final_layer.weight, final_b=model.final_layer.bias,
+                           head_aux=deep, head_logit=total, head_prob=prob)
+    ops.mlp_forward(last, [], ep)
+    ctx.model, ctx.units, ctx.seed = model, units, seed
+    ctx.save_for_backward(deep_in, fm1, fm2, deep, prob, slot, *[t for s in saved for t in s])
+    return prob, total, deep
+
+
+def deepfm_tail_backward(ctx, dprob, dtotal, dfm1_o, dfm2_o, ddeep_o):
+    """Backward of deepfm_tail_forward: (deep_in, dfm1, dfm2, dL/d deep_in, the dense parameters'
+    gradients in deepfm_dense_params order)."""
+    model, units = ctx.model, ctx.units
+    deep_in, fm1, fm2, deep, prob, slot, *flat = ctx.saved_tensors
+    saved = [tuple(flat[4 * u:4 * u + 4]) for u in range(len(units))]
+    B, dev = deep_in.shape[0], deep_in.device
+    go = [_grad_out(g, prob) for g in (dprob, dtotal, dfm1_o, dfm2_o, ddeep_o)]
+    dfm1 = torch.empty(B, 1, device=dev, dtype=torch.float32)
+    dfm2 = torch.empty(B, 1, device=dev, dtype=torch.float32)
+    ddeep = torch.empty(B, 1, device=dev, dtype=torch.float32)
+    dfinal_w = torch.empty_like(model.final_layer.weight)
+    dfinal_b = torch.empty(1, device=dev, dtype=torch.float32)
+    ops.fm_combine_backward(*go, prob, fm1, fm2, deep, model.final_layer.weight, dfm1, dfm2, ddeep, dfinal_w,
+                            dfinal_b)
+    last = saved[-1][1] if saved else deep_in
+    dy = torch.empty_like(last)
+    dw_do = torch.empty_like(model.deep_output_layer.weight)
+    db_do = torch.empty(1, device=dev, dtype=torch.float32)
+    ops.logit_head_backward(ddeep, None, None, last, None, model.deep_output_layer.weight, dy, None, dw_do, db_do)
+    d_deep_in, unit_grads = deep_stack_backward(dy, deep_in, units, saved, ctx.seed, slot)
+    flat_g = [t for g in unit_grads for t in g if t is not None]
+    return deep_in, dfm1, dfm2, d_deep_in, (*flat_g, dw_do, db_do, dfinal_w, dfinal_b)
+
+
+def deepfm_dense_params(model, units):
+    """The replicated (non-table) parameters of a DeepFM, in the order of deepfm_tail_backward's gradients."""
+    if model.deep_output_layer.bias is None or model.final_layer.bias is None:
+        raise NotImplementedError("rankops DeepFM training expects the reference's biased output layers")
+    return _unit_params(units) + [model.deep_output_layer.weight, model.deep_output_layer.bias,
+                                  model.final_layer.weight, model.final_layer.bias]
+
+
 class _DeepFMTrain(torch.autograd.Function):
     """DeepFM forward + backward in train mode (deepfm.py:121-151): FM gather, Linear -> BN(batch
     statistics) -> ReLU -> Dropout units, deep_output_layer, final_layer + sigmoid."""
@@ -418,42 +472,16 @@ class _DeepFMTrain(torch.autograd.Function):
         fm1 = torch.empty(B, 1, device=dev, dtype=torch.float32)
         fm2 = torch.empty(B, 1, device=dev, dtype=torch.float32)
         ops.fm_gather(second, first, D, B, deep_in, fm1, fm2)
-        units = deep_units(model.deep_layers)
-        seed, slot = model._dropout.next(dev)
-        saved = deep_stack_forward(deep_in, units, seed, slot)
-        last = saved[-1][1] if saved else deep_in
-        deep = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        total = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        ep = ops.make_epilogue(head_w=model.deep_output_layer.weight, head_b=model.deep_output_layer.bias, fm1=fm1,
-                               fm2=fm2, final_w=model.final_layer.weight, final_b=model.final_layer.bias,
-                               head_aux=deep, head_logit=total, head_prob=prob)
-        ops.mlp_forward(last, [], ep)
-        ctx.model, ctx.names, ctx.idx, ctx.units, ctx.seed = model, names, idx, units, seed
-        ctx.save_for_backward(deep_in, fm1, fm2, deep, prob, slot, *[t for s in saved for t in s])
+        prob, total, deep = deepfm_tail_forward(ctx, model, deep_in, fm1, fm2)
+        ctx.names, ctx.idx = names, idx
         return prob, total, fm1, fm2, deep
 
     @staticmethod
     def backward(ctx, dprob, dtotal, dfm1_o, dfm2_o, ddeep_o):
-        model, units = ctx.model, ctx.units
-        deep_in, fm1, fm2, deep, prob, slot, *flat = ctx.saved_tensors
-        saved = [tuple(flat[4 * u:4 * u + 4]) for u in range(len(units))]
+        model = ctx.model
+        deep_in, dfm1, dfm2, d_deep_in, dense_grads = deepfm_tail_backward(ctx, dprob, dtotal, dfm1_o, dfm2_o, ddeep_o)
         B, dev = deep_in.shape[0], deep_in.device
         D, F = model.embedding_dim, len(ctx.names)
-        go = [_grad_out(g, prob) for g in (dprob, dtotal, dfm1_o, dfm2_o, ddeep_o)]
-        dfm1 = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        dfm2 = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        ddeep = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        dfinal_w = torch.empty_like(model.final_layer.weight)
-        dfinal_b = torch.empty(1, device=dev, dtype=torch.float32)
-        ops.fm_combine_backward(*go, prob, fm1, fm2, deep, model.final_layer.weight, dfm1, dfm2, ddeep, dfinal_w,
-                                dfinal_b)
-        last = saved[-1][1] if saved else deep_in
-        dy = torch.empty_like(last)
-        dw_do = torch.empty_like(model.deep_output_layer.weight)
-        db_do = torch.empty(1, device=dev, dtype=torch.float32)
-        ops.logit_head_backward(ddeep, None, None, last, None, model.deep_output_layer.weight, dy, None, dw_do, db_do)
-        d_deep_in, unit_grads = deep_stack_backward(dy, deep_in, units, saved, ctx.seed, slot)
         d_second = torch.empty(B, F * D, device=dev, dtype=torch.float32)
         ops.fm_backward(deep_in, d_deep_in, dfm2, F, D, d_second)
         w2 = [model.second_order_embeddings[n].weight for n in ctx.names]
@@ -465,19 +493,56 @@ class _DeepFMTrain(torch.autograd.Function):
         else:
             g2 = embedding_grads(w2, ctx.idx, 0, d_second)
             g1 = embedding_grads(w1, ctx.idx, 0, dfm1, cols=[0] * F)
-        flat_g = [t for g in unit_grads for t in g if t is not None]
-        return (None, None, None, *g1, *g2, *flat_g, dw_do, db_do, dfinal_w, dfinal_b)
+        return (None, None, None, *g1, *g2, *dense_grads)
 
 
 def deepfm_train_forward(model, names, idx):
-    if model.deep_output_layer.bias is None or model.final_layer.bias is None:
-        raise NotImplementedError("rankops DeepFM training expects the reference's biased output layers")
     units = deep_units(model.deep_layers)
+    dense = deepfm_dense_params(model, units)
     params = ([model.first_order_embeddings[n].weight for n in names]
-              + [model.second_order_embeddings[n].weight for n in names] + _unit_params(units)
-              + [model.deep_output_layer.weight, model.deep_output_layer.bias, model.final_layer.weight,
-                 model.final_layer.bias])
+              + [model.second_order_embeddings[n].weight for n in names] + dense)
     return _DeepFMTrain.apply(model, names, idx, *params)
+
+
+class _ShardedDeepFMTrain(torch.autograd.Function):
+    """ShardedDeepFM's train forward + the local half of its backward (rankops/sharded.py): the
+    received row blocks are assembled (rk_shard_fm_assemble) and run through DeepFM's tail; the
+    backward hands autograd the local gradients of the replicated dense parameters and leaves the
+    table gradients, packed for the gradient all-to-all by rk_shard_fm_backward_pack and already
+    scaled by 1 / world, on the module for sync_gradients().  No collective runs in here: autograd
+    calls backward from its own thread, where neither a barrier nor the caller's stream is safe."""
+
+    @staticmethod
+    def forward(ctx, model, recv_rows, recv_idx, B, *params):
+        D, F, dev = model.embedding_dim, len(model.fields), recv_rows.device
+        deep_in = torch.empty(B, F * D, device=dev, dtype=torch.float32)
+        fm1 = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        fm2 = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        if B:
+            ops.shard_fm_assemble(recv_rows, F, model.world, D, deep_in, fm1, fm2)
+        prob, total, deep = deepfm_tail_forward(ctx, model, deep_in, fm1, fm2)
+        ctx.recv_idx = recv_idx
+        return prob, total, fm1, fm2, deep
+
+    @staticmethod
+    def backward(ctx, dprob, dtotal, dfm1_o, dfm2_o, ddeep_o):
+        model = ctx.model
+        if model._pending is not None:
+            raise RuntimeError("ShardedDeepFM: a train backward is already outstanding; call sync_gradients() "
+                               "before the next backward (one step at a time)")
+        deep_in, dfm1, dfm2, d_deep_in, dense_grads = deepfm_tail_backward(ctx, dprob, dtotal, dfm1_o, dfm2_o, ddeep_o)
+        B = deep_in.shape[0]
+        send = torch.empty(sum(model.train_row_splits(B)[0]), device=deep_in.device, dtype=torch.float32)
+        if B:
+            ops.shard_fm_backward_pack(deep_in, d_deep_in, dfm2, dfm1, 1.0 / model.world, len(model.fields),
+                                       model.world, model.embedding_dim, send)
+        model._pending = (send, ctx.recv_idx, B)
+        return (None, None, None, None, *dense_grads)
+
+
+def sharded_deepfm_train_forward(model, recv_rows, recv_idx, B):
+    units = deep_units(model.deep_layers)
+    return _ShardedDeepFMTrain.apply(model, recv_rows, recv_idx, B, *deepfm_dense_params(model, units))
 
 
 # ---------------------------------------------------------------- DIN

@@ -62,6 +62,8 @@
  *   rk_bn_act_train_forward / rk_bn_act_backward  Linear -> BatchNorm1d (train) -> ReLU -> Dropout
  *                      and its backward                       deepfm.py:100-109
  *   rk_fm_backward, rk_fm_combine_backward  FM and final_layer + sigmoid backward  deepfm.py:122-151
+ *   rk_shard_fm_assemble, rk_shard_fm_backward_pack, rk_shard_unpack_grads  the table-sharded
+ *                      DeepFM's train step around its all-to-alls (the sharding is this build's own)
  *   rk_rng_next, rk_dropout_mask  dropout stream counter / explicit mask
  *   rk_dice_train_forward / rk_dice_backward  Dice with batch statistics and its backward  din.py:26-36
  *   rk_prelu_train_forward / rk_prelu_backward  the activation='prelu' option (nn.PReLU)  din.py:277-279
@@ -643,6 +645,37 @@ int rk_shard_gather_rows_split(const rk_segment* second, const rk_segment* first
 int rk_deepfm_forward_fo(const rk_segment* fields, const float* const* first, const int64_t* first_ld,
                          int32_t num_fields, int32_t dim, int64_t batch, const rk_mlp_layer* layers,
                          int32_t nlayers, const rk_epilogue* head, float* fm1, float* fm2, void* stream);
+
+/* ---- table-sharded DeepFM, training (rankops.sharded).  The wire is the split
+ * format above in both directions; fields are dealt round robin, field f on owner f % num_owners
+ * at slot f / num_owners, so owner r holds F_r = F / P + (r < F % P) fields and its block of
+ * [batch][F_r][dim] rows then pad4(batch) first-order floats follows the blocks of owners 0..r-1
+ * (an owner without fields has no block).  dim % 4 == 0, at most 32 fields per owner, buffers
+ * 16-B aligned; anything else returns RK_ERR_INVALID before any write.  batch == 0 returns RK_OK
+ * without a launch. ---- */
+/* Receiver, forward: recv (the P blocks as received from the row all-to-all) -> deep_in
+ * [batch, num_fields * dim] in field order (ld_deep % 4 == 0), fm1[b] = the owners' first-order
+ * partials added in owner order, fm2[b] = 0.5 * sum_d ((sum_f e)^2 - sum_f e^2). */
+int rk_shard_fm_assemble(const float* recv, int32_t num_fields, int32_t num_owners, int32_t dim,
+                         int64_t batch, float* deep_in, int64_t ld_deep, float* fm1, float* fm2,
+                         void* stream);
+/* Receiver, backward: rk_fm_backward's gradient, times scale, written straight into the gradient
+ * send buffer `out` (the same P blocks): row (b, f) = scale * (d_deep[b, f dim + d] + dfm2[b] *
+ * (S_d - e[b, f, d])), S_d summed in field order from deep_in; every owner's tail gets
+ * scale * dfm1[b], its pad lanes zeros.  d_deep and dfm2 may be NULL (zero). */
+int rk_shard_fm_backward_pack(const float* deep_in, int64_t ld_in, const float* d_deep, int64_t ld_d,
+                              const float* dfm2, const float* dfm1, float scale, int64_t batch,
+                              int32_t num_fields, int32_t num_owners, int32_t dim, float* out,
+                              void* stream);
+/* Owner, backward: recv = the gradient blocks of every source s for this owner's num_fields
+ * tables ([source_batch][num_fields][dim] rows then pad4(source_batch) first-order gradients per
+ * source), idx = the int32 indices kept from the forward [s][b][j].  With N = num_sources *
+ * source_batch and i = s * source_batch + b:  ids[j * N + i] = idx[s][b][j] widened (-1 stays -1),
+ * values2[(j * N + i) * dim ..] = the row, values1[i] = the tail value (shared by the first-order
+ * gradients of all the tables).  num_fields == 0 returns RK_OK without a launch. */
+int rk_shard_unpack_grads(const float* recv, const int32_t* idx, int32_t num_fields, int32_t dim,
+                          int32_t num_sources, int64_t source_batch, int64_t* ids, float* values2,
+                          float* values1, void* stream);
 
 /* FwFM.forward (fwfm.py:114-139): per sample, logit = sum_f linear[f] row + sum_{i<j} field_weight[p]
  * <embeddings[i] row, embeddings[j] row> + bias[0] (p runs i-major over i < j, fwfm.py:129-136),
