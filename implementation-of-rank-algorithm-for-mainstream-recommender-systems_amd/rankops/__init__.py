@@ -7,6 +7,7 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
     DeepFM                                 algorithm/DeepFM/deepfm.py
     DIN, Dice, din_attention               algorithm/DIN/din.py
     DIEN, dien_interest, dien_aux_loss     algorithm/DIEN/dien.py (with the auxiliary loss)
+    dien_extract, dien_evolve, DIEN.score  the same split for one history and many candidates
     AFM, create_feature_columns            algorithm/AFM/afm.py
     DeepCrossingModel, residual_unit       algorithm/DeepCrossing/deepcrossing.py
     BSTModel, BSTTransformer               algorithm/BST/bst.py
@@ -30,7 +31,8 @@ from .dcn import DCNModel, cross_layer  # noqa: F401
 from .deepcrossing import DeepCrossingModel, residual_unit  # noqa: F401
 from .deepfm import DeepFM  # noqa: F401
 from .din import DIN, Dice, din_attention, din_attention_gather  # noqa: F401
-from .dien import DIEN, dien_aux_loss, dien_aux_loss_gather, dien_interest, dien_interest_gather  # noqa: F401
+from .dien import (DIEN, DIENInterests, dien_aux_loss, dien_aux_loss_gather, dien_evolve, dien_extract,  # noqa: F401
+                   dien_extract_gather, dien_interest, dien_interest_gather)
 from .fwfm import FwFM  # noqa: F401
 from .loader import BatchAssembler, Vocabulary, label_encode, wechat_vocabularies  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
@@ -41,5 +43,6 @@ __all__ = [
     "Dice", "FwFM", "RankOpsError", "Vocabulary", "create_feature_columns", "cross_layer", "din_attention", "din_attention_gather",
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
-    "dien_aux_loss", "dien_aux_loss_gather", "SparseAdam",
+    "dien_aux_loss", "dien_aux_loss_gather", "dien_extract", "dien_extract_gather", "dien_evolve", "DIENInterests",
+    "SparseAdam",
 ]

@@ -181,6 +181,21 @@ SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32]
         + [c_void_p] * 9 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
+    "rk_dien_extract": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32]
+        + [c_void_p] * 4 + [c_void_p, c_void_p],
+    ),
+    "rk_dien_extract_dense": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 4
+        + [c_void_p, c_void_p],
+    ),
+    "rk_dien_evolve": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32]
+        + [c_void_p] * 5 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
+    ),
     "rk_dien_interest_backward_workspace_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
     "rk_dien_interest_backward": (
         ctypes.c_int,

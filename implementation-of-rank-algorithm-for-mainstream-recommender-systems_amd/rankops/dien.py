@@ -33,6 +33,12 @@ rk_dien_interest (history gather, GRU, attention scores, masked softmax, AGRU / 
 final interest state into the row's last nh columns, and the fcn stack runs as DIN's tail.  The row
 order is DIN's (dense in the given order, category in ModuleDict order), not input_layer's
 alphabetical one: there is no TF checkpoint this could ever load.
+
+Request-level scoring (eval, inference only): `extract_interests(sequence)` runs the interest
+extractor over R histories once (rk_dien_extract), `score(dense, category, target, interests,
+request_index)` runs attention, evolution and the tail for B candidates that name their request
+(rk_dien_evolve); bit-equal to `forward` on the histories repeated per candidate.  As functions:
+`dien_extract(_gather)`, `dien_evolve`.  `forward` keeps the one fused launch.
 """
 from __future__ import annotations
 
@@ -250,6 +256,132 @@ def dien_interest_gather(query, table, seq, keys_length, weights, cell_type="AGR
         except ops._lib.RankOpsError as e:
             _convert(e, H, nh, T)
     return _pack(out, att, hs, return_attention, return_states)
+
+
+# ------------------------------------------------------------------ request-level scoring
+
+def _extract_weights(weights, H: int):
+    """The nine-tuple checked as dien_interest checks it; returns the extractor's four and nh."""
+    ws, nh = _weights(weights, H)
+    return ws[:4], nh
+
+
+def dien_extract(keys, keys_length, weights):
+    """dien_extract(keys[R,T,H], keys_length[R], weights) -> hs [R,T,nh]: the interest extractor (TF
+    GRUCell over the history, pass 1 of dien_interest) once per request, on rk_dien_extract_dense.
+    Rows t >= keys_length are zero; hs is bit-equal to dien_interest(..., return_states=True)'s.
+    `weights` is dien_interest's nine-tuple, of which the first four (Wg, bg, Wc, bc) are used; hs
+    is valid only for them.  Feed it to dien_evolve with one query per candidate.
+    Inference only: the result carries no grad_fn; train through dien_interest."""
+    keys = ops.as_f32(keys, "keys")
+    keys_length = ops.as_index(keys_length, "keys_length")
+    if keys.dim() != 3:
+        raise ValueError(f"dien_extract: keys must be [R, T, H], got {tuple(keys.shape)}")
+    R, T, H = keys.shape
+    if keys_length.dim() != 1 or keys_length.shape[0] != R:
+        raise ValueError(f"dien_extract: keys_length must be [{R}], got {tuple(keys_length.shape)}")
+    ws, nh = _extract_weights(weights, H)
+    _check_envelope(H, nh, T)
+    keys = keys.detach()
+    if keys.stride(2) != 1 or keys.stride(1) % 4 or keys.stride(0) % 4 or keys.data_ptr() % 16:
+        keys = keys.contiguous()
+    hs = torch.empty(R, T, nh, device=keys.device, dtype=torch.float32)
+    if R > 0:
+        try:
+            ops.dien_extract_dense(keys, keys_length.contiguous(), nh, [w.detach() for w in ws], hs)
+        except ops._lib.RankOpsError as e:
+            _convert(e, H, nh, T)
+    return hs
+
+
+def dien_extract_gather(table, seq, keys_length, weights):
+    """dien_extract with the histories given as (embedding table [V,H], ids [R,T]): the gather
+    happens inside the kernel (rk_dien_extract); ids at t >= keys_length are never read.
+    Bit-equal to dien_extract(table[seq], ...).
+    Inference only: the result carries no grad_fn; train through dien_interest_gather."""
+    table = ops.as_f32(table, "table")
+    seq = ops.as_index(seq, "keys index")
+    keys_length = ops.as_index(keys_length, "keys_length")
+    if table.dim() != 2 or seq.dim() != 2:
+        raise ValueError(f"dien_extract_gather: table {tuple(table.shape)} and ids {tuple(seq.shape)} do not match")
+    R, T = seq.shape
+    H = table.shape[1]
+    if keys_length.dim() != 1 or keys_length.shape[0] != R:
+        raise ValueError(f"dien_extract_gather: keys_length must be [{R}], got {tuple(keys_length.shape)}")
+    ws, nh = _extract_weights(weights, H)
+    _check_envelope(H, nh, T)
+    table = table.detach()
+    if table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
+        table = table.contiguous()
+    hs = torch.empty(R, T, nh, device=table.device, dtype=torch.float32)
+    if R > 0:
+        try:
+            ops.dien_extract(table, seq.contiguous(), keys_length.contiguous(), T, H, nh, [w.detach() for w in ws],
+                             hs, R, table.device)
+        except ops._lib.RankOpsError as e:
+            _convert(e, H, nh, T)
+    return hs
+
+
+def dien_evolve(query, hs, keys_length, request_index, weights, cell_type="AGRU", return_attention=False):
+    """dien_evolve(query[B,H], hs[R,T,nh], keys_length[R], request_index[B], weights) -> final interest
+    state [B,nh] on rk_dien_evolve: candidate b is scored against the history of request
+    request_index[b] (any order; a request may have no candidate or many): attention of hs against
+    `A . query`, masked softmax over all T positions, then the AGRU / AUGRU cell over hs for
+    t < keys_length.  `return_attention` adds the attention weights [B,T].  State and attention
+    are bit-equal to dien_interest with that request's history repeated for every candidate.
+    `weights` is dien_interest's nine-tuple, of which the last five (A, Vg, vg, Vc, vc) are used;
+    `hs` and `keys_length` are dien_extract's, computed with the same nine.  Rows of hs at
+    t >= keys_length are never read; a request_index outside [0, R) gives a zero state and raises
+    the index-out-of-range flag (rankops.error_flags()).
+    Inference only: the results carry no grad_fn; train through dien_interest."""
+    cell = _cell(cell_type)
+    query = ops.as_f32(query, "query")
+    hs = ops.as_f32(hs, "hs")
+    keys_length = ops.as_index(keys_length, "keys_length")
+    request_index = ops.as_index(request_index, "request_index")
+    if query.dim() != 2 or hs.dim() != 3:
+        raise ValueError(f"dien_evolve: query {tuple(query.shape)} must be [B, H] and hs {tuple(hs.shape)} [R, T, nh]")
+    B, H = query.shape
+    R, T, _ = hs.shape
+    if keys_length.dim() != 1 or keys_length.shape[0] != R:
+        raise ValueError(f"dien_evolve: keys_length must be [{R}], got {tuple(keys_length.shape)}")
+    if request_index.dim() != 1 or request_index.shape[0] != B:
+        raise ValueError(f"dien_evolve: request_index must be [{B}], one request per query row, got "
+                         f"{tuple(request_index.shape)}")
+    ws, nh = _weights(weights, H)
+    if hs.shape[2] != nh:
+        raise ValueError(f"dien_evolve: hs must be [R, T, {nh}], got {tuple(hs.shape)}")
+    _check_envelope(H, nh, T)
+    if B > 0 and R == 0:
+        raise ValueError("dien_evolve: hs holds no request, yet request_index names one per query row")
+    query, hs = query.detach(), hs.detach().contiguous()
+    if query.stride(1) != 1:
+        query = query.contiguous()
+    f32 = dict(device=query.device, dtype=torch.float32)
+    out = torch.empty(B, nh, **f32)
+    att = torch.empty(B, T, **f32) if return_attention else None
+    if B > 0:
+        try:
+            ops.dien_evolve(query.data_ptr(), query.stride(0), hs, keys_length.contiguous(), request_index.contiguous(),
+                            H, cell, [w.detach() for w in ws[4:]], out.data_ptr(), out.stride(0), att, B, query.device)
+        except ops._lib.RankOpsError as e:
+            _convert(e, H, nh, T)
+    return (out, att) if return_attention else out
+
+
+class DIENInterests:
+    """What DIEN.extract_interests returns: `hs` [R, T, nh], the extractor states of R behaviour
+    histories, and `keys_length` [R].  Valid only for the weights it was computed with: a cache
+    of these keyed by user must be dropped after every weight update."""
+    __slots__ = ("hs", "keys_length")
+
+    def __init__(self, hs, keys_length):
+        self.hs = hs
+        self.keys_length = keys_length
+
+    def __len__(self):
+        return self.hs.shape[0]
 
 
 AUX_ENVELOPE = ENVELOPE + f", 1 <= T_neg (negatives per step) <= {ops.DIEN_AUX_MAX_NEG}"
@@ -481,6 +613,13 @@ class DIEN(EngineModule):
                 self.gru["candidate"].bias, self.attention_project_matrix, self.evolution["gates"].weight,
                 self.evolution["gates"].bias, self.evolution["candidate"].weight, self.evolution["candidate"].bias)
 
+    @staticmethod
+    def _history(sequence):
+        """(ids [B, T], lengths [B]) of the behaviour history, contiguous int64."""
+        seq = ops.as_index(sequence[SEQ_KEY], f"sequence[{SEQ_KEY!r}]").contiguous()
+        seq_len = ops.as_index(sequence[f"{SEQ_KEY}_length"], "sequence length").contiguous()
+        return seq, seq_len
+
     def _plan(self, dense, category, sequence, target):
         """Row layout [dense | category | target | final interest state] and the gather segments
         (dien.py:179-191,237)."""
@@ -502,8 +641,7 @@ class DIEN(EngineModule):
         lookups.append((tgt.weight, tgt_idx, col))
         q_col = col
         state_col = q_col + tgt.embedding_dim
-        seq = ops.as_index(sequence[SEQ_KEY], f"sequence[{SEQ_KEY!r}]").contiguous()
-        seq_len = ops.as_index(sequence[f"{SEQ_KEY}_length"], "sequence length").contiguous()
+        seq, seq_len = (None, None) if sequence is None else self._history(sequence)  # None: score()
         return dict(B=B, dev=dev, segs=segs, lookups=lookups, q_col=q_col, state_col=state_col,
                     width=state_col + self.gru_output_units, H=tgt.embedding_dim, seq=seq, seq_len=seq_len)
 
@@ -549,6 +687,74 @@ class DIEN(EngineModule):
             ops.dien_interest(ops._lib.fptr(row, pl["q_col"]), width, self.embeddings["feedid"].weight, pl["seq"],
                               pl["seq_len"], T, H, nh, _cell(self.custom_gru_type), self.interest_weights(),
                               ops._lib.fptr(row, pl["state_col"]), width, att, B, dev)
+        except ops._lib.RankOpsError as e:
+            _convert(e, H, nh, T)
+        run_tail(row, self._tail, self.output_layer, {}, logit, prob)
+        return (prob, logit, att) if return_attention else (prob, logit)
+
+    # ---- request-level scoring (eval only): one history per request, many candidates per history
+
+    def extract_interests(self, sequence) -> DIENInterests:
+        """The interest extractor over R behaviour histories, `sequence[SEQ_KEY]` [R, T] with its
+        `_length` [R], on rk_dien_extract: what `forward` computes before it looks at the target.
+        Returns a DIENInterests (hs [R, T, nh] and the lengths) for `score`.  It is valid only for
+        the weights it was computed with (the feedid table and gru.*): a cache of these keyed by
+        user must be dropped after a weight update.  Eval mode only, no grad_fn."""
+        check_eval(self)
+        seq, seq_len = self._history(sequence)
+        if seq.dim() != 2 or seq_len.dim() != 1 or seq_len.shape[0] != seq.shape[0]:
+            raise ValueError(f"rankops DIEN: the history must be ids [R, T] with lengths [R], got "
+                             f"{tuple(seq.shape)} and {tuple(seq_len.shape)}")
+        return DIENInterests(dien_extract_gather(self.embeddings["feedid"].weight, seq, seq_len,
+                                                 self.interest_weights()), seq_len)
+
+    def score(self, dense, category, target, interests, request_index, return_attention=False):
+        """`forward` for B candidates of R requests whose interests were extracted once:
+        `interests` is `extract_interests`' result, `request_index` [B] names each candidate's
+        request (any order), dense / category / target are per candidate as in `forward`.
+        Returns (probability, logit), plus the attention weights [B, T] on request: bit-equal to
+        `forward` with each request's history repeated for its candidates.  Launches:
+        rk_concat_gather, rk_dien_evolve into the row's state columns, the fcn tail.  Eval mode
+        only, no grad_fn."""
+        check_eval(self)
+        if not isinstance(interests, DIENInterests):
+            raise TypeError(f"rankops DIEN: interests must be what extract_interests returns, got "
+                            f"{type(interests).__name__}")
+        request_index = ops.as_index(request_index, "request_index")
+        if request_index.dim() != 1:
+            raise ValueError(f"rankops DIEN: request_index must be [B], got {tuple(request_index.shape)}")
+        hs = ops.as_f32(interests.hs, "interests.hs")
+        lens = ops.as_index(interests.keys_length, "interests.keys_length")
+        if hs.dim() != 3 or lens.dim() != 1 or lens.shape[0] != hs.shape[0]:
+            raise ValueError(f"rankops DIEN: interests must hold hs [R, T, nh] and lengths [R], got "
+                             f"{tuple(hs.shape)} and {tuple(lens.shape)}")
+        R, T, nh = hs.shape
+        dev = request_index.device
+        if request_index.shape[0] == 0:  # no candidate: nothing to launch
+            out = common.empty_rows(dev, 2)
+            return out + (torch.empty(0, T, device=dev, dtype=torch.float32),) if return_attention else out
+        pl = self._plan(dense, category, None, target)
+        B, H, width = pl["B"], pl["H"], pl["width"]
+        if request_index.shape[0] != B:
+            raise ValueError(f"rankops DIEN: request_index must name one request for each of the {B} candidates, got "
+                             f"{tuple(request_index.shape)}")
+        if nh != self.gru_output_units:
+            raise ValueError(f"rankops DIEN: interests of {nh} units, the model has {self.gru_output_units}")
+        if R == 0:
+            raise ValueError("rankops DIEN: interests holds no request, yet request_index names one per candidate")
+        if width != self._tail[0].linear.in_features:
+            raise ValueError(f"rankops DIEN: the inputs make a row of {width} columns, the first fcn layer takes "
+                             f"{self._tail[0].linear.in_features}")
+        _check_envelope(H, nh, T)
+        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        row = torch.empty(B, width, device=dev, dtype=torch.float32)
+        att = torch.empty(B, T, device=dev, dtype=torch.float32) if return_attention else None
+        ops.concat_gather(pl["segs"], B, row)
+        try:
+            ops.dien_evolve(ops._lib.fptr(row, pl["q_col"]), width, hs.detach().contiguous(), lens.contiguous(),
+                            request_index.contiguous(), H, _cell(self.custom_gru_type), self.interest_weights()[4:],
+                            ops._lib.fptr(row, pl["state_col"]), width, att, B, dev)
         except ops._lib.RankOpsError as e:
             _convert(e, H, nh, T)
         run_tail(row, self._tail, self.output_layer, {}, logit, prob)

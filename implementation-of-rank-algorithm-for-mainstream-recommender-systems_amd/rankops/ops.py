@@ -322,6 +322,39 @@ def dien_interest_train_dense(query, keys, keys_length, nh, cell_type, weights, 
                                            _lib.stream_of(keys)), "rk_dien_interest_train_dense")
 
 
+def dien_extract(key_table, seq, seq_len, T, H, nh, weights, hs, requests, device):
+    """rk_dien_extract: the interest extractor over key_table[seq] once per request -> hs [requests, T, nh]
+    (rows t >= seq_len zero); weights = (Wg, bg, Wc, bc)."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    check(lib.rk_dien_extract(ptr(key_table), key_table.shape[0], key_table.stride(0), ptr(seq), seq.stride(0), T,
+                              ptr(seq_len), requests, H, nh, *[ptr(w) for w in weights], ptr(hs),
+                              _lib.raw_stream(device)), "rk_dien_extract")
+
+
+def dien_extract_dense(keys, keys_length, nh, weights, hs):
+    """rk_dien_extract_dense: the same over keys [R, T, H] (rows 16-B aligned)."""
+    lib = _lib.load()
+    _lib.ensure_device(keys.device)
+    R, T, H = keys.shape
+    check(lib.rk_dien_extract_dense(ptr(keys), keys.stride(0), keys.stride(1), T, ptr(keys_length), R, H, nh,
+                                    *[ptr(w) for w in weights], ptr(hs), _lib.stream_of(keys)),
+          "rk_dien_extract_dense")
+
+
+def dien_evolve(query_ptr, ld_query, hs, seq_len, request_index, H, cell_type, weights, out_ptr, ld_out, att, batch,
+                device):
+    """rk_dien_evolve: attention + AGRU/AUGRU of candidate b over hs[request_index[b]] (hs [R, T, nh]
+    contiguous); query / out are strided pointers (they may lie in one row buffer), weights =
+    (A, Vg, vg, Vc, vc), att an optional [batch, T] output of the attention weights."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    R, T, nh = hs.shape
+    check(lib.rk_dien_evolve(query_ptr, ld_query, ptr(hs), R, T, ptr(seq_len), ptr(request_index), batch, H, nh,
+                             cell_type, *[ptr(w) for w in weights], out_ptr, ld_out, ptr(att),
+                             att.stride(0) if att is not None else 0, _lib.raw_stream(device)), "rk_dien_evolve")
+
+
 def dien_interest_backward(query_ptr, ld_query, keys, seq, ld_keys_b, seq_len, T, H, nh, cell_type, weights, hs, ss,
                            att, d_out_ptr, ld_dout, dquery_ptr, ld_dquery, accumulate_dquery, dkeys, batch, device,
                            seq_masked=None, d_hs=None, accumulate_dkeys=False):

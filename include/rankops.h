@@ -32,7 +32,9 @@
  *                      states, and backprop through time of the recurrence   DIEN/dien.py:314-334
  *   rk_dien_aux_loss(_dense), rk_dien_aux_loss_backward, rk_dien_interest_backward_aux  the auxiliary
  *                      loss over the extractor states and its gradients      DIEN/dien.py:256-300
- *   rk_dice_forward    Dice.forward() in eval (BatchNorm running statistics)           din.py:26-36
+ *   rk_dien_extract(_dense), rk_dien_evolve  rk_dien_interest cut in two for request-level scoring:
+ *                      the extractor once per history, attention + evolution once per candidate
+ *   rk_dice_forward   Dice.forward() in eval (BatchNorm running statistics)           din.py:26-36
  *   rk_row_l2norm_mean DIN mini-batch-aware l2 term          din.py:318-322
  *   rk_afm_forward     AFM.forward()                         afm.py:92-119
  *   rk_bst_attention   BSTTransformer scores/mask/softmax/AV bst.py:73-84 (mask from seq_length, bst.py:228-229)
@@ -304,6 +306,42 @@ int rk_dien_interest_train_dense(const float* query, int64_t ld_query, const flo
                                  const float* bc, const float* A, const float* Vg, const float* vg,
                                  const float* Vc, const float* vc, float* out, int64_t ld_out,
                                  float* att_out, int64_t ld_att, float* hs, float* ss, void* stream);
+
+/* Request-level scoring: rk_dien_interest cut in two, for a ranking request of one history and many
+ * candidates.  The interest extractor (the GRU over the history) does not read the query, so it
+ * runs once per request; attention and the AGRU / AUGRU evolution run once per candidate.
+ * Inference only.  Same envelope, validation and determinism as rk_dien_interest.
+ *
+ * rk_dien_extract: for each of `requests` histories (key_table, seq [requests, ld_seq], seq_len
+ *   [requests], as rk_dien_interest takes them) writes the extractor states hs [requests, T, nh]
+ *   (contiguous, 16-B aligned), rows t >= seq_len[r] zero: bit-equal to the hs of
+ *   rk_dien_interest_train on the same histories.  ids at t >= seq_len[r] are never read; an
+ *   out-of-range id reads a zero row and raises RK_FLAG_INDEX_OOB.  requests == 0: RK_OK, no launch.
+ * rk_dien_extract_dense: the same over keys (row t of request r at keys + r*ld_keys_b + t*ld_keys_t).
+ * hs is valid only for the weights Wg, bg, Wc, bc it was computed with.                           */
+int rk_dien_extract(const float* key_table, int64_t key_rows, int64_t ld_key, const int64_t* seq,
+                    int64_t ld_seq, int32_t T, const int64_t* seq_len, int64_t requests, int32_t H,
+                    int32_t nh, const float* Wg, const float* bg, const float* Wc, const float* bc,
+                    float* hs, void* stream);
+int rk_dien_extract_dense(const float* keys, int64_t ld_keys_b, int64_t ld_keys_t, int32_t T,
+                          const int64_t* keys_length, int64_t requests, int32_t H, int32_t nh,
+                          const float* Wg, const float* bg, const float* Wc, const float* bc,
+                          float* hs, void* stream);
+
+/* rk_dien_evolve: candidate b (query row at query + b*ld_query) belongs to request
+ *   r = request_index[b] (any order; a request may have no candidate or many) and gets the
+ *   attention of hs[r] (rk_dien_extract's, with its seq_len [requests]) against A query[b], the
+ *   masked softmax and the AGRU / AUGRU evolution: out[b, 0:nh] at out + b*ld_out and, when
+ *   att_out != NULL, att_out[b, 0:T], both bit-equal to rk_dien_interest on candidate b with the
+ *   history of request r.  Rows of hs at t >= seq_len[r] are never read.  A request_index outside
+ *   [0, requests) is scored as an empty history (zero state, uniform attention) and raises
+ *   RK_FLAG_INDEX_OOB.  query and out may lie in one row buffer.  batch == 0 or requests == 0:
+ *   RK_OK, no launch, nothing written.                                                            */
+int rk_dien_evolve(const float* query, int64_t ld_query, const float* hs, int64_t requests, int32_t T,
+                   const int64_t* seq_len, const int64_t* request_index, int64_t batch, int32_t H,
+                   int32_t nh, int32_t cell_type, const float* A, const float* Vg, const float* vg,
+                   const float* Vc, const float* vc, float* out, int64_t ld_out, float* att_out,
+                   int64_t ld_att, void* stream);
 
 /* Backward of the interest recurrence (backprop through time, t = seq_len-1 ... 0) given
  * d_out[b, 0:nh] = dL/d(out) at d_out + b*ld_dout and the forward's inputs, hs, ss and att:
