@@ -20,7 +20,7 @@
 // read).  h_t overwrites row t of that buffer, the scores and the softmax run over it once the
 // first pass is done, and the second pass reads h_t and a_t back one step ahead again.
 // No cross-wave traffic, no atomics: results are bit-reproducible, and the table form and the
-// dense form run the same code after the gather.
+// dense form run the same code after the gather.  The phases themselves are in dien_cell.h.
 #include "dien_cell.h"
 
 namespace rk {
@@ -36,167 +36,24 @@ __global__ __launch_bounds__(64) void dien_interest_kernel(
     float* __restrict__ att_out, int64_t ld_att, uint32_t* flags, float* __restrict__ hs_out,
     float* __restrict__ ss_out) {
   constexpr int RW = H > NH ? H : NH;  // LDS row: x_t first, h_t after step t
-  constexpr int NG = NH / 8;
   extern __shared__ __attribute__((aligned(16))) float dien_sm[];
-  const int lane = threadIdx.x, p = lane & 15, s = lane >> 4, j = p % NH, half = p >> 3;
+  const int lane = threadIdx.x, p = lane & 15, s = lane >> 4;
   const int64_t b = (int64_t)blockIdx.x * kDienSamples + s;
   const bool live = b < batch;
   float* rows = dien_sm + (size_t)s * sample_stride;  // [T][RW]
   float* att = rows + T * RW;                          // [T]: scores, then attention weights
   float* wea = att + ((T + 3) & ~3);                   // [NH]: A . e_target
-  int len = 0;
-  if (live) {
-    const int64_t l = seq_len[b];
-    len = l < 0 ? 0 : (l > T ? T : (int)l);
-  }
+  const int len = live ? dien_len(seq_len, b, T) : 0;
 
-  // ---- the sample's len history rows into LDS: lane p resolves position t0 + p, then the 16
-  // lanes copy the 16 rows as float4 chunks (control flow is uniform over a sample's row)
-  constexpr int C = H / 4;
-  for (int t0 = 0; t0 < len; t0 += 16) {
-    long long off = -1;
-    const int t = t0 + p;
-    if (t < len) {
-      if (seq) {
-        const int64_t r = seq[b * ld_seq + t];
-        if (r >= 0 && r < key_rows)
-          off = r * ld_key;
-        else
-          flag_oob(flags);
-      } else {
-        off = b * ld_kb + (int64_t)t * ld_key;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-      const int e = i * 16 + p, rr = e / C, cc = e % C;
-      const long long o = __shfl(off, rr, 16);
-      if (t0 + rr < len) {
-        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (o >= 0) v = *reinterpret_cast<const f32x4*>(key_table + o + 4 * cc);
-        *reinterpret_cast<f32x4*>(rows + (t0 + rr) * RW + 4 * cc) = v;
-      }
-    }
-  }
-
-  // ---- A . e_target, one unit per lane
-  {
-    float a = 0.f;
-    if (live) {
-      const float* q = query + b * ld_query;
-#pragma unroll
-      for (int i = 0; i < H; ++i) a = fmaf(w.A[j * H + i], q[i], a);
-    }
-    if (p < NH) wea[j] = a;
-  }
+  dien_gather_rows<H, RW>(key_table, key_rows, ld_key, seq, ld_seq, ld_kb, b, len, p, flags, rows);
+  dien_project_query<H, NH>(w.A, query, ld_query, b, live, p, wea);
   __syncthreads();
-
-  // ---- pass 1: interest extractor
-  {
-    DienCell<H, NH> g;
-    g.load(w.Wg, w.bg, w.Wc, w.bc, p);
-    float h = 0.f, gi[NG], ci = 0.f;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) gi[i] = 0.f;
-    if (len > 0) g.input(rows, gi, ci);
-    for (int t = 0; t < len; ++t) {
-      float gn[NG], cn = 0.f;
-#pragma unroll
-      for (int i = 0; i < NG; ++i) gn[i] = 0.f;
-      if (t + 1 < len) g.input(rows + (t + 1) * RW, gn, cn);
-      float u, c;
-      g.step(gi, ci, h, half, u, c);
-      h = fmaf(u, h - c, c);  // u*h + (1-u)*c
-      if (p < NH) rows[t * RW + j] = h;
-      if constexpr (SAVE) {
-        if (p < NH) hs_out[(b * T + t) * NH + j] = h;
-      }
-#pragma unroll
-      for (int i = 0; i < NG; ++i) gi[i] = gn[i];
-      ci = cn;
-    }
-  }
+  dien_extract_pass<H, NH, RW, true, SAVE>(w.Wg, w.bg, w.Wc, w.bc, rows, len, p, hs_out, b, T);
   __syncthreads();
-
-  // ---- scores and the softmax over all T positions, lane p takes t = p, p + 16, ...
-  {
-    float wv[NH];
-#pragma unroll
-    for (int c4 = 0; c4 < NH / 4; ++c4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wea + 4 * c4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) wv[4 * c4 + e] = v[e];
-    }
-    const float pad = -4294967296.0f;  // (-2**32 + 1) rounded to fp32, dien.py:216
-    float m = pad;
-    for (int t = p; t < T; t += 16) {
-      float sc = pad;
-      if (t < len) {
-        sc = 0.f;
-#pragma unroll
-        for (int c4 = 0; c4 < NH / 4; ++c4) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(rows + t * RW + 4 * c4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc = fmaf(v[e], wv[4 * c4 + e], sc);
-        }
-      }
-      att[t] = sc;
-      m = fmaxf(m, sc);
-    }
-    m = row16_max(m);
-    float sum = 0.f;
-    for (int t = p; t < T; t += 16) {
-      const float e = expf(att[t] - m);
-      att[t] = e;
-      sum += e;
-    }
-    sum = row16_sum(sum);
-    const float inv = 1.0f / sum;
-    for (int t = p; t < T; t += 16) {
-      const float a = att[t] * inv;
-      att[t] = a;
-      if (att_out && live) att_out[b * ld_att + t] = a;
-    }
-  }
+  dien_attention<NH, RW>(rows, wea, att, T, len, p, att_out, ld_att, b, live);
   __syncthreads();
-
-  // ---- pass 2: interest evolution over h_t, t < len
-  {
-    DienCell<NH, NH> g;
-    g.load(w.Vg, w.vg, w.Vc, w.vc, p);
-    float st = 0.f, gi[NG], ci = 0.f, a = 0.f;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) gi[i] = 0.f;
-    if (len > 0) {
-      g.input(rows, gi, ci);
-      a = att[0];
-    }
-    for (int t = 0; t < len; ++t) {
-      float gn[NG], cn = 0.f, an = 0.f;
-#pragma unroll
-      for (int i = 0; i < NG; ++i) gn[i] = 0.f;
-      if (t + 1 < len) {
-        g.input(rows + (t + 1) * RW, gn, cn);
-        an = att[t + 1];
-      }
-      float u, c;
-      g.step(gi, ci, st, half, u, c);
-      if (cell_type == 0) {
-        st = fmaf(a, c - st, st);  // (1-a)*s + a*c
-      } else {
-        const float u2 = fmaf(-a, u, u);  // (1-a)*u
-        st = fmaf(u2, st - c, c);         // u'*s + (1-u')*c
-      }
-      if constexpr (SAVE) {
-        if (p < NH) ss_out[(b * T + t) * NH + j] = st;
-      }
-#pragma unroll
-      for (int i = 0; i < NG; ++i) gi[i] = gn[i];
-      ci = cn;
-      a = an;
-    }
-    if (live && p < NH) out[b * ld_out + j] = st;
-  }
+  dien_evolve_pass<NH, RW, SAVE>(w.Vg, w.vg, w.Vc, w.vc, rows, att, len, p, cell_type, ss_out, b, T, out, ld_out,
+                                 live);
   if constexpr (SAVE) {
     if (live)
       for (int e = len * NH + p; e < T * NH; e += 16) {
@@ -204,14 +61,6 @@ __global__ __launch_bounds__(64) void dien_interest_kernel(
         ss_out[b * T * NH + e] = 0.f;
       }
   }
-}
-
-// Floats of LDS per sample: the rows, the scores and A . e_target, padded so that the four
-// samples of a wave start 16 banks apart (their broadcast float4 row reads never collide).
-static int dien_sample_stride(int T, int H, int NH) {
-  const int rw = H > NH ? H : NH;
-  const int base = T * rw + ((T + 3) & ~3) + 16;
-  return base + ((16 - base % 64) + 64) % 64;
 }
 
 }  // namespace rk
@@ -229,41 +78,19 @@ static int launch_dien(const float* query, int64_t ld_query, const float* key_ta
     return fail(RK_ERR_INVALID, "%s: null pointer", who);
   if (T <= 0 || batch < 0 || H <= 0 || nh <= 0 || ld_query < H || ld_out < nh || ld_key < H || (att_out && ld_att < T))
     return fail(RK_ERR_INVALID, "%s: bad shape T=%d H=%d nh=%d", who, T, H, nh);
-  if (cell_type != 0 && cell_type != 1)
-    return fail(RK_ERR_INVALID, "%s: cell_type %d is neither 0 (AGRU) nor 1 (AUGRU)", who, cell_type);
-  if ((H != 8 && H != 16 && H != 32) || (nh != 8 && nh != 16) || T > 256)
-    return fail(RK_ERR_UNSUPPORTED, "%s: H=%d nh=%d T=%d outside the envelope H in {8,16,32}, nh in {8,16}, T <= 256",
-                who, H, nh, T);
-  if (ld_key % 4 != 0 || ld_kb % 4 != 0 || ((uintptr_t)key_table & 15u))
-    return fail(RK_ERR_UNSUPPORTED, "%s: history rows must be 16-B aligned", who);
+  if (int rc = dien_check_cell(who, cell_type)) return rc;
+  if (int rc = dien_check_envelope(who, H, nh, T)) return rc;
+  if (int rc = dien_check_history_rows(who, key_table, ld_key, ld_kb)) return rc;
   if (batch == 0) return RK_OK;
-  const int stride = dien_sample_stride(T, H, nh);
+  // floats of LDS per sample: the rows, the scores and A . e_target
+  const int stride = dien_padded_stride(T * (H > nh ? H : nh) + ((T + 3) & ~3) + 16);
   const size_t shm = (size_t)kDienSamples * stride * sizeof(float);
   const unsigned blocks = (unsigned)((batch + kDienSamples - 1) / kDienSamples);
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t* fl = device_flags();
-#define RK_DIEN_LAUNCH(HH, NN, SV)                                                                            \
-  if (shm > 64 * 1024) raise_lds_limit((const void*)dien_interest_kernel<HH, NN, SV>, (int)shm);              \
-  dien_interest_kernel<HH, NN, SV><<<blocks, 64, shm, st>>>(query, ld_query, key_table, key_rows, ld_key, seq, \
-                                                            ld_seq, ld_kb, T, seq_len, batch, w, cell_type,   \
-                                                            stride, out, ld_out, att_out, ld_att, fl, hs_out, \
-                                                            ss_out);
-#define RK_DIEN_CASE(HH, NN)                                                                                  \
-  if (H == HH && nh == NN) {                                                                                  \
-    if (save) {                                                                                               \
-      RK_DIEN_LAUNCH(HH, NN, true)                                                                            \
-    } else {                                                                                                  \
-      RK_DIEN_LAUNCH(HH, NN, false)                                                                           \
-    }                                                                                                         \
-  }
-  RK_DIEN_CASE(8, 8)
-  RK_DIEN_CASE(16, 8)
-  RK_DIEN_CASE(32, 8)
-  RK_DIEN_CASE(8, 16)
-  RK_DIEN_CASE(16, 16)
-  RK_DIEN_CASE(32, 16)
-#undef RK_DIEN_CASE
-#undef RK_DIEN_LAUNCH
+  dien_launch(
+      H, nh,
+      [save](auto s) { return save ? dien_interest_kernel<s.H, s.NH, true> : dien_interest_kernel<s.H, s.NH, false>; },
+      blocks, shm, (hipStream_t)stream, query, ld_query, key_table, key_rows, ld_key, seq, ld_seq, ld_kb, T, seq_len,
+      batch, w, cell_type, stride, out, ld_out, att_out, ld_att, device_flags(), hs_out, ss_out);
   return check_launch(who);
 }
 

@@ -127,11 +127,7 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
   float* wea = att + T4;          // [NH]: A . e_target
   float* dwl = wea + 16;          // [NH]: d(A . e_target)
   long long* offs = reinterpret_cast<long long*>(dwl + 16);  // [T]: element offset of key row t, -1: zero row
-  int len = 0;
-  if (live) {
-    const int64_t l = seq_len[b];
-    len = l < 0 ? 0 : (l > T ? T : (int)l);
-  }
+  const int len = live ? dien_len(seq_len, b, T) : 0;
   if (lane < 32) zero_row[lane] = 0.f;
   for (int t = p; t < len; t += 16) {
     long long off = -1;
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(64) void dien_interest_backward_kernel(
     offs[t] = off;
     att[t] = att_in[b * ld_att + t];
   }
-  {
+  {  // dien_project_query, restated: the call moves <8,16> from 32 to 30 AGPRs, and these figures are pinned
     float a = 0.f;
     if (live) {
       const float* q = query + b * ld_query;
@@ -335,13 +331,6 @@ __global__ void dien_unpack_wgrad_kernel(const float* __restrict__ P, const floa
   }
 }
 
-// Floats of LDS per sample (see the kernel's carve-up), padded so the four samples start 16 banks apart.
-static int dien_bwd_sample_stride(int T, int NH) {
-  const int t4 = (T + 3) & ~3;
-  const int base = T * NH + 2 * t4 + 32 + 2 * t4;
-  return base + ((16 - base % 64) + 64) % 64;
-}
-
 static int64_t align4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
 struct DienBwdLayout {
@@ -395,11 +384,8 @@ RK_API int rk_dien_interest_backward_aux(const float* query, int64_t ld_query, c
       ld_att < T || (seq && (key_rows <= 0 || ld_seq < T)) ||
       (!seq && ld_keys_b < (int64_t)T * ld_key && batch > 1))
     return fail(RK_ERR_INVALID, "%s: bad shape T=%d H=%d nh=%d", who, T, H, nh);
-  if (cell_type != 0 && cell_type != 1)
-    return fail(RK_ERR_INVALID, "%s: cell_type %d is neither 0 (AGRU) nor 1 (AUGRU)", who, cell_type);
-  if ((H != 8 && H != 16 && H != 32) || (nh != 8 && nh != 16) || T > 256)
-    return fail(RK_ERR_UNSUPPORTED, "%s: H=%d nh=%d T=%d outside the envelope H in {8,16,32}, nh in {8,16}, T <= 256",
-                who, H, nh, T);
+  if (int rc = dien_check_cell(who, cell_type)) return rc;
+  if (int rc = dien_check_envelope(who, H, nh, T)) return rc;
   if (ld_key % 4 != 0 || ld_keys_b % 4 != 0 || (((uintptr_t)keys | (uintptr_t)hs | (uintptr_t)ss) & 15u))
     return fail(RK_ERR_UNSUPPORTED, "%s: history rows and saved states must be 16-B aligned", who);
   hipStream_t st = (hipStream_t)stream;
@@ -423,23 +409,15 @@ RK_API int rk_dien_interest_backward_aux(const float* query, int64_t ld_query, c
   const DienWeights w{Wg, bg, Wc, bc, A, Vg, vg, Vc, vc};
   float *g1 = workspace + l.g1, *o1 = workspace + l.o1, *g2 = workspace + l.g2, *o2 = workspace + l.o2;
   const DienGrads gr{dquery, g1, o1, g2, o2, workspace + l.dwea, workspace + l.qc, seq_masked};
-  const int stride = dien_bwd_sample_stride(T, nh);
+  // floats of LDS per sample: dh, da and att, wea and dwl, offs (see the kernel's carve-up)
+  const int t4 = (T + 3) & ~3;
+  const int stride = dien_padded_stride(T * nh + 2 * t4 + 32 + 2 * t4);
   const size_t shm = (size_t)(32 + kDienSamples * stride) * sizeof(float);
   const unsigned blocks = (unsigned)((batch + kDienSamples - 1) / kDienSamples);
-#define RK_DIEN_CASE(HH, NN)                                                                                   \
-  if (H == HH && nh == NN) {                                                                                   \
-    if (shm > 64 * 1024) raise_lds_limit((const void*)dien_interest_backward_kernel<HH, NN>, (int)shm);        \
-    dien_interest_backward_kernel<HH, NN><<<blocks, 64, shm, st>>>(                                            \
-        query, ld_query, keys, key_rows, ld_key, seq, ld_seq, ld_keys_b, T, seq_len, batch, w, cell_type,      \
-        stride, hs, ss, att, ld_att, d_out, ld_dout, ld_dquery, accumulate_dquery, gr, d_hs);                  \
-  }
-  RK_DIEN_CASE(8, 8)
-  RK_DIEN_CASE(16, 8)
-  RK_DIEN_CASE(32, 8)
-  RK_DIEN_CASE(8, 16)
-  RK_DIEN_CASE(16, 16)
-  RK_DIEN_CASE(32, 16)
-#undef RK_DIEN_CASE
+  dien_launch(
+      H, nh, [](auto s) { return dien_interest_backward_kernel<s.H, s.NH>; }, blocks, shm, st, query, ld_query, keys,
+      key_rows, ld_key, seq, ld_seq, ld_keys_b, T, seq_len, batch, w, cell_type, stride, hs, ss, att, ld_att, d_out,
+      ld_dout, ld_dquery, accumulate_dquery, gr, d_hs);
   int rc = check_launch(who);
   if (rc != RK_OK) return rc;
   const int64_t R = batch * T;
