@@ -17,6 +17,8 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the
 reference's Dataset bucketing + collate with C++ column bucketing and one H2D copy per batch;
 `rankops.metrics` (EvalAccumulator, roc_auc) computes evaluate()'s loss / accuracy / AUC on the GPU;
+`rankops.ranking` (topk_segments, topk_per_request, grouped_auc; DIEN.rank) keeps the best k candidates
+of each request and computes the per-user AUC / GAUC there too;
 `rankops.train` holds the HIP backward (train-mode forwards return autograd-connected outputs)
 and `rankops.Adam`, a one-launch torch.optim.Adam; with `sparse_grad=True` a model's tables get
 sparse gradients and `rankops.SparseAdam` (torch.optim.SparseAdam / LazyAdam) updates only their rows.
@@ -36,6 +38,7 @@ from .dien import (DIEN, DIENInterests, dien_aux_loss, dien_aux_loss_gather, die
 from .fwfm import FwFM  # noqa: F401
 from .loader import BatchAssembler, Vocabulary, label_encode, wechat_vocabularies  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
+from .ranking import GroupedAUC, GroupTable, RequestTopK, grouped_auc, topk_per_request, topk_segments  # noqa: F401
 from .train import Adam, SparseAdam  # noqa: F401
 
 __all__ = [
@@ -44,5 +47,5 @@ __all__ = [
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
     "dien_aux_loss", "dien_aux_loss_gather", "dien_extract", "dien_extract_gather", "dien_evolve", "DIENInterests",
-    "SparseAdam",
+    "SparseAdam", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
 ]

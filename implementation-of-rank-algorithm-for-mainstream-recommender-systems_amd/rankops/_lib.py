@@ -22,7 +22,7 @@ RK_ERR_UNSUPPORTED = 4  # include/rankops.h
 RK_FLAG_INDEX_OOB = 1
 RK_ACT_NONE, RK_ACT_RELU, RK_ACT_LEAKY, RK_ACT_DICE, RK_ACT_PRELU = 0, 1, 2, 3, 4
 RK_MAX_SEGMENTS = 64
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 
 class Segment(ctypes.Structure):
@@ -385,6 +385,16 @@ SIGNATURES = {
     "rk_eval_batch": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_int32, c_void_p, c_void_p, c_void_p]),
     "rk_auc_workspace_size": (ctypes.c_int, [c_int64, POINTER(c_int64)]),
     "rk_auc": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rk_topk_segments": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "rk_topk_by_request_workspace_size": (ctypes.c_int, [c_int64, c_int64, POINTER(c_int64)]),
+    "rk_topk_segments_sorted": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int64, c_void_p]),
+    "rk_topk_by_request": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int64, c_void_p]),
+    "rk_grouped_auc_workspace_size": (ctypes.c_int, [c_int64, POINTER(c_int64)]),
+    "rk_grouped_auc": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rk_linear_tiled": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, _MLP_P, c_void_p, c_int64, c_void_p]),
     "rk_shard_pack_indices": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     "rk_shard_gather_rows": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64,

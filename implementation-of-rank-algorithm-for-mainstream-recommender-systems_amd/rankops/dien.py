@@ -759,3 +759,13 @@ class DIEN(EngineModule):
             _convert(e, H, nh, T)
         run_tail(row, self._tail, self.output_layer, {}, logit, prob)
         return (prob, logit, att) if return_attention else (prob, logit)
+
+    def rank(self, dense, category, target, interests, request_index, k):
+        """`score`, then the best k candidates of each request: (RequestTopK, probability, logit),
+        the top-K's indices being rows of the candidate batch.  Ranked on the logit: fp32
+        probabilities saturate into ties where the logits still differ.  The request count is
+        `interests`'; a request without candidates gets counts 0.  Eval mode only, as `score`."""
+        from .ranking import topk_per_request
+        prob, logit = self.score(dense, category, target, interests, request_index)
+        top = topk_per_request(logit, ops.as_index(request_index, "request_index"), int(interests.hs.shape[0]), k)
+        return top, prob, logit

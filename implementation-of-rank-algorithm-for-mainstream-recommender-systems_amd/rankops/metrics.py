@@ -15,6 +15,9 @@ and integer counts.  One host synchronisation per evaluation, at `result()`.
         acc.add(prob, label, logits=logit)
     avg_loss, accuracy, auc = acc.result()
 
+With `acc.add(..., groups=batch_userid)` on every batch, `acc.grouped_auc()` also gives the
+per-user AUC's impression-weighted mean (GAUC) over the same rows, from `rk_grouped_auc`.
+
 The loss is the one each script's criterion computes: BCEWithLogitsLoss on the logits for
 dcn/bst/deepcrossing (dcn.py:274,229), BCELoss on the probabilities for din/deepfm/afm/fwfm
 (din.py:434,379), DIN adding its per-batch l2_reg (din.py:380) — pass it as `extra`.
@@ -71,11 +74,14 @@ class EvalAccumulator:
         self._acc = torch.zeros(3, dtype=torch.float64, device=self.device)  # [loss sum | uint64 | uint64]
         self._probs = []
         self._labels = []
+        self._groups = []
         self._n = 0
 
-    def add(self, probs: torch.Tensor, labels: torch.Tensor, logits: torch.Tensor = None, extra=None):
+    def add(self, probs: torch.Tensor, labels: torch.Tensor, logits: torch.Tensor = None, extra=None, *,
+            groups: torch.Tensor = None):
         """One batch: probabilities, labels, the logits (needed for BCEWithLogitsLoss) and an
-        optional per-batch scalar added to the batch loss (DIN's l2_reg)."""
+        optional per-batch scalar added to the batch loss (DIN's l2_reg).  `groups` (keyword only):
+        the batch's group ids, one per row (the user ids), kept for `grouped_auc()`."""
         lib = _lib.load()
         p = probs.detach().reshape(-1).to(torch.float32).contiguous()
         y = labels.detach().reshape(-1).to(torch.float32).contiguous()
@@ -83,6 +89,11 @@ class EvalAccumulator:
             raise RuntimeError(f"EvalAccumulator.add: tensors must be on {self.device}")
         if p.numel() != y.numel() or p.numel() == 0:
             raise ValueError("EvalAccumulator.add: probs and labels must have the same non-zero size")
+        if groups is not None:
+            if not isinstance(groups, torch.Tensor) or groups.device != self.device or groups.numel() != p.numel():
+                raise ValueError(f"EvalAccumulator.add: groups must be {p.numel()} ids on {self.device}")
+            if groups.dtype.is_floating_point or groups.dtype == torch.bool:
+                raise TypeError(f"EvalAccumulator.add: groups must be an integer tensor, got {groups.dtype}")
         x = None
         if self.loss_kind == 0:
             if logits is None:
@@ -99,6 +110,9 @@ class EvalAccumulator:
         self._keep = (x, e)  # alive until the kernel has read them (stream order)
         self._probs.append(p)
         self._labels.append(y)
+        if groups is not None:
+            # a copy: the ids are a model input, and a loader may refill its batch buffers in place
+            self._groups.append(groups.detach().reshape(-1).to(torch.int64, copy=True))
         self._n += p.numel()
 
     def result(self):
@@ -110,3 +124,16 @@ class EvalAccumulator:
         counts = acc.view(torch.int64)
         loss_sum, correct, batches = float(acc[0]), int(counts[1]), int(counts[2])
         return loss_sum / batches, correct / self._n, float(auc)
+
+    def grouped_auc(self, return_groups: bool = False):
+        """rankops.grouped_auc over every batch added so far, the probabilities grouped by the
+        `groups=` each `add` was given: GroupedAUC(gauc, valid_groups, valid_rows) as device
+        tensors (no synchronisation), with the per-group table on request."""
+        from .ranking import grouped_auc
+        if not self._n:
+            raise ValueError("EvalAccumulator: no batches")
+        if len(self._groups) != len(self._probs):
+            raise ValueError(f"EvalAccumulator.grouped_auc: {len(self._probs) - len(self._groups)} of "
+                             f"{len(self._probs)} batches were added without groups=")
+        return grouped_auc(torch.cat(self._probs), torch.cat(self._labels), torch.cat(self._groups),
+                           return_groups=return_groups)

@@ -46,6 +46,8 @@
  *                      first deep layer (the deep input never reaches HBM)  deepfm.py:100-112,122-142
  *   rk_deepfm_forward  DeepFM.forward() in one launch at configs[1]'s shape   deepfm.py:121-151
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
+ *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
+ *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
  *   rk_fwfm_forward    FwFM.forward()                        fwfm.py:114-139
  *   training (loss.backward() + optimizer.step() of the train() loops, dcn.py:196-201):
  *   rk_gemm            the Linear backward GEMMs (dX = dZ W, dW = dZ^T X, db)   dcn.py:147-150
@@ -91,7 +93,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 1
+#define RK_ABI_VERSION 2
 
 #define RK_OK 0
 #define RK_ERR_INVALID 1     /* bad argument (shape, null pointer, limit) */
@@ -1077,6 +1079,50 @@ int rk_eval_batch(const float* logits, const float* probs, const float* labels, 
 int rk_auc_workspace_size(int64_t n, int64_t* bytes);
 int rk_auc(const float* scores, const float* labels, int64_t n, void* workspace, int64_t ws_bytes,
            double* out, void* stream);
+
+/* ---- per-request ranking: segmented top-K and grouped AUC (ranking.hip) ----
+ * Top-K order, both forms: within a request by score descending, -0.0 == +0.0, NaN below every
+ * number (-inf included), ties by the lower row.  values [R, k] float (the original bits of
+ * scores[indices]), indices [R, k] int64 (rows of scores), counts [R] int64 = min(k, candidates of
+ * r); slots at or past counts[r] hold -inf / -1.  1 <= k <= 1024, n <= 2^32 - 2.  No allocation, no
+ * synchronisation, capturable; R == 0 returns RK_OK without a launch.
+ * rk_topk_segments: request r owns the contiguous rows offsets[r] .. offsets[r+1] of scores[n]
+ *   (offsets non-decreasing).  One launch, one wave per request, the running best kept in
+ *   registers; k <= RK_TOPK_SEGMENT_MAX_K (else RK_ERR_UNSUPPORTED: use rk_topk_segments_sorted).
+ *   An offset outside [0, n] is clamped and raises RK_FLAG_INDEX_OOB: no row past n is read.
+ * rk_topk_segments_sorted: the same result for every k by the sort path of rk_topk_by_request;
+ *   rows that no segment covers are left out.
+ * rk_topk_by_request: row b belongs to request request_index[b], in any order.  A stable radix
+ *   sort of (request, inverted order-preserving score bits) with the row as value, over the bits
+ *   R needs; then the first k rows of each request.  A request_index outside [0, R) is left out
+ *   and raises RK_FLAG_INDEX_OOB.  workspace: rk_topk_by_request_workspace_size(n, R) bytes (for
+ *   both sorted entry points).                                                                  */
+#define RK_TOPK_MAX_K 1024
+#define RK_TOPK_SEGMENT_MAX_K 64
+int rk_topk_segments(const float* scores, int64_t n, const int64_t* offsets, int64_t R, int32_t k,
+                     float* values, int64_t* indices, int64_t* counts, void* stream);
+int rk_topk_by_request_workspace_size(int64_t n, int64_t R, int64_t* bytes);
+int rk_topk_segments_sorted(const float* scores, int64_t n, const int64_t* offsets, int64_t R, int32_t k,
+                            float* values, int64_t* indices, int64_t* counts, void* workspace,
+                            int64_t ws_bytes, void* stream);
+int rk_topk_by_request(const float* scores, const int64_t* request_index, int64_t n, int64_t R,
+                       int32_t k, float* values, int64_t* indices, int64_t* counts, void* workspace,
+                       int64_t ws_bytes, void* stream);
+/* AUC per group and its impression-weighted mean (GAUC, the DIN / DIEN papers' metric), rk_auc's
+ * integer scheme per group: sort by (group, score) with -0.0 == +0.0, reduce equal pairs to
+ * (positives, negatives), negatives-before by a scan that restarts at each group,
+ * 2U_g = sum pos (2 neg_before + neg) in int64.  Outputs, one row per group present in ascending
+ * group id (arrays of n entries, the first *n_groups written): group_ids, two_u, pos, neg (int64);
+ * n_groups: device int64.  summary (3 x 8 bytes): [0] double GAUC = sum_g n_g U_g / (P_g N_g) /
+ * sum_g n_g over the groups with both classes, n_g = P_g + N_g, summed in a fixed order (no
+ * floating atomics: the same bits for any order of the rows); NaN when no group is valid or a valid
+ * group holds a NaN score; [1] int64 number of valid groups; [2] int64 their row total.  A group
+ * id outside [0, 2^31) is left out and raises RK_FLAG_INDEX_OOB.  1 <= n <= 2^32 - 2.
+ * workspace: rk_grouped_auc_workspace_size(n) bytes.                                            */
+int rk_grouped_auc_workspace_size(int64_t n, int64_t* bytes);
+int rk_grouped_auc(const float* scores, const float* labels, const int64_t* groups, int64_t n,
+                   void* workspace, int64_t ws_bytes, void* summary, int64_t* group_ids, int64_t* two_u,
+                   int64_t* pos, int64_t* neg, int64_t* n_groups, void* stream);
 
 int rk_bn_fold(const float* mean, const float* var, const float* weight, const float* bias,
                float eps, int32_t n, float* scale, float* shift, void* stream);
