@@ -8,6 +8,8 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
     DIN, Dice, din_attention               algorithm/DIN/din.py
     DIEN, dien_interest, dien_aux_loss     algorithm/DIEN/dien.py (with the auxiliary loss)
     dien_extract, dien_evolve, DIEN.score  the same split for one history and many candidates
+    DIEN.forward / DIEN.prepare            the whole eval forward in one launch (rk_dien_forward), bound to
+                                           its inputs by prepare() as DIN.prepare does
     AFM, create_feature_columns            algorithm/AFM/afm.py
     DeepCrossingModel, residual_unit       algorithm/DeepCrossing/deepcrossing.py
     BSTModel, BSTTransformer               algorithm/BST/bst.py

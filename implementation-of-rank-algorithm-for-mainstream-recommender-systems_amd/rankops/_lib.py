@@ -196,6 +196,20 @@ SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32]
         + [c_void_p] * 5 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
     ),
+    "rk_dien_forward": (
+        ctypes.c_int,
+        [_SEG_P, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32,
+         c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 9
+        + [_MLP_P, c_int32, _EPI_P, c_void_p, c_int64, c_void_p],
+    ),
+    "rk_dien_forward_plan": (
+        ctypes.c_int,
+        [_SEG_P, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32,
+         c_void_p, c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 9
+        + [_MLP_P, c_int32, _EPI_P, c_void_p, c_int64, POINTER(c_void_p)],
+    ),
+    "rk_dien_plan_launch": (ctypes.c_int, [c_void_p, c_void_p]),
+    "rk_dien_plan_destroy": (None, [c_void_p]),
     "rk_dien_interest_backward_workspace_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
     "rk_dien_interest_backward": (
         ctypes.c_int,

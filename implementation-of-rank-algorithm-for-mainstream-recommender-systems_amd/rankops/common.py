@@ -383,6 +383,10 @@ EAGER_CACHE = True  # eval forwards reuse their marshalled launches (EagerCalls)
 FUSED_MLP = True  # one rk_mlp_forward launch per tail when the widths fit (see fused_mlp_fits)
 FUSED_GATHER_MLP = True  # DeepCrossing: the row gather inside that launch (rk_mlp_forward_gather)
 FUSED_DIN = True  # DIN: gather + attention + fcn tail + head in one rk_din_forward launch
+FUSED_DIEN = True  # DIEN: gather + interest recurrence + fcn tail + head in one rk_dien_forward launch
+# ... while the batch is at most this many 16-sample workgroups per CU (B 4096 on 256 CUs): one more
+# workgroup than that and the three launches are faster again; None: at any batch
+FUSED_DIEN_WG_PER_CU = 1
 FUSED_BST = True  # BST: all transformer blocks + pooling in one rk_bst_forward_blocks launch
 FUSED_BST_FWD = True  # BST at d_model 16: row gather + blocks + pooling + DNN tail in one rk_bst_small_forward
 # A first layer this wide runs as its own 2D-tiled GEMM (rk_linear_tiled) before the fused tail:

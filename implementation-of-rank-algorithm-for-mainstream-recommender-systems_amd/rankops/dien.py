@@ -28,11 +28,15 @@ with the reset rows first, Linear(H+nh, nh)); `attention_project_matrix` [nh, H]
 `fcn.*`, `output_layer.*` as in DIN.  Initialisation as TF does it: Glorot-uniform kernels, gate
 biases 1 (custom_grucell.py:66-68), other biases 0.
 
-Launches: rk_concat_gather builds [dense | category | target | .] in one row buffer,
-rk_dien_interest (history gather, GRU, attention scores, masked softmax, AGRU / AUGRU) writes the
-final interest state into the row's last nh columns, and the fcn stack runs as DIN's tail.  The row
-order is DIN's (dense in the given order, category in ModuleDict order), not input_layer's
-alphabetical one: there is no TF checkpoint this could ever load.
+Launches: the eval forward is one rk_dien_forward launch (common.FUSED_DIEN) inside its envelope
+(gru_output_units 8, hidden units [512, 256, 128], a history short enough for 16 samples' rows in
+LDS): the row [dense | category | target | .] is gathered into LDS, the interest recurrence (history
+gather, GRU, attention scores, masked softmax, AGRU / AUGRU) writes the final interest state into
+the row's last nh columns, and the fcn stack runs over it as DIN's tail.  Outside the envelope the
+same three steps are three launches (rk_concat_gather, rk_dien_interest, the tail), with the same
+bits.  `prepare(dense, category, sequence, target)` binds the one launch to its inputs like
+DIN.prepare.  The row order is DIN's (dense in the given order, category in ModuleDict order), not
+input_layer's alphabetical one: there is no TF checkpoint this could ever load.
 
 Request-level scoring (eval, inference only): `extract_interests(sequence)` runs the interest
 extractor over R histories once (rk_dien_extract), `score(dense, category, target, interests,
@@ -46,7 +50,7 @@ import torch
 import torch.nn as nn
 
 from . import common, ops, train
-from .common import EngineModule, Layer, check_eval, load_vocabulary, run_tail, table_rows
+from .common import PACKED, EngineModule, Layer, check_eval, fused_mlp_fits, load_vocabulary, run_tail, table_rows
 from .din import FIELDS, SEQ_KEY, Dice
 
 NEG_SEQ_KEY = "neg_" + SEQ_KEY  # neg_his_read_comment_7d_seq: the auxiliary loss's sampled negatives
@@ -680,8 +684,18 @@ class DIEN(EngineModule):
             return (prob, logit, att, *aux) if return_attention else (prob, logit, *aux)
         logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
         prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        row = torch.empty(B, width, device=dev, dtype=torch.float32)
         att = torch.empty(B, T, device=dev, dtype=torch.float32) if return_attention else None
+        if self._fusable(pl, T):
+            # the whole forward in one launch (rk_dien_forward); outside its envelope the three below,
+            # which compute the same bits
+            try:
+                self._launch_fused(pl, logit, prob, att)
+                return (prob, logit, att) if return_attention else (prob, logit)
+            except ops._lib.RankOpsError as e:
+                if getattr(e, "code", None) != ops._lib.RK_ERR_UNSUPPORTED:
+                    raise
+                self._mark_unfusable(pl, T)
+        row = torch.empty(B, width, device=dev, dtype=torch.float32)
         ops.concat_gather(pl["segs"], B, row)
         try:
             ops.dien_interest(ops._lib.fptr(row, pl["q_col"]), width, self.embeddings["feedid"].weight, pl["seq"],
@@ -691,6 +705,86 @@ class DIEN(EngineModule):
             _convert(e, H, nh, T)
         run_tail(row, self._tail, self.output_layer, {}, logit, prob)
         return (prob, logit, att) if return_attention else (prob, logit)
+
+    # ---- the one-launch forward (rk_dien_forward) and its prepared form
+
+    def _fusable(self, pl, T) -> bool:
+        """Whether the eval forward tries rk_dien_forward: the switch, the cheap half of its envelope
+        (the library checks all of it and answers RK_ERR_UNSUPPORTED), no earlier refusal of the
+        shape, and a batch that gives no CU a second workgroup (a workgroup holds 4 chain waves among
+        its 16 and a CU holds one workgroup, so past that the recurrence of rk_dien_interest's one-wave
+        workgroups, many per CU, is faster than the launches saved).  It needs run_tail's fused path
+        for the bits to be the three launches'."""
+        per_cu = common.FUSED_DIEN_WG_PER_CU
+        return (common.FUSED_DIEN and common.FUSED_MLP and self.gru_output_units == 8 and pl["H"] in (8, 16, 32)
+                and fused_mlp_fits(pl["width"], [l.linear.out_features for l in self._tail])
+                and (per_cu is None or (pl["B"] + 15) // 16 <= per_cu * common._num_cus(pl["dev"]))
+                and (pl["width"], T, pl["H"]) not in self.__dict__.get("_unfusable", ()))
+
+    def _mark_unfusable(self, pl, T):
+        """rk_dien_forward refused this shape (RK_ERR_UNSUPPORTED, e.g. its LDS need at a long history):
+        later forwards of the shape take the three launches at once."""
+        self.__dict__.setdefault("_unfusable", set()).add((pl["width"], T, pl["H"]))
+
+    def _fused_args(self, pl, packed, logit, prob, att):
+        layers = [ops.make_mlp_layer(l.linear.weight, pk, **l.epilogue_kwargs()) for l, pk in zip(self._tail, packed)]
+        head = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias,
+                                 head_logit=logit, head_prob=prob)
+        return (pl["segs"], pl["width"], pl["q_col"], pl["state_col"], self.embeddings["feedid"].weight, pl["seq"],
+                pl["seq_len"], pl["H"], self.gru_output_units, _cell(self.custom_gru_type), self.interest_weights(),
+                layers, head, att, pl["B"], pl["dev"])
+
+    def _launch_fused(self, pl, logit, prob, att):
+        ops.dien_forward(*self._fused_args(pl, [PACKED(l.linear.weight) for l in self._tail], logit, prob, att))
+
+    def prepare(self, dense, category, sequence, target):
+        """An eval forward bound to these input tensors (the single-kernel analogue of capturing
+        the forward in a hipGraph): returns `run()` that recomputes the whole forward from the
+        current contents of the inputs with one kernel launch (rk_dien_forward_plan /
+        rk_dien_plan_launch) and returns the same (prob, logit) tensors each time; `run.plan` is the
+        plan.  The binding is by address: an input that would need a converted copy (not float32 /
+        int64, a history that is not contiguous) raises instead of being bound to a copy.  Unlike
+        `forward` it takes the one launch at any batch: past one 16-sample workgroup per CU a
+        hipGraph of the three launches is faster.  Like a captured graph it binds the current
+        weights: prepare again after changing them."""
+        if self.training:
+            raise RuntimeError("DIEN.prepare: eval mode only (call .eval() first)")
+        pl = self._plan(dense, category, sequence, target)
+        B, dev, width = pl["B"], pl["dev"], pl["width"]
+        T = pl["seq"].shape[1]
+        ids = [v for k, v in category.items() if k != "feedid" and k in self.embeddings]
+        ids += [target["feedid"], sequence[SEQ_KEY], sequence[f"{SEQ_KEY}_length"]]
+        if any(t.dtype != torch.int64 for t in ids) or any(v.dtype != torch.float32 for v in dense.values()) \
+                or not all(t.is_contiguous() for t in ids[-2:]):
+            raise RuntimeError("DIEN.prepare: the inputs must be the caller's own float32 / int64 tensors (the history "
+                               "contiguous): a converted copy would stop following later writes")
+        if B == 0:
+            raise RuntimeError("DIEN.prepare: an empty batch has nothing to launch")
+        if width != self._tail[0].linear.in_features:
+            raise ValueError(f"rankops DIEN: the inputs make a row of {width} columns, the first fcn layer takes "
+                             f"{self._tail[0].linear.in_features}")
+        if not (common.FUSED_MLP and self.gru_output_units == 8 and pl["H"] in (8, 16, 32)
+                and fused_mlp_fits(width, [l.linear.out_features for l in self._tail])):
+            raise RuntimeError("DIEN.prepare: configuration outside rk_dien_forward's envelope")
+        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        packed = [PACKED.pin(l.linear.weight) for l in self._tail]  # never rewritten under the plan
+        args = self._fused_args(pl, packed, logit, prob, None)
+        keep = (pl, packed, [l.epilogue_kwargs() for l in self._tail], args[10], args[11], logit, prob,
+                self.embeddings["feedid"].weight, self.output_layer.weight, self.output_layer.bias)
+        try:
+            plan = ops.dien_forward_plan(*args, keep=keep)
+        except ops._lib.RankOpsError as e:
+            if getattr(e, "code", None) != ops._lib.RK_ERR_UNSUPPORTED:
+                raise
+            raise RuntimeError(f"DIEN.prepare: configuration outside rk_dien_forward's envelope: {e}") from e
+        out = (prob, logit)
+
+        def run():
+            plan.launch()
+            return out
+        run.plan = plan
+        return run
 
     # ---- request-level scoring (eval only): one history per request, many candidates per history
 

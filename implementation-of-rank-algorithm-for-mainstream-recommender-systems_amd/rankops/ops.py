@@ -355,6 +355,66 @@ def dien_evolve(query_ptr, ld_query, hs, seq_len, request_index, H, cell_type, w
                              att.stride(0) if att is not None else 0, _lib.raw_stream(device)), "rk_dien_evolve")
 
 
+def _dien_forward_args(segs, width, q_col, state_col, key_table, seq, seq_len, H, nh, cell_type, weights, layers,
+                       head: Epilogue, att, batch):
+    """The rk_dien_forward argument list (without the stream / plan slot) and the ctypes arrays it
+    points into."""
+    arr = _seg_array(segs)
+    larr = (_lib.MlpLayer * max(1, len(layers)))(*layers)
+    args = (arr, len(segs), width, q_col, state_col, ptr(key_table), key_table.shape[0], key_table.stride(0), ptr(seq),
+            seq.stride(0), seq.shape[1], ptr(seq_len), batch, H, nh, cell_type, *[ptr(w) for w in weights], larr,
+            len(layers), ctypes.byref(head), ptr(att), att.stride(0) if att is not None else 0)
+    return args, (arr, larr, head)
+
+
+def dien_forward(segs, width, q_col, state_col, key_table, seq, seq_len, H, nh, cell_type, weights, layers,
+                 head: Epilogue, att, batch, device):
+    """rk_dien_forward: the whole DIEN eval forward (row gather, GRU + attention + AGRU/AUGRU, fcn tail,
+    head) in one launch; weights = (Wg, bg, Wc, bc, A, Vg, vg, Vc, vc), att an optional [batch, T]
+    output of the attention weights."""
+    lib = _lib.load()
+    _lib.ensure_device(device)
+    args, _keep = _dien_forward_args(segs, width, q_col, state_col, key_table, seq, seq_len, H, nh, cell_type,
+                                     weights, layers, head, att, batch)
+    check(lib.rk_dien_forward(*args, _lib.raw_stream(device)), "rk_dien_forward")
+
+
+class DienPlan:
+    """rk_dien_forward_plan: the one-launch DIEN forward with its arguments validated once; launch()
+    runs the kernel on the current stream (no per-call host work besides the ctypes call).  Binds
+    the pointers it was made with — `keep` holds every tensor it reads or writes alive for the
+    plan's lifetime."""
+
+    def __init__(self, args, keep, device):
+        self._lib = _lib.load()
+        self._device = device
+        self._handle = ctypes.c_void_p()
+        check(self._lib.rk_dien_forward_plan(*args, ctypes.byref(self._handle)), "rk_dien_forward_plan")
+        self._keep = keep
+
+    def launch(self):
+        check(self._lib.rk_dien_plan_launch(self._handle, _lib.raw_stream(self._device)), "rk_dien_plan_launch")
+
+    def launch_on(self, stream: int):
+        """Launch on an explicit HIP stream (a raw handle, e.g. `torch.cuda.Stream().cuda_stream`),
+        without making it the current stream."""
+        check(self._lib.rk_dien_plan_launch(self._handle, ctypes.c_void_p(stream)), "rk_dien_plan_launch")
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            self._lib.rk_dien_plan_destroy(h)
+            h.value = None
+
+
+def dien_forward_plan(segs, width, q_col, state_col, key_table, seq, seq_len, H, nh, cell_type, weights, layers,
+                      head: Epilogue, att, batch, device, keep=()):
+    _lib.ensure_device(device)
+    args, k = _dien_forward_args(segs, width, q_col, state_col, key_table, seq, seq_len, H, nh, cell_type, weights,
+                                 layers, head, att, batch)
+    return DienPlan(args, (k, tuple(keep)), device)
+
+
 def dien_interest_backward(query_ptr, ld_query, keys, seq, ld_keys_b, seq_len, T, H, nh, cell_type, weights, hs, ss,
                            att, d_out_ptr, ld_dout, dquery_ptr, ld_dquery, accumulate_dquery, dkeys, batch, device,
                            seq_masked=None, d_hs=None, accumulate_dkeys=False):

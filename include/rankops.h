@@ -34,6 +34,8 @@
  *                      loss over the extractor states and its gradients      DIEN/dien.py:256-300
  *   rk_dien_extract(_dense), rk_dien_evolve  rk_dien_interest cut in two for request-level scoring:
  *                      the extractor once per history, attention + evolution once per candidate
+ *   rk_dien_forward(_plan)  the whole DIEN eval forward (row gather, rk_dien_interest, fcn tail, head)
+ *                      in one launch
  *   rk_dice_forward   Dice.forward() in eval (BatchNorm running statistics)           din.py:26-36
  *   rk_row_l2norm_mean DIN mini-batch-aware l2 term          din.py:318-322
  *   rk_afm_forward     AFM.forward()                         afm.py:92-119
@@ -344,6 +346,45 @@ int rk_dien_evolve(const float* query, int64_t ld_query, const float* hs, int64_
                    int32_t nh, int32_t cell_type, const float* A, const float* Vg, const float* vg,
                    const float* Vc, const float* vc, float* out, int64_t ld_out, float* att_out,
                    int64_t ld_att, void* stream);
+
+/* rk_dien_forward: the whole DIEN eval forward in one launch.  The row [0, width) of sample b is
+ *   gathered by `row_segs` (rk_concat_gather's semantics: the last covering segment wins, an
+ *   out-of-range id reads zero and raises RK_FLAG_INDEX_OOB); its columns [q_col, q_col + H) are the
+ *   query of rk_dien_interest over key_table[seq[b, 0:seq_len[b]]], whose final state goes to columns
+ *   [state_col, state_col + nh) (whatever a segment puts there is overwritten; the two ranges must
+ *   not overlap); then `layers` (packed by rk_mlp_pack_weight) and the output layer + sigmoid of
+ *   `head` (head_w / head_b / head_logit / head_prob) run over the row, which never leaves LDS.
+ *   att_out (optional): the attention weights [batch, 0:T] at att_out + b*ld_att.
+ *   prob, logit and att_out are bit-equal to rk_concat_gather + rk_dien_interest + rk_mlp_forward.
+ * Envelope: H in {8,16,32}, nh = 8, nseg <= 32, width in (64, 128] with hidden units
+ *   [512, 256, 128], history rows 16-B aligned, and an LDS need (16 samples' histories beside the
+ *   row buffers, growing with T * max(H, nh)) within the CU's 160 KiB; anything else returns
+ *   RK_ERR_UNSUPPORTED before any launch (the three launches compute the same).
+ * Validates before launching, allocates nothing, does not synchronise, capturable.  batch == 0:
+ *   RK_OK, no launch.                                                                            */
+int rk_dien_forward(const rk_segment* row_segs, int32_t nseg, int32_t width, int32_t q_col,
+                    int32_t state_col, const float* key_table, int64_t key_rows, int64_t ld_key,
+                    const int64_t* seq, int64_t ld_seq, int32_t T, const int64_t* seq_len,
+                    int64_t batch, int32_t H, int32_t nh, int32_t cell_type, const float* Wg,
+                    const float* bg, const float* Wc, const float* bc, const float* A,
+                    const float* Vg, const float* vg, const float* Vc, const float* vc,
+                    const rk_mlp_layer* layers, int32_t nlayers, const rk_epilogue* head,
+                    float* att_out, int64_t ld_att, void* stream);
+/* A prepared rk_dien_forward, as rk_din_forward_plan: the same arguments, validated once, launched
+ * later by rk_dien_plan_launch on any stream at the cost of one kernel launch.  A plan binds the
+ * pointers it was made with: keep every buffer alive, and make a new plan after the weights move
+ * or their packed images are rebuilt.                                                           */
+int rk_dien_forward_plan(const rk_segment* row_segs, int32_t nseg, int32_t width, int32_t q_col,
+                         int32_t state_col, const float* key_table, int64_t key_rows,
+                         int64_t ld_key, const int64_t* seq, int64_t ld_seq, int32_t T,
+                         const int64_t* seq_len, int64_t batch, int32_t H, int32_t nh,
+                         int32_t cell_type, const float* Wg, const float* bg, const float* Wc,
+                         const float* bc, const float* A, const float* Vg, const float* vg,
+                         const float* Vc, const float* vc, const rk_mlp_layer* layers,
+                         int32_t nlayers, const rk_epilogue* head, float* att_out, int64_t ld_att,
+                         void** plan);
+int rk_dien_plan_launch(const void* plan, void* stream);
+void rk_dien_plan_destroy(void* plan);
 
 /* Backward of the interest recurrence (backprop through time, t = seq_len-1 ... 0) given
  * d_out[b, 0:nh] = dL/d(out) at d_out + b*ld_dout and the forward's inputs, hs, ss and att:
