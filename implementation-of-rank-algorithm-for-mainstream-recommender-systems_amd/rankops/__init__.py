@@ -14,6 +14,9 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
     DeepCrossingModel, residual_unit       algorithm/DeepCrossing/deepcrossing.py
     BSTModel, BSTTransformer               algorithm/BST/bst.py
     FwFM                                   algorithm/FwFM/fwfm.py
+    XDeepFM, cin                           xDeepFM (listed in the reference's README, no script in the
+                                           snapshot): DeepFM with the Compressed Interaction Network,
+                                           rk_cin_forward + the deep tail
 
 `rankops.sharded.ShardedDeepFM` adds the table-sharded multi-GPU DeepFM lookup (RCCL
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the
@@ -41,7 +44,9 @@ from .fwfm import FwFM  # noqa: F401
 from .loader import BatchAssembler, Vocabulary, label_encode, wechat_vocabularies  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
 from .ranking import GroupedAUC, GroupTable, RequestTopK, grouped_auc, topk_per_request, topk_segments  # noqa: F401
+from .ops import cin  # noqa: F401
 from .train import Adam, SparseAdam  # noqa: F401
+from .xdeepfm import XDeepFM  # noqa: F401
 
 __all__ = [
     "AFM", "BSTModel", "BSTTransformer", "BatchAssembler", "DCNModel", "DIN", "DeepCrossingModel", "DeepFM",
@@ -49,5 +54,5 @@ __all__ = [
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
     "dien_aux_loss", "dien_aux_loss_gather", "dien_extract", "dien_extract_gather", "dien_evolve", "DIENInterests",
-    "SparseAdam", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
+    "SparseAdam", "XDeepFM", "cin", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
 ]

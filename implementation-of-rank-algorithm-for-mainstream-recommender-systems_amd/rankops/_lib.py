@@ -22,7 +22,7 @@ RK_ERR_UNSUPPORTED = 4  # include/rankops.h
 RK_FLAG_INDEX_OOB = 1
 RK_ACT_NONE, RK_ACT_RELU, RK_ACT_LEAKY, RK_ACT_DICE, RK_ACT_PRELU = 0, 1, 2, 3, 4
 RK_MAX_SEGMENTS = 64
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 
 class Segment(ctypes.Structure):
@@ -419,6 +419,10 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     "rk_deepfm_forward_fo": (ctypes.c_int, [_SEG_P, c_void_p, c_void_p, c_int32, c_int32, c_int64, _MLP_P, c_int32,
                                             _EPI_P, c_void_p, c_void_p, c_void_p]),
+    "rk_cin_pack_weight": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "rk_cin_forward": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_int64, POINTER(c_void_p), POINTER(c_void_p),
+                                      POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rk_shard_gather_rows_split": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_void_p, c_int32, c_int64,
                                                   c_int64, c_int64, c_void_p, c_void_p]),
     "rk_shard_fm_assemble": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p,

@@ -458,6 +458,7 @@ class PackedWeights:
 
 PACKED = PackedWeights()
 BST_PACKED = PackedWeights(lambda w, out=None: ops.pack_bst_weight(w, out=out))  # bst_block_kernel's projections
+CIN_PACKED = PackedWeights(lambda w, out=None: ops.pack_cin_weight(w, out=out))  # rk_cin_forward's layer weights
 
 
 def empty_rows(device, n: int, shape=(0, 1)):

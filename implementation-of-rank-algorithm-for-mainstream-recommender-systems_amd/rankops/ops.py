@@ -248,6 +248,92 @@ def deepfm_forward_fo(fields, first, first_ld, dim, batch, layers, ep, fm1, fm2)
                                    _lib.stream_of(fm1)), "rk_deepfm_forward_fo")
 
 
+CIN_ACT = {"identity": _lib.RK_ACT_NONE, "relu": _lib.RK_ACT_RELU}
+
+
+def pack_cin_weight(weight: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """One CIN layer's weight ([n, k], or nn.Conv1d's [n, k, 1]) -> rk_cin_pack_weight's image, a flat
+    pad16(n) * pad16(k) tensor (into `out` when given: a previous image of the same shape)."""
+    lib = _lib.load()
+    require_gpu(weight, "cin weight")
+    if weight.dtype != torch.float32 or weight.dim() not in (2, 3) or (weight.dim() == 3 and weight.shape[2] != 1):
+        raise ValueError(f"pack_cin_weight: expected a float32 [n, k] or [n, k, 1] weight, got {tuple(weight.shape)}")
+    n, k = weight.shape[0], weight.shape[1]
+    w = weight.detach().reshape(n, k)
+    if w.stride(1) != 1:
+        w = w.contiguous()
+    size = (n + 15) // 16 * 16 * ((k + 15) // 16 * 16)
+    if out is None or out.numel() != size or out.device != w.device:
+        out = torch.empty(size, device=w.device, dtype=torch.float32)
+    check(lib.rk_cin_pack_weight(w.data_ptr(), w.stride(0), n, k, out.data_ptr(), _lib.stream_of(out)),
+          "rk_cin_pack_weight")
+    return out
+
+
+def cin_forward_args(second, first, dim, batch, images, biases, sizes, activation, out_w, out_b, deep_in, fm1, pooled,
+                     cin_logit, device):
+    """The rk_cin_forward argument list (the stream last, None) and the ctypes arrays it points into.
+    fm1 at [14], cin_logit at [17] and the stream at [-1] are the per-call slots of a cached forward."""
+    _lib.ensure_device(device)
+    nl = len(images)
+    a2 = _as_seg_array(second)
+    a1 = _as_seg_array(first) if first is not None else None
+    wp = (ctypes.c_void_p * max(1, nl))(*[ptr(w) for w in images])
+    bp = (ctypes.c_void_p * max(1, nl))(*[ptr(b) for b in biases])
+    hs = (ctypes.c_int32 * max(1, nl))(*[int(h) for h in sizes])
+    act = CIN_ACT[activation] if isinstance(activation, str) else int(activation)
+    args = [a2, a1, len(second), dim, batch, wp, bp, hs, nl, act, ptr(out_w), ptr(out_b), ptr(deep_in),
+            deep_in.stride(0) if deep_in is not None else 0, ptr(fm1), ptr(pooled),
+            pooled.stride(0) if pooled is not None else 0, ptr(cin_logit), None]
+    return args, (a2, a1, wp, bp, hs)
+
+
+def cin_forward(second, first, dim, batch, images, biases, sizes, activation, device, *, out_w=None, out_b=None,
+                deep_in=None, fm1=None, pooled=None, cin_logit=None):
+    """rk_cin_forward: row gather, first-order sum, every CIN layer, the pooling over d and the output
+    layer in one launch.  second / first: lists of Segments (all tables or all dense; first may be
+    None without fm1), images: pack_cin_weight() of each layer, sizes: H_k; every output is optional."""
+    args, _keep = cin_forward_args(second, first, dim, batch, images, biases, sizes, activation, out_w, out_b,
+                                   deep_in, fm1, pooled, cin_logit, device)
+    args[-1] = _lib.raw_stream(device)
+    check(_lib.load().rk_cin_forward(*args), "rk_cin_forward")
+
+
+def cin(x0: torch.Tensor, weights, biases=None, activation: str = "identity", out_w=None, out_b=None):
+    """The Compressed Interaction Network over dense rows x0 [B, m, D] (any row stride; field rows
+    16-B aligned): x^k[b, n, d] = act(sum_{h, i} W_k[n, h m + i] x^{k-1}[b, h, d] x0[b, i, d] + bias_k[n])
+    for weights[k] of shape [H_k, H_{k-1} m] (or nn.Conv1d's [H_k, H_{k-1} m, 1]), H_0 = m.  Returns
+    pooled [B, sum H_k] (the sums over d, layers side by side); with out_w [sum H_k] and out_b [1]
+    also the logit pooled . out_w + out_b as (pooled, logit [B, 1])."""
+    as_f32(x0, "x0")
+    if activation not in CIN_ACT:
+        raise ValueError(f"rankops.cin: activation must be one of {sorted(CIN_ACT)}, got {activation!r}")
+    if x0.dim() != 3 or x0.stride(2) != 1:
+        raise ValueError(f"rankops.cin: x0 must be [B, m, D] with unit stride along D, got {tuple(x0.shape)}")
+    B, m, D = x0.shape
+    weights = list(weights)
+    biases = list(biases) if biases is not None else [None] * len(weights)
+    sizes, hprev = [], m
+    for k, w in enumerate(weights):
+        as_f32(w, f"weights[{k}]")
+        if w.shape[1] != hprev * m:
+            raise ValueError(f"rankops.cin: weights[{k}] has {w.shape[1]} columns, expected {hprev * m}")
+        if biases[k] is not None and as_f32(biases[k], f"biases[{k}]").numel() != w.shape[0]:
+            raise ValueError(f"rankops.cin: biases[{k}] must have {w.shape[0]} elements")
+        hprev = w.shape[0]
+        sizes.append(hprev)
+    dev = x0.device
+    pooled = torch.empty(B, sum(sizes), device=dev, dtype=torch.float32)
+    logit = torch.empty(B, 1, device=dev, dtype=torch.float32) if out_w is not None else None
+    if B > 0:
+        images = [pack_cin_weight(w) for w in weights]
+        biases = [b if b is None or b.is_contiguous() else b.contiguous() for b in biases]
+        segs = [Segment(fptr(x0, i * x0.stride(1)), None, 0, x0.stride(0), 0, D, i * D) for i in range(m)]
+        cin_forward(segs, None, D, B, images, biases, sizes, activation, dev, out_w=out_w, out_b=out_b,
+                    pooled=pooled, cin_logit=logit)
+    return pooled if out_w is None else (pooled, logit)
+
+
 def din_attention(query_ptr, ld_query, key_table, seq, seq_len, T, H, weights, use_softmax, out_ptr, ld_out,
                   batch, device):
     lib = _lib.load()

@@ -47,6 +47,9 @@
  *   rk_fm_linear_packed  the DeepFM front end in one launch: packed-table gather, fm1, fm2 and the
  *                      first deep layer (the deep input never reaches HBM)  deepfm.py:100-112,122-142
  *   rk_deepfm_forward  DeepFM.forward() in one launch at configs[1]'s shape   deepfm.py:121-151
+ *   rk_cin_forward, rk_cin_pack_weight  xDeepFM's front end in one launch: row gather, first-order sum,
+ *                      the Compressed Interaction Network, its pooling and output layer (the
+ *                      reference lists the model, its script is not in the snapshot)
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
  *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
  *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
@@ -95,7 +98,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 2
+#define RK_ABI_VERSION 3
 
 #define RK_OK 0
 #define RK_ERR_INVALID 1     /* bad argument (shape, null pointer, limit) */
@@ -694,6 +697,37 @@ int rk_fm_linear_packed(const rk_segment* fields, int32_t num_fields, int32_t di
 int rk_deepfm_forward(const rk_segment* fields, int32_t num_fields, int32_t dim, int64_t batch,
                       const rk_mlp_layer* layers, int32_t nlayers, const rk_epilogue* head, float* fm1,
                       float* fm2, void* stream);
+
+/* ---- xDeepFM: the Compressed Interaction Network (Lian et al. 2018, eq. 6-8, direct form) ---- */
+/* One CIN layer's weight W [n, k] (nn.Conv1d(k, n, 1).weight, k = H_prev * num_fields, row stride
+ * ldw) as the image rk_cin_forward streams: pad16(n) * pad16(k) floats, zero padded, in the load
+ * order of v_mfma_f32_16x16x4_f32's A operand:
+ *   out[((mt * pad16(k)/16 + ks) * 64 + lane) * 4 + e] = W[16 mt + lane % 16][16 ks + 4 e + lane / 16].
+ * A layout pass run once per weight version (the host layer caches it).  out 16-B aligned.      */
+int rk_cin_pack_weight(const float* w, int64_t ldw, int32_t n, int32_t k, float* out, void* stream);
+
+/* The xDeepFM front end in one launch.  second_order: num_fields segments of `dim` columns, all
+ * tables or all dense, rows 16-B aligned (src_ld % 4 == 0), out_col % 4 == 0 = the field's column
+ * in deep_in; x0[b, i, :] = the row of field i.  For k = 1..num_layers, with H_0 = num_fields:
+ *   x^k[b, n, d] = act( sum_{h, i} W_k[n, h * num_fields + i] * x^{k-1}[b, h, d] * x0[b, i, d] + biases[k][n] )
+ * (weights[k]: the rk_cin_pack_weight image of W_k [layer_sizes[k], layer_sizes[k-1] * num_fields];
+ * biases[k] may be NULL; activation RK_ACT_NONE or RK_ACT_RELU), then
+ *   pooled[b, off_k + n] = sum_d x^k[b, n, d]   (off_k = layer_sizes[0] + .. + layer_sizes[k-1])
+ *   cin_logit[b] = pooled[b, :] . out_w + out_b[0].
+ * Outputs, each may be NULL: deep_in [batch, ld_deep] (the gathered rows, 16-B aligned, ld_deep % 4
+ * == 0), fm1 [batch] = the sum over fields, in order, of first_order's one-column segments (tables
+ * or dense as second_order; first_order may be NULL when fm1 is), pooled [batch, ld_pooled],
+ * cin_logit [batch] (needs out_w, out_b).  The feature maps stay in LDS; sums run in a fixed order
+ * (no atomics), so two launches give the same bits.
+ * Envelope: 2 <= num_fields <= 32, dim in {4, 8, 16, 32, 64}, 1 <= num_layers <= 4,
+ * 1 <= layer_sizes[k] <= 256 (else RK_ERR_UNSUPPORTED); NULL or shape errors: RK_ERR_INVALID before
+ * any launch; batch == 0: RK_OK, no launch.  Out-of-range ids read zero rows and raise
+ * RK_FLAG_INDEX_OOB.                                                                            */
+int rk_cin_forward(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                   int32_t dim, int64_t batch, const float* const* weights, const float* const* biases,
+                   const int32_t* layer_sizes, int32_t num_layers, int32_t activation,
+                   const float* out_w, const float* out_b, float* deep_in, int64_t ld_deep, float* fm1,
+                   float* pooled, int64_t ld_pooled, float* cin_logit, void* stream);
 
 /* ---- table-sharded DeepFM, the local steps around the all-to-alls (rankops.sharded; the
  * reference's DeepFM.forward, deepfm.py:121-151, runs on one device) ---- */
