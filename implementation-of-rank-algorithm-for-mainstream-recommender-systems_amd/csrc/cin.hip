@@ -131,12 +131,14 @@ __device__ __forceinline__ void cin_unit(const float* __restrict__ W, int KS4, i
   }
 }
 
-template <int NC>
+// TRAIN: every layer's maps also go to HBM for the backward (cin_backward.hip), as
+// maps[b][off_k + n][d] (sample stride hsum * D); the eval instantiation has none of that code.
+template <int NC, bool TRAIN>
 __global__ __launch_bounds__(kCinThreads) void cin_forward_kernel(
     const CinFields f, const CinLayers L, int m, int D, int nlayers, int act, int ld, int hp_max, int64_t batch,
     const float* __restrict__ out_w, const float* __restrict__ out_b, float* __restrict__ deep_in, int64_t ld_deep,
     float* __restrict__ fm1, float* __restrict__ pooled, int64_t ld_pooled, float* __restrict__ cin_logit,
-    uint32_t* flags) {
+    uint32_t* flags, float* __restrict__ maps, int hsum) {
   extern __shared__ __attribute__((aligned(16))) float cin_smem[];
   constexpr int NQ = NC / 4;   // float4 columns of the tile
   constexpr int NT = NC / 16;  // 16-column MFMA tiles
@@ -230,6 +232,11 @@ __global__ __launch_bounds__(kCinThreads) void cin_forward_kernel(
       const int c4 = id % NQ, n = id / NQ;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (ok) v = *reinterpret_cast<const f32x4*>(next + n * ld + c4 * 4);
+      if constexpr (TRAIN) {
+        const int64_t b = b0 + c4 / G;
+        if (ok && b < batch)
+          *reinterpret_cast<f32x4*>(maps + ((b * hsum + off + n) * D + (c4 & (G - 1)) * 4)) = v;
+      }
       float sum = (v[0] + v[1]) + (v[2] + v[3]);
       for (int o = 1; o < G; o <<= 1) sum += __shfl_xor(sum, o, kWave);
       if (ok && (c4 & (G - 1)) == 0) idle[(c4 / G) * Hp + n] = sum;
@@ -285,11 +292,12 @@ RK_API int rk_cin_pack_weight(const float* w, int64_t ldw, int32_t n, int32_t k,
   return check_launch("rk_cin_pack_weight");
 }
 
-RK_API int rk_cin_forward(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
-                          int32_t dim, int64_t batch, const float* const* weights, const float* const* biases,
-                          const int32_t* layer_sizes, int32_t num_layers, int32_t activation, const float* out_w,
-                          const float* out_b, float* deep_in, int64_t ld_deep, float* fm1, float* pooled,
-                          int64_t ld_pooled, float* cin_logit, void* stream) {
+// rk_cin_forward (maps == nullptr, the eval kernels) and rk_cin_forward_train (the TRAIN kernels)
+static int cin_forward_launch(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                              int32_t dim, int64_t batch, const float* const* weights, const float* const* biases,
+                              const int32_t* layer_sizes, int32_t num_layers, int32_t activation, const float* out_w,
+                              const float* out_b, float* deep_in, int64_t ld_deep, float* fm1, float* pooled,
+                              int64_t ld_pooled, float* cin_logit, float* maps, void* stream) {
   if (!second_order || !weights || !biases || !layer_sizes || num_fields <= 0 || num_layers <= 0 || dim <= 0)
     return fail(RK_ERR_INVALID, "rk_cin_forward: null segments / layers or a non-positive count");
   if (num_fields < 2 || num_fields > kCinMaxFields)
@@ -355,7 +363,7 @@ RK_API int rk_cin_forward(const rk_segment* second_order, const rk_segment* firs
   if (dense != 0 && dense != num_fields)
     return fail(RK_ERR_UNSUPPORTED, "rk_cin_forward: segments must be all tables or all dense");
   if (batch == 0) return RK_OK;
-  const bool layers = pooled || cin_logit;
+  const bool layers = pooled || cin_logit || maps;
   if (!layers && !deep_in && !fm1) return RK_OK;
   // tile: 128 columns with rows padded by 16 floats (the four K rows of a B read on distinct banks),
   // else 64 columns, unpadded when the widest envelope (256 maps, 32 fields) needs it
@@ -371,16 +379,41 @@ RK_API int rk_cin_forward(const rk_segment* second_order, const rk_segment* firs
   const int lds = (int)bytes(nc, pad);
   hipStream_t st = (hipStream_t)stream;
   const int nl = layers ? num_layers : 0;
+#define RK_CIN_LAUNCH(NC, TRAIN)                                                                              \
+  do {                                                                                                        \
+    raise_lds_limit((const void*)cin_forward_kernel<NC, TRAIN>, lds);                                         \
+    cin_forward_kernel<NC, TRAIN><<<(unsigned)blocks, kCinThreads, lds, st>>>(                                \
+        t, L, num_fields, dim, nl, activation, nc + pad, hp, batch, out_w, out_b, deep_in, ld_deep, fm1, pooled, \
+        ld_pooled, cin_logit, device_flags(), maps, hsum);                                                    \
+  } while (0)
   if (nc == 128) {
-    raise_lds_limit((const void*)cin_forward_kernel<128>, lds);
-    cin_forward_kernel<128><<<(unsigned)blocks, kCinThreads, lds, st>>>(
-        t, L, num_fields, dim, nl, activation, nc + pad, hp, batch, out_w, out_b, deep_in, ld_deep, fm1, pooled,
-        ld_pooled, cin_logit, device_flags());
+    if (maps) RK_CIN_LAUNCH(128, true);
+    else RK_CIN_LAUNCH(128, false);
   } else {
-    raise_lds_limit((const void*)cin_forward_kernel<64>, lds);
-    cin_forward_kernel<64><<<(unsigned)blocks, kCinThreads, lds, st>>>(
-        t, L, num_fields, dim, nl, activation, nc + pad, hp, batch, out_w, out_b, deep_in, ld_deep, fm1, pooled,
-        ld_pooled, cin_logit, device_flags());
+    if (maps) RK_CIN_LAUNCH(64, true);
+    else RK_CIN_LAUNCH(64, false);
   }
-  return check_launch("rk_cin_forward");
+#undef RK_CIN_LAUNCH
+  return check_launch(maps ? "rk_cin_forward_train" : "rk_cin_forward");
+}
+
+RK_API int rk_cin_forward(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                          int32_t dim, int64_t batch, const float* const* weights, const float* const* biases,
+                          const int32_t* layer_sizes, int32_t num_layers, int32_t activation, const float* out_w,
+                          const float* out_b, float* deep_in, int64_t ld_deep, float* fm1, float* pooled,
+                          int64_t ld_pooled, float* cin_logit, void* stream) {
+  return cin_forward_launch(second_order, first_order, num_fields, dim, batch, weights, biases, layer_sizes,
+                            num_layers, activation, out_w, out_b, deep_in, ld_deep, fm1, pooled, ld_pooled, cin_logit,
+                            nullptr, stream);
+}
+
+RK_API int rk_cin_forward_train(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                                int32_t dim, int64_t batch, const float* const* weights, const float* const* biases,
+                                const int32_t* layer_sizes, int32_t num_layers, int32_t activation,
+                                const float* out_w, const float* out_b, float* deep_in, int64_t ld_deep, float* fm1,
+                                float* pooled, int64_t ld_pooled, float* cin_logit, float* maps, void* stream) {
+  if (!maps || !aligned16(maps)) return fail(RK_ERR_INVALID, "rk_cin_forward_train: maps must be a 16-B aligned buffer");
+  return cin_forward_launch(second_order, first_order, num_fields, dim, batch, weights, biases, layer_sizes,
+                            num_layers, activation, out_w, out_b, deep_in, ld_deep, fm1, pooled, ld_pooled, cin_logit,
+                            maps, stream);
 }

@@ -16,7 +16,8 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
     FwFM                                   algorithm/FwFM/fwfm.py
     XDeepFM, cin                           xDeepFM (listed in the reference's README, no script in the
                                            snapshot): DeepFM with the Compressed Interaction Network,
-                                           rk_cin_forward + the deep tail
+                                           rk_cin_forward + the deep tail; trainable=True trains
+                                           (rk_cin_backward, rk_cin_wgrad), cin is differentiable
 
 `rankops.sharded.ShardedDeepFM` adds the table-sharded multi-GPU DeepFM lookup (RCCL
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the

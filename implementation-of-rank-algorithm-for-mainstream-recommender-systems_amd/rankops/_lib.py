@@ -423,6 +423,17 @@ SIGNATURES = {
     "rk_cin_forward": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_int64, POINTER(c_void_p), POINTER(c_void_p),
                                       POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rk_cin_forward_train": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_int64, POINTER(c_void_p),
+                                            POINTER(c_void_p), POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p,
+                                            c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                            c_void_p]),
+    "rk_cin_pack_weight_t": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rk_cin_backward": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int64, POINTER(c_void_p),
+                                       POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rk_cin_wgrad_workspace_floats": (c_int64, [c_int32, POINTER(c_int32), c_int32]),
+    "rk_cin_wgrad": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int64, POINTER(c_int32), c_int32, c_void_p,
+                                    c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int64, c_void_p]),
     "rk_shard_gather_rows_split": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_void_p, c_int32, c_int64,
                                                   c_int64, c_int64, c_void_p, c_void_p]),
     "rk_shard_fm_assemble": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p,

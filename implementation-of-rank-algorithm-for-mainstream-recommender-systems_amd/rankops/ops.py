@@ -299,12 +299,204 @@ def cin_forward(second, first, dim, batch, images, biases, sizes, activation, de
     check(_lib.load().rk_cin_forward(*args), "rk_cin_forward")
 
 
-def cin(x0: torch.Tensor, weights, biases=None, activation: str = "identity", out_w=None, out_b=None):
+def pack_cin_weight_t(weight: torch.Tensor, num_fields: int, out: torch.Tensor = None) -> torch.Tensor:
+    """One CIN layer's weight ([n, hprev * num_fields] or nn.Conv1d's [n, k, 1]) -> rk_cin_pack_weight_t's
+    image for rk_cin_backward: W^T, field-major, a flat num_fields * pad16(hprev) * pad16(n) tensor
+    (into `out` when given: a previous image of the same shape)."""
+    lib = _lib.load()
+    require_gpu(weight, "cin weight")
+    if weight.dtype != torch.float32 or weight.dim() not in (2, 3) or (weight.dim() == 3 and weight.shape[2] != 1):
+        raise ValueError(f"pack_cin_weight_t: expected a float32 [n, k] or [n, k, 1] weight, got {tuple(weight.shape)}")
+    n, k = weight.shape[0], weight.shape[1]
+    if num_fields <= 0 or k % num_fields:
+        raise ValueError(f"pack_cin_weight_t: {k} columns are no multiple of {num_fields} fields")
+    w = weight.detach().reshape(n, k)
+    if w.stride(1) != 1:
+        w = w.contiguous()
+    hprev = k // num_fields
+    size = num_fields * ((hprev + 15) // 16 * 16) * ((n + 15) // 16 * 16)
+    if out is None or out.numel() != size or out.device != w.device:
+        out = torch.empty(size, device=w.device, dtype=torch.float32)
+    check(lib.rk_cin_pack_weight_t(w.data_ptr(), w.stride(0), n, hprev, num_fields, out.data_ptr(),
+                                   _lib.stream_of(out)), "rk_cin_pack_weight_t")
+    return out
+
+
+def cin_forward_train(second, first, dim, batch, images, biases, sizes, activation, device, maps, *, out_w=None,
+                      out_b=None, deep_in=None, fm1=None, pooled=None, cin_logit=None):
+    """rk_cin_forward_train: cin_forward that also writes every layer's feature maps into
+    maps [batch, sum H_k, dim] (contiguous) for cin_backward / cin_wgrad."""
+    args, _keep = cin_forward_args(second, first, dim, batch, images, biases, sizes, activation, out_w, out_b,
+                                   deep_in, fm1, pooled, cin_logit, device)
+    if maps.shape != (batch, sum(int(h) for h in sizes), dim) or not maps.is_contiguous():
+        raise ValueError(f"cin_forward_train: maps must be contiguous [batch, sum H_k, dim], got {tuple(maps.shape)}")
+    args[-1:] = [maps.data_ptr(), _lib.raw_stream(device)]
+    check(_lib.load().rk_cin_forward_train(*args), "rk_cin_forward_train")
+
+
+def _rows_ok(t):
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+def cin_backward(x0_rows, num_fields, dim, images_t, sizes, activation, maps, *, dpooled=None, dlogit=None,
+                 out_w=None, dx0_add=None, dx0=None, dy=None):
+    """rk_cin_backward: the CIN's data backward in one launch.  x0_rows [B, >= m D] (field i at column
+    i D; 16-B aligned rows), images_t: pack_cin_weight_t() of each layer, maps: cin_forward_train's.
+    The gradient of pooled is dpooled [B, sum H_k] and / or dlogit [B] * out_w.  Returns
+    (dx0 [B, m D] (+ dx0_add), dy [B, sum H_k, D]: the pre-activation gradients cin_wgrad reads)."""
+    B, dev = x0_rows.shape[0], x0_rows.device
+    _lib.ensure_device(dev)
+    nl = len(images_t)
+    if dx0 is None:
+        dx0 = torch.empty(B, num_fields * dim, device=dev, dtype=torch.float32)
+    if dy is None:
+        dy = torch.empty_like(maps)
+    for t, what in ((x0_rows, "x0_rows"), (dx0, "dx0"), (dx0_add, "dx0_add")):
+        if t is not None and B > 0 and not _rows_ok(t):
+            raise ValueError(f"cin_backward: {what} needs unit column stride and 16-B aligned rows")
+    if dpooled is not None and dpooled.stride(1) != 1:
+        dpooled = dpooled.contiguous()
+    wp = (ctypes.c_void_p * max(1, nl))(*[ptr(w) for w in images_t])
+    hs = (ctypes.c_int32 * max(1, nl))(*[int(h) for h in sizes])
+    act = CIN_ACT[activation] if isinstance(activation, str) else int(activation)
+    check(_lib.load().rk_cin_backward(
+        ptr(x0_rows), x0_rows.stride(0), num_fields, dim, B, wp, hs, nl, act, ptr(maps), ptr(dpooled),
+        dpooled.stride(0) if dpooled is not None else 0, ptr(dlogit), ptr(out_w), ptr(dx0_add),
+        dx0_add.stride(0) if dx0_add is not None else 0, ptr(dx0), dx0.stride(0), ptr(dy), _lib.raw_stream(dev)),
+        "rk_cin_backward")
+    return dx0, dy
+
+
+def cin_wgrad_workspace(num_fields, sizes, device):
+    nl = len(sizes)
+    hs = (ctypes.c_int32 * max(1, nl))(*[int(h) for h in sizes])
+    n = _lib.load().rk_cin_wgrad_workspace_floats(num_fields, hs, nl)
+    return torch.empty(max(1, n), device=device, dtype=torch.float32)
+
+
+def cin_wgrad(x0_rows, num_fields, dim, sizes, maps, dy, *, bias=True, workspace=None):
+    """rk_cin_wgrad: ([dW_k [H_k, H_{k-1} m]], [dbias_k [H_k]] or None) of every layer from the rows,
+    the saved maps and cin_backward's dy; slabs of the reduction are added in a fixed order."""
+    B, dev = x0_rows.shape[0], x0_rows.device
+    _lib.ensure_device(dev)
+    nl = len(sizes)
+    if B > 0 and not _rows_ok(x0_rows):
+        raise ValueError("cin_wgrad: x0_rows needs unit column stride and 16-B aligned rows")
+    dws, dbs, hprev = [], [], num_fields
+    for h in sizes:
+        dws.append(torch.empty(int(h), hprev * num_fields, device=dev, dtype=torch.float32))
+        dbs.append(torch.empty(int(h), device=dev, dtype=torch.float32) if bias else None)
+        hprev = int(h)
+    if workspace is None:
+        workspace = cin_wgrad_workspace(num_fields, sizes, dev)
+    hs = (ctypes.c_int32 * max(1, nl))(*[int(h) for h in sizes])
+    wp = (ctypes.c_void_p * max(1, nl))(*[ptr(w) for w in dws])
+    bp = (ctypes.c_void_p * max(1, nl))(*[ptr(b) for b in dbs])
+    check(_lib.load().rk_cin_wgrad(ptr(x0_rows), x0_rows.stride(0), num_fields, dim, B, hs, nl, ptr(maps), ptr(dy),
+                                   wp, bp, workspace.data_ptr(), workspace.numel(), _lib.raw_stream(dev)),
+          "rk_cin_wgrad")
+    return dws, (dbs if bias else None)
+
+
+def _cin_launch(x0, weights, biases, sizes, activation, out_w, out_b, maps):
+    """pooled (and the logit with out_w) of rankops.cin's rows; with `maps` through rk_cin_forward_train."""
+    B, m, D = x0.shape
+    dev = x0.device
+    pooled = torch.empty(B, sum(sizes), device=dev, dtype=torch.float32)
+    logit = torch.empty(B, 1, device=dev, dtype=torch.float32) if out_w is not None else None
+    if B > 0:
+        images = [pack_cin_weight(w) for w in weights]
+        biases = [b if b is None or b.is_contiguous() else b.contiguous() for b in biases]
+        segs = [Segment(fptr(x0, i * x0.stride(1)), None, 0, x0.stride(0), 0, D, i * D) for i in range(m)]
+        if maps is None:
+            cin_forward(segs, None, D, B, images, biases, sizes, activation, dev, out_w=out_w, out_b=out_b,
+                        pooled=pooled, cin_logit=logit)
+        else:
+            cin_forward_train(segs, None, D, B, images, biases, sizes, activation, dev, maps, out_w=out_w,
+                              out_b=out_b, pooled=pooled, cin_logit=logit)
+    return pooled, logit
+
+
+class _CinFn(torch.autograd.Function):
+    """rankops.cin under autograd: rk_cin_forward_train, then rk_cin_backward + rk_cin_wgrad (and
+    rk_logit_head_backward for the output layer).  Inputs: x0, out_w, out_b, the weights, the biases."""
+
+    @staticmethod
+    def forward(ctx, activation, nl, x0, out_w, out_b, *wb):
+        weights, biases = list(wb[:nl]), list(wb[nl:])
+        B, m, D = x0.shape
+        sizes = [w.shape[0] for w in weights]
+        x0, out_w, out_b = x0.detach(), _detach(out_w), _detach(out_b)
+        maps = torch.empty(B, sum(sizes), D, device=x0.device, dtype=torch.float32)
+        pooled, logit = _cin_launch(x0, [w.detach() for w in weights], [_detach(b) for b in biases], sizes,
+                                    activation, out_w, out_b, maps)
+        ctx.activation, ctx.nl, ctx.sizes, ctx.shape = activation, nl, sizes, (B, m, D)
+        ctx.save_for_backward(x0, maps, pooled, out_w, *weights)
+        ctx.mark_non_differentiable(maps)
+        if logit is None:
+            return pooled, maps
+        return pooled, logit, maps
+
+    @staticmethod
+    def backward(ctx, dpooled, *rest):
+        x0, maps, pooled, out_w, *weights = ctx.saved_tensors
+        dlogit = rest[0] if len(rest) == 2 else None
+        B, m, D = ctx.shape
+        nl, sizes, dev = ctx.nl, ctx.sizes, x0.device
+        need = ctx.needs_input_grad  # (activation, nl, x0, out_w, out_b, weights.., biases..)
+        if dpooled is None and dlogit is None:
+            return (None,) * (5 + 2 * nl)
+        if B == 0:  # nothing to launch: zero gradients of every shape
+            zero = lambda t, n: torch.zeros_like(t) if n and t is not None else None  # noqa: E731
+            return (None, None, *[zero(t, n) for t, n in zip((x0, out_w), need[2:4])],
+                    torch.zeros(1, device=dev) if need[4] else None,
+                    *[zero(w, n) for w, n in zip(weights, need[5:5 + nl])],
+                    *[torch.zeros(h, device=dev) if n else None for h, n in zip(sizes, need[5 + nl:])])
+        if dpooled is not None:
+            dpooled = dpooled.to(torch.float32)
+        dl = dlogit.to(torch.float32).reshape(B).contiguous() if dlogit is not None else None
+        d_out_w = d_out_b = None
+        if dl is not None and (need[3] or need[4]):
+            d_out_w = torch.empty(1, sum(sizes), device=dev, dtype=torch.float32)
+            d_out_b = torch.empty(1, device=dev, dtype=torch.float32)
+            logit_head_backward(dl, None, None, pooled, None, out_w, None, None, d_out_w, d_out_b)
+        elif need[3] or need[4]:
+            d_out_w = torch.zeros(1, sum(sizes), device=dev, dtype=torch.float32)
+            d_out_b = torch.zeros(1, device=dev, dtype=torch.float32)
+        if B > 0 and x0.stride(1) == D and x0.stride(0) % 4 == 0 and x0.data_ptr() % 16 == 0 and (
+                B == 1 or x0.stride(0) >= m * D):
+            rows = x0.as_strided((B, m * D), (x0.stride(0), 1))  # the caller's rows, whatever their stride
+        else:
+            rows = x0.contiguous().view(B, m * D)
+        images_t = [pack_cin_weight_t(w, m) for w in weights]
+        dx0, dy = cin_backward(rows, m, D, images_t, sizes, ctx.activation, maps, dpooled=dpooled, dlogit=dl,
+                               out_w=out_w if dl is not None else None)
+        dws = dbs = [None] * nl
+        if any(need[5:]):
+            dws, dbs = cin_wgrad(rows, m, D, sizes, maps, dy)
+            dws = [g.view(w.shape) for g, w in zip(dws, weights)]
+        return (None, None, dx0.view(B, m, D) if need[2] else None,
+                d_out_w.view(out_w.shape) if need[3] else None, d_out_b if need[4] else None,
+                *[g if n else None for g, n in zip(dws, need[5:5 + nl])],
+                *[g if n else None for g, n in zip(dbs, need[5 + nl:])])
+
+
+def _detach(t):
+    return None if t is None else t.detach()
+
+
+def cin(x0: torch.Tensor, weights, biases=None, activation: str = "identity", out_w=None, out_b=None,
+        return_maps: bool = False):
     """The Compressed Interaction Network over dense rows x0 [B, m, D] (any row stride; field rows
     16-B aligned): x^k[b, n, d] = act(sum_{h, i} W_k[n, h m + i] x^{k-1}[b, h, d] x0[b, i, d] + bias_k[n])
     for weights[k] of shape [H_k, H_{k-1} m] (or nn.Conv1d's [H_k, H_{k-1} m, 1]), H_0 = m.  Returns
     pooled [B, sum H_k] (the sums over d, layers side by side); with out_w [sum H_k] and out_b [1]
-    also the logit pooled . out_w + out_b as (pooled, logit [B, 1])."""
+    also the logit pooled . out_w + out_b as (pooled, logit [B, 1]).
+
+    Differentiable: with grad enabled and x0, a weight, a bias, out_w or out_b requiring grad the call
+    goes through autograd (HIP backward: rk_cin_backward, rk_cin_wgrad); with plain tensors it is the
+    eval launch.  return_maps=True appends the list of feature maps x^k as [B, H_k, D] views (no
+    gradient flows through them)."""
     as_f32(x0, "x0")
     if activation not in CIN_ACT:
         raise ValueError(f"rankops.cin: activation must be one of {sorted(CIN_ACT)}, got {activation!r}")
@@ -322,16 +514,18 @@ def cin(x0: torch.Tensor, weights, biases=None, activation: str = "identity", ou
             raise ValueError(f"rankops.cin: biases[{k}] must have {w.shape[0]} elements")
         hprev = w.shape[0]
         sizes.append(hprev)
-    dev = x0.device
-    pooled = torch.empty(B, sum(sizes), device=dev, dtype=torch.float32)
-    logit = torch.empty(B, 1, device=dev, dtype=torch.float32) if out_w is not None else None
-    if B > 0:
-        images = [pack_cin_weight(w) for w in weights]
-        biases = [b if b is None or b.is_contiguous() else b.contiguous() for b in biases]
-        segs = [Segment(fptr(x0, i * x0.stride(1)), None, 0, x0.stride(0), 0, D, i * D) for i in range(m)]
-        cin_forward(segs, None, D, B, images, biases, sizes, activation, dev, out_w=out_w, out_b=out_b,
-                    pooled=pooled, cin_logit=logit)
-    return pooled if out_w is None else (pooled, logit)
+    grad = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (x0, out_w, out_b, *weights, *biases))
+    if grad:
+        *out, maps = _CinFn.apply(activation, len(weights), x0, out_w, out_b, *weights, *biases)
+    else:
+        maps = torch.empty(B, sum(sizes), D, device=x0.device, dtype=torch.float32) if return_maps else None
+        pooled, logit = _cin_launch(x0, weights, biases, sizes, activation, out_w, out_b, maps)
+        out = [pooled] if out_w is None else [pooled, logit]
+    if return_maps:
+        offs = [sum(sizes[:k]) for k in range(len(sizes))]
+        out.append([maps[:, o:o + h] for o, h in zip(offs, sizes)])
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def din_attention(query_ptr, ld_query, key_table, seq, seq_len, T, H, weights, use_softmax, out_ptr, ld_out,

@@ -545,6 +545,115 @@ def sharded_deepfm_train_forward(model, recv_rows, recv_idx, B):
     return _ShardedDeepFMTrain.apply(model, recv_rows, recv_idx, B, *deepfm_dense_params(model, units))
 
 
+# ---------------------------------------------------------------- xDeepFM
+
+class _NoSave:
+    """Stands in for an autograd context where a train-mode forward keeps nothing (no_grad)."""
+
+    def save_for_backward(self, *tensors):
+        pass
+
+
+def _xdeepfm_front(model, names, idx, maps: bool):
+    """The train forward's first launches: both CIN weight images packed on the stream into the
+    model's own buffers (a hipGraph replay repacks the weights Adam just stepped; common.CIN_PACKED
+    decides on the host and would freeze an image into the graph), then rk_cin_forward_train (or
+    rk_cin_forward when no maps are kept).  Returns (deep_in, fm1, cin_logit, pooled, maps, images_t)."""
+    D, F = model.embedding_dim, len(names)
+    B, dev = idx[0].shape[0], idx[0].device
+    second = ops.table_seg_array([model.second_order_embeddings[n].weight for n in names], idx,
+                                 [f * D for f in range(F)])
+    first = ops.table_seg_array([model.first_order_embeddings[n].weight for n in names], idx, list(range(F)))
+    own = model.__dict__.setdefault("_cin_train_images", {})
+    images, images_t = [], []
+    for k, c in enumerate(model.cin_layers):
+        own[k, 0] = ops.pack_cin_weight(c.weight, out=own.get((k, 0)))
+        images.append(own[k, 0])
+        if maps:
+            own[k, 1] = ops.pack_cin_weight_t(c.weight, F, out=own.get((k, 1)))
+            images_t.append(own[k, 1])
+    biases = [c.bias for c in model.cin_layers]
+    f32 = dict(device=dev, dtype=torch.float32)
+    deep_in = torch.empty(B, F * D, **f32)
+    fm1, cin_logit = torch.empty(B, 1, **f32), torch.empty(B, 1, **f32)
+    sizes = model.cin_layer_sizes
+    out = dict(out_w=model.cin_output_layer.weight, out_b=model.cin_output_layer.bias, deep_in=deep_in, fm1=fm1,
+               cin_logit=cin_logit)
+    if not maps:
+        ops.cin_forward(second, first, D, B, images, biases, sizes, model.cin_activation, dev, **out)
+        return deep_in, fm1, cin_logit, None, None, None
+    pooled = torch.empty(B, sum(sizes), **f32)
+    saved = torch.empty(B, sum(sizes), D, **f32)
+    ops.cin_forward_train(second, first, D, B, images, biases, sizes, model.cin_activation, dev, saved, pooled=pooled,
+                          **out)
+    return deep_in, fm1, cin_logit, pooled, saved, images_t
+
+
+class _XDeepFMTrain(torch.autograd.Function):
+    """XDeepFM forward + backward in train mode: rk_cin_forward_train (gather, first-order sum, the
+    CIN with its maps kept, pooling, cin_output_layer), DeepFM's train tail with fm2 = cin_logit;
+    backward: the tail, cin_output_layer (rk_logit_head_backward on the kept pooled), rk_cin_backward
+    (dx0 + the deep stack's input gradient in its epilogue), rk_cin_wgrad, the embedding gradients.
+    Inputs after the fixed arguments: first-order tables, second-order tables, deepfm_dense_params,
+    the CIN weights, the CIN biases, cin_output_layer's weight and bias."""
+
+    @staticmethod
+    def forward(ctx, model, names, idx, *params):
+        deep_in, fm1, cin_logit, pooled, maps, images_t = _xdeepfm_front(model, names, idx, True)
+        prob, total, deep = deepfm_tail_forward(ctx, model, deep_in, fm1, cin_logit)
+        ctx.names, ctx.idx = names, idx
+        ctx.cin = (pooled, maps, images_t)
+        return prob, total, fm1, cin_logit, deep
+
+    @staticmethod
+    def backward(ctx, dprob, dtotal, dfm1_o, dcin_o, ddeep_o):
+        model = ctx.model
+        deep_in, dfm1, dcin, d_deep_in, dense_grads = deepfm_tail_backward(ctx, dprob, dtotal, dfm1_o, dcin_o, ddeep_o)
+        pooled, maps, images_t = ctx.cin
+        B, dev = deep_in.shape[0], deep_in.device
+        D, F = model.embedding_dim, len(ctx.names)
+        out_w = model.cin_output_layer.weight
+        d_out_w = torch.empty_like(out_w)
+        d_out_b = torch.empty(1, device=dev, dtype=torch.float32)
+        ops.logit_head_backward(dcin, None, None, pooled, None, out_w, None, None, d_out_w, d_out_b)
+        sizes = model.cin_layer_sizes
+        d_second, dy = ops.cin_backward(deep_in, F, D, images_t, sizes, model.cin_activation, maps, dlogit=dcin,
+                                        out_w=out_w, dx0_add=d_deep_in)
+        ws = model.__dict__.get("_cin_wgrad_ws")
+        if ws is None or ws.device != dev:
+            ws = model.__dict__["_cin_wgrad_ws"] = ops.cin_wgrad_workspace(F, sizes, dev)
+        dws, dbs = ops.cin_wgrad(deep_in, F, D, sizes, maps, dy, workspace=ws)
+        dws = [g.view(c.weight.shape) for g, c in zip(dws, model.cin_layers)]
+        w2 = [model.second_order_embeddings[n].weight for n in ctx.names]
+        w1 = [model.first_order_embeddings[n].weight for n in ctx.names]
+        if model.sparse_grad:  # both table sets in one packing launch
+            g = sparse_embedding_grads(w1 + w2, [[(i, dfm1, 0)] for i in ctx.idx]
+                                       + [[(i, d_second, f * D)] for f, i in enumerate(ctx.idx)])
+            g1, g2 = g[:F], g[F:]
+        else:
+            g2 = embedding_grads(w2, ctx.idx, 0, d_second)
+            g1 = embedding_grads(w1, ctx.idx, 0, dfm1, cols=[0] * F)
+        return (None, None, None, *g1, *g2, *dense_grads, *dws, *dbs, d_out_w, d_out_b)
+
+
+def xdeepfm_train_forward(model, names, idx, grad: bool = True):
+    """XDeepFM train-mode forward: (probability, total_logit, linear_logit, cin_logit, deep_logit)
+    attached to _XDeepFMTrain when `grad`; otherwise the same launches with nothing kept."""
+    if not grad:
+        deep_in, fm1, cin_logit, *_ = _xdeepfm_front(model, names, idx, False)
+        prob, total, deep = deepfm_tail_forward(_NoSave(), model, deep_in, fm1, cin_logit)
+        return prob, total, fm1, cin_logit, deep
+    units = deep_units(model.deep_layers)
+    dense = deepfm_dense_params(model, units)
+    if any(c.bias is None for c in model.cin_layers) or model.cin_output_layer.bias is None:
+        raise NotImplementedError("rankops XDeepFM training expects biased CIN and output layers")
+    params = ([model.first_order_embeddings[n].weight for n in names]
+              + [model.second_order_embeddings[n].weight for n in names] + dense
+              + [c.weight for c in model.cin_layers] + [c.bias for c in model.cin_layers]
+              + [model.cin_output_layer.weight, model.cin_output_layer.bias])
+    return _XDeepFMTrain.apply(model, names, idx, *params)
+
+
 # ---------------------------------------------------------------- DIN
 
 def din_units(model):

@@ -5,7 +5,8 @@ The reference's README lists the model; its script is not in the snapshot, so th
 one, in the conventions of the reference's DeepFM (algorithm/DeepFM/deepfm.py):
 
 `XDeepFM(vocab_dir, embedding_dim=8, hidden_units=None, cin_layer_sizes=None,
-         cin_activation="identity", dropout_rate=0.1, batch_norm=True, *, vocab_sizes=None)`
+         cin_activation="identity", dropout_rate=0.1, batch_norm=True, *, vocab_sizes=None,
+         trainable=False, sparse_grad=False)`
 `forward(category) -> (probability, total_logit, linear_logit, cin_logit, deep_logit)`, each [B, 1].
 
 Modules are created in the order first_order_embeddings, second_order_embeddings, deep_layers,
@@ -22,14 +23,21 @@ cin_output_layer = Linear(sum H_k, 1).  With x0 = the stacked second-order rows 
 
 Launches (eval): rk_cin_forward (row gather, first-order sum, every CIN layer on FP32 MFMA with the
 feature maps in LDS, pooling, cin_output_layer), then the deep tail (common.tail_launches /
-run_tail) whose head epilogue is DeepFM's with fm2 = cin_logit.  Training is not implemented.
+run_tail) whose head epilogue is DeepFM's with fm2 = cin_logit.
+
+Training is opt-in: `XDeepFM(..., trainable=True)` in train mode returns the five outputs attached to
+autograd (rankops.train._XDeepFMTrain: rk_cin_forward_train keeps the feature maps, DeepFM's train
+tail with batch statistics and Dropout, then rk_cin_backward and rk_cin_wgrad), and under no_grad
+runs the same forward keeping nothing; `sparse_grad=True` hands the tables sparse COO gradients
+(rankops.SparseAdam) as in DeepFM.  The default (trainable=False) raises NotImplementedError in train
+mode, as before.  Neither flag adds, reorders or re-initialises a parameter.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from . import common, ops
+from . import common, ops, train
 from .common import EngineModule, Layer, check_eval, run_tail, table_rows
 from .deepfm import WECHAT_FIELDS
 
@@ -40,8 +48,11 @@ _FM1_SLOT, _CIN_SLOT = 14, 17
 
 class XDeepFM(EngineModule):
     def __init__(self, vocab_dir, embedding_dim=8, hidden_units=None, cin_layer_sizes=None,
-                 cin_activation="identity", dropout_rate=0.1, batch_norm=True, *, vocab_sizes=None):
+                 cin_activation="identity", dropout_rate=0.1, batch_norm=True, *, vocab_sizes=None,
+                 trainable=False, sparse_grad=False):
         super().__init__()
+        self.trainable = bool(trainable)      # train mode runs the HIP train forward / backward (rankops.train)
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         if hidden_units is None:
             hidden_units = [512, 256, 128]
         if cin_layer_sizes is None:
@@ -85,6 +96,7 @@ class XDeepFM(EngineModule):
             self.cin_layers.append(nn.Conv1d(hprev * self.num_categories, h, 1))
             hprev = h
         self.cin_output_layer = nn.Linear(sum(self.cin_layer_sizes), 1)
+        self._dropout = train.DropoutStreams()
 
     def _indices(self, category):
         names = list(self.second_order_embeddings)
@@ -167,11 +179,15 @@ class XDeepFM(EngineModule):
         return run
 
     def forward(self, category):
-        check_eval(self)  # training (the CIN backward) is not implemented
+        if not self.trainable:
+            check_eval(self)  # train mode is opt-in (trainable=True)
         names, idx = self._indices(category)
         B, dev = idx[0].shape[0], idx[0].device
         if B == 0:
             return common.empty_rows(dev, 5)
+        if self.training:  # BatchNorm batch statistics, Dropout, HIP backward (rankops.train)
+            grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+            return train.xdeepfm_train_forward(self, names, idx, grad)
         stream = ops._lib.raw_stream(dev)
         built = None
         own = all(t is category[n] for t, n in zip(idx, names))  # no converted copies: addresses are the caller's

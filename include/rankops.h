@@ -50,6 +50,8 @@
  *   rk_cin_forward, rk_cin_pack_weight  xDeepFM's front end in one launch: row gather, first-order sum,
  *                      the Compressed Interaction Network, its pooling and output layer (the
  *                      reference lists the model, its script is not in the snapshot)
+ *   rk_cin_forward_train, rk_cin_pack_weight_t, rk_cin_backward, rk_cin_wgrad  xDeepFM training:
+ *                      the CIN forward keeping its maps, its data backward and weight gradients
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
  *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
  *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
@@ -728,6 +730,44 @@ int rk_cin_forward(const rk_segment* second_order, const rk_segment* first_order
                    const int32_t* layer_sizes, int32_t num_layers, int32_t activation,
                    const float* out_w, const float* out_b, float* deep_in, int64_t ld_deep, float* fm1,
                    float* pooled, int64_t ld_pooled, float* cin_logit, void* stream);
+
+/* ---- xDeepFM training: the CIN's train forward, data backward and weight gradient ---- */
+/* rk_cin_forward that also writes every layer's feature maps for the backward:
+ *   maps[(b * hsum + off_k + n) * dim + d] = x^k[b, n, d],  hsum = sum layer_sizes   (16-B aligned,
+ * batch * hsum * dim floats).  Every other argument, output and bit as rk_cin_forward.          */
+int rk_cin_forward_train(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                         int32_t dim, int64_t batch, const float* const* weights, const float* const* biases,
+                         const int32_t* layer_sizes, int32_t num_layers, int32_t activation,
+                         const float* out_w, const float* out_b, float* deep_in, int64_t ld_deep, float* fm1,
+                         float* pooled, int64_t ld_pooled, float* cin_logit, float* maps, void* stream);
+
+/* W [n, hprev * num_fields] (row stride ldw) transposed and field-major for rk_cin_backward: the
+ * matrix A[i * pad16(hprev) + h][n] = W[n][h * num_fields + i], zero padded, in rk_cin_pack_weight's
+ * tile order; out: num_fields * pad16(hprev) * pad16(n) floats, 16-B aligned.                    */
+int rk_cin_pack_weight_t(const float* w, int64_t ldw, int32_t n, int32_t hprev, int32_t num_fields, float* out,
+                         void* stream);
+
+/* The CIN's data backward in one launch.  x0 [batch, ld_x0]: the rows (field i at column i * dim),
+ * maps: rk_cin_forward_train's, weights_t[k]: rk_cin_pack_weight_t images.  The gradient of
+ * pooled[b, j] is dpooled[b, j] (may be NULL) + dlogit[b] * out_w[j] (dlogit may be NULL; one of the
+ * two is required).  Writes dx0 [batch, ld_dx0] (+ dx0_add [batch, ld_add] when given) and
+ * dy[(b * hsum + off_k + n) * dim + d] = dL/dy^k (the pre-activation gradients rk_cin_wgrad reads;
+ * ReLU's derivative is maps > 0).  FP32 MFMA, fixed summation order, no atomics.  Envelope, errors
+ * and batch == 0 as rk_cin_forward; rows 16-B aligned with strides % 4 == 0.                     */
+int rk_cin_backward(const float* x0, int64_t ld_x0, int32_t num_fields, int32_t dim, int64_t batch,
+                    const float* const* weights_t, const int32_t* layer_sizes, int32_t num_layers,
+                    int32_t activation, const float* maps, const float* dpooled, int64_t ld_dpooled,
+                    const float* dlogit, const float* out_w, const float* dx0_add, int64_t ld_add, float* dx0,
+                    int64_t ld_dx0, float* dy, void* stream);
+
+/* dW_k [layer_sizes[k], layer_sizes[k-1] * num_fields] (contiguous) and dbias_k [layer_sizes[k]]
+ * (dbias or dbias[k] may be NULL) of every layer from x0, maps and rk_cin_backward's dy: slabs of the
+ * batch * dim reduction go to `workspace` (rk_cin_wgrad_workspace_floats: a fixed number of slabs,
+ * independent of the batch) and are added in slab order.  batch == 0: zeroed gradients, RK_OK.   */
+int64_t rk_cin_wgrad_workspace_floats(int32_t num_fields, const int32_t* layer_sizes, int32_t num_layers);
+int rk_cin_wgrad(const float* x0, int64_t ld_x0, int32_t num_fields, int32_t dim, int64_t batch,
+                 const int32_t* layer_sizes, int32_t num_layers, const float* maps, const float* dy,
+                 float* const* dw, float* const* dbias, float* workspace, int64_t workspace_floats, void* stream);
 
 /* ---- table-sharded DeepFM, the local steps around the all-to-alls (rankops.sharded; the
  * reference's DeepFM.forward, deepfm.py:121-151, runs on one device) ---- */

@@ -12,7 +12,14 @@ are compared before anything is timed.
 From the shapes the tool computes the CIN's flops, 2 D sum_k H_k H_{k-1} m per sample, and reports
 the kernel's rate as a share of the 157.3 TF FP32 matrix peak of the MI355X (the MFMA FP32 peak, not
 a measured ceiling).  `--batches 2048,8192` measures other batch sizes.  Needs a GPU; prints one JSON
-line at the end."""
+line at the end.
+
+The training leg (`train_*` keys; `--no-train` skips it) times one whole step at the same four points:
+XDeepFM(trainable=True) train forward + BCE + backward + rankops.Adam, eager and as a replayed hipGraph,
+alternated with the float32 torch restatement of the model (the same modules, the CIN as
+tests/xdeepfm_ref.cin with the outer product materialised) under torch autograd with torch.optim.Adam,
+on the same rows, in the same process.  The first step's loss of the two is compared before timing."""
+import copy
 import json
 import os
 import sys
@@ -111,6 +118,82 @@ def measure(fields, D, B):
     return r
 
 
+class TorchXDeepFM(torch.nn.Module):
+    """The float32 torch restatement of a rankops.XDeepFM for the training baseline: a deep copy of
+    its modules run by torch (embeddings, tests/xdeepfm_ref.cin, the deep layers as they are)."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.m = copy.deepcopy(model)
+
+    def forward(self, cat):
+        m = self.m
+        names = list(m.second_order_embeddings)
+        linear = torch.cat([m.first_order_embeddings[n](cat[n]) for n in names], dim=1).sum(dim=1, keepdim=True)
+        x0 = torch.stack([m.second_order_embeddings[n](cat[n]) for n in names], dim=1)
+        pooled = X.cin(x0, [c.weight for c in m.cin_layers], [c.bias for c in m.cin_layers], m.cin_activation,
+                       chunk=x0.shape[0])
+        cin_logit = m.cin_output_layer(pooled)
+        h = x0.reshape(x0.shape[0], -1)
+        for layer in m.deep_layers:
+            h = layer(h)
+        deep = m.deep_output_layer(h)
+        return torch.sigmoid(m.final_layer(torch.cat([linear, cin_logit, deep], dim=1)))
+
+
+def measure_train(fields, D, B):
+    case = ("time", fields, D, B)
+    sizes = fields if fields is not None else {f: H.WECHAT_VOCAB[f] for f in rankops.deepfm.WECHAT_FIELDS}
+    torch.manual_seed(42)
+    model = rankops.XDeepFM(None, embedding_dim=D, vocab_sizes=sizes, dropout_rate=0.0, trainable=True).cuda().train()
+    twin = TorchXDeepFM(model).cuda().train()  # dropout off on both sides: one loss to compare
+    cat = H.to_device(X.model_inputs(case), "cuda")
+    label = (torch.rand(B, generator=torch.Generator().manual_seed(5)) < 0.3).float().cuda()
+    crit = torch.nn.BCELoss()
+    opt = rankops.Adam(model.parameters(), lr=1e-3, capturable=True)
+    topt = torch.optim.Adam(twin.parameters(), lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = crit(model(cat)[0].squeeze(1), label)
+        loss.backward()
+        opt.step()
+        return loss
+
+    def torch_step():
+        topt.zero_grad(set_to_none=True)
+        loss = crit(twin(cat).squeeze(1), label)
+        loss.backward()
+        topt.step()
+        return loss
+
+    a, b = float(step().detach()), float(torch_step().detach())
+    assert abs(a - b) <= 1e-4 * (1 + abs(b)), f"first-step loss: engine {a}, torch {b}"
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        step()
+        step()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    opt.zero_grad(set_to_none=True)
+    with torch.cuda.graph(graph):
+        step()
+    iters = 10 if B * len(sizes) * D <= 4096 * 960 else 3
+    legs = {"train_step_eager_us": lambda: event_us(step, iters), "train_step_graph_us": lambda: event_us(graph.replay, iters),
+            "train_step_torch_us": lambda: event_us(torch_step, iters)}
+    r = {k: [] for k in legs}
+    for _ in range(ROUNDS):
+        for k, leg in legs.items():
+            r[k].append(round(leg(), 1))
+    r["train_torch_vs_graph"] = round(min(r["train_step_torch_us"]) / min(r["train_step_graph_us"]), 2)
+    r["train_torch_vs_eager"] = round(min(r["train_step_torch_us"]) / min(r["train_step_eager_us"]), 2)
+    r["train_first_loss"] = [a, b]
+    del graph, model, twin, opt, topt
+    torch.cuda.empty_cache()
+    return r
+
+
 def main():
     assert torch.cuda.is_available(), "xdeepfm_time needs a ROCm GPU"
     rankops.load_library()
@@ -122,6 +205,8 @@ def main():
     for name, (fields, D) in SHAPES.items():
         for B in batches:
             r = measure(fields, D, B)
+            if "--no-train" not in sys.argv[1:]:
+                r.update(measure_train(fields, D, B))
             result[f"{name}_B{B}"] = r
             print(f"{name} B {B}: " + ", ".join(f"{k} {v}" for k, v in r.items()), flush=True)
     result["sclk_after"] = shader_clock()
