@@ -201,13 +201,21 @@ struct LayerPipe {
   }
 };
 
+// The default of mlp_layer's `Sink`: the epilogue writes the layer's output to LDS (and `store`).
+struct LdsSink {
+  __device__ __forceinline__ void take(int j, int r, int row, float z) const {}
+};
+
 // One layer (weights already in flight in P) over RT row tiles of 16 rows: each weight float4
 // feeds RT x 4 MFMAs.  kchunks = Kp / 16 (a multiple of 4).
-template <int TPW, int RT, int PD, bool STORE>
+// Sink (mmoe.hip): a type other than LdsSink receives every finished element instead of `out` —
+// sink->take(j, r, row, z) with z the epilogue's value of column tile j (of TPW), accumulator
+// register r, LDS row `row` (0 in the pad columns) — and nothing is written to LDS or `store`.
+template <int TPW, int RT, int PD, bool STORE, class Sink = LdsSink>
 __device__ __forceinline__ void mlp_layer(LayerPipe& P, const rk_mlp_layer& L, const float* __restrict__ in,
                                           int ldin, float* __restrict__ out, int ldout, int Kp, int wave, int lane,
                                           int64_t m0, int rows, int dbg_mark = 0,
-                                          unsigned long long dbg_t0 = 0) {
+                                          unsigned long long dbg_t0 = 0, Sink* sink = nullptr) {
   const int li = lane & 15, kq = 4 * (lane >> 4);
   const int kchunks = Kp / 16;
   f32x4_t acc[TPW][RT];
@@ -305,9 +313,14 @@ __device__ __forceinline__ void mlp_layer(LayerPipe& P, const rk_mlp_layer& L, c
           const int row = 16 * t + (lane >> 4) * 4 + r;
           const float v = col_apply(L, ep, DICE, acc[j][t][r], RES, res[t][r]);
           const float z = real ? v : 0.f;
-          out[row * ldout + n] = z;  // padded columns [n, Np) become the next layer's zero K pad
-          if constexpr (STORE)
-            if (store && real && row < rows) store[(m0 + row) * ld_store + n] = z;
+          if constexpr (std::is_same_v<Sink, LdsSink>) {
+            out[row * ldout + n] = z;  // padded columns [n, Np) become the next layer's zero K pad
+            if constexpr (STORE)
+              if (store && real && row < rows) store[(m0 + row) * ld_store + n] = z;
+          } else {
+            static_assert(RT == 1 && !STORE, "a sink takes one row tile and no store");
+            sink->take(j, r, row, z);
+          }
         }
     }
   };

@@ -1,0 +1,430 @@
+// MMoE (Multi-gate Mixture-of-Experts, Ma et al., KDD 2018) eval forward in one launch, on the
+// fused-MLP machinery of mlp_core.h: 16 rows per workgroup of 16 waves, FP32 MFMA
+// (v_mfma_f32_16x16x4_f32), fragment-major packed weights streamed through the 8-slot ring.
+//
+//   x     = the gathered row (rk_concat_gather's column map, as mlp_gather_kernel)
+//   g_k   = softmax_e(gate_k(x))                  one GEMM over the K stacked gates, [K E, width]
+//   f_e   = expert_e(x)                           E stacks of Linear + ReLU, one after another
+//   m_k   = sum_e g_k[e] f_e                      behind every expert's last layer, from its registers
+//   logit_k = head_k(tower_k(m_k)),  prob_k = sigmoid(logit_k)
+//
+// Phases of a workgroup (a barrier after each layer; the next layer's weight ring is issued before
+// that barrier, LayerPipe::prepare):
+//   1. wave w gathers row m0 + w into xs (stays there: every expert's first layer reads it)
+//   2. gate GEMM xs -> gs (waves 0..3 own its <= 4 column tiles), then the softmax per (row, task),
+//      maximum subtracted, its weights left transposed in gt
+//   3. experts e = 0..E-1: layers ping-pong ha / hb; the last layer has no LDS output: its epilogue
+//      hands the wave's finished tiles back in registers (TileSink), and each lane adds
+//      g[row][k][e] * z into its own elements of the per-task mixtures mt.  [B, E, H] exists
+//      nowhere; e ascends, so two runs give the same bits.
+//   4. per task k: the lane's mixture elements -> ha (and `mixed`), tower layers ha / hb, then the
+//      head (one wave per row).
+// The mixtures live in LDS, not in registers: a 16-wave workgroup has 128 VGPRs per lane, which
+// mlp_layer's ring, accumulators and operands fill (mlp_gather_kernel: 126), and K x TPW x 4
+// accumulators kept across the experts' layers went to scratch (240 B per lane at 4 tasks).  In mt
+// every element belongs to one lane (the MFMA accumulator layout, the 4 rows of a register
+// quadruple contiguous: one conflict-free 16-byte read and write per tile and task), so no barrier
+// guards it.  mt holds T tasks (the host fits as many as the 160 KiB allow); with T < K steps 3 and
+// 4 run once per group of T tasks.
+//
+// LDS (floats): xs [16][pad64(width) + 8], ha and hb [16][max pad64(hidden) + 8], gs [16][64 + 8] (the
+// gate logits), gt [64][16] (the gate weights, gt[(e K + k) 16 + row]), mt [T][pad64(H)][16]
+// (mt[(i pad64(H) + n) 16 + row]).
+#include "mlp_core.h"
+
+namespace rk {
+
+constexpr int kMmSegs = 16;
+constexpr int kMmCols = 256;
+constexpr int kMmMaxExperts = 16;
+constexpr int kMmMaxTasks = 8;
+constexpr int kMmMaxGates = 64;  // num_tasks * num_experts: the gate GEMM's columns (4 tiles)
+constexpr int kMmMaxDepth = 3;
+constexpr int kMmLayers = (kMmMaxExperts + kMmMaxTasks) * kMmMaxDepth;
+constexpr int kMmLdG = kMmMaxGates + kMlpLdPad;
+
+struct MmoeArgs {
+  rk_segment segs[kMmSegs];
+  uint8_t col_seg[kMmCols], col_off[kMmCols];  // 255: no segment
+  rk_mmoe_layer layers[kMmLayers];             // expert e layer l at [e De + l], tower k layer l at [E De + k Dt + l]
+  rk_mmoe_layer gate;                          // the stacked gates [K E, width]
+  const float* head_w[kMmMaxTasks];
+  const float* head_b[kMmMaxTasks];
+  int64_t M;
+  int width, E, K, De, Dt, H;
+  int has_head;
+  int ldx, ldh;  // LDS row strides (floats)
+  int T;         // tasks mixed per pass over the experts (mt's capacity)
+  float* logits;
+  float* probs;
+  float* mixed;
+  float* gate_probs;
+  uint32_t* flags;
+};
+static_assert(sizeof(MmoeArgs) <= 4096, "kernel arguments beyond 4 KiB");
+
+// The rk_mlp_layer view of a compact descriptor over an input of K columns (Linear + bias + act).
+__device__ __forceinline__ rk_mlp_layer mm_view(const rk_mmoe_layer& d, int K) {
+  rk_mlp_layer L = {};
+  L.w = d.w;
+  L.ldw = pad64(K);
+  L.n = d.n;
+  L.act = d.act == RK_ACT_RELU ? RK_ACT_RELU : RK_ACT_NONE;  // (the epilogue's Dice / residual variants fold away)
+  L.bias = d.bias;
+  return L;
+}
+
+// mlp_layer's sink of an expert's last layer: the wave's finished tiles stay in registers.
+// (One type per tile count: with one object for both, the compiler merged the two layer variants'
+// epilogue stores behind a runtime index and kept the tiles in scratch.)
+template <int TPW>
+struct TileSink {
+  f32x4_t z[TPW];
+  __device__ __forceinline__ void take(int j, int r, int row, float v) { z[j][r] = v; }
+};
+
+// mlp_rows' per-layer dispatch: wave w owns column tiles w and w + 16; a wave without a tile takes
+// part in the active waves' lockstep barriers.
+__device__ __forceinline__ void mm_prepare(LayerPipe& pipe, const rk_mlp_layer& L, int K, int wave, int lane) {
+  const int nt = pad64(L.n) / 16, kch = pad64(K) / 16;
+  if (wave + kMlpWaves < nt)
+    pipe.prepare<2, 4>(L, kch, wave, lane);
+  else if (wave < nt)
+    pipe.prepare<1, 8>(L, kch, wave, lane);
+}
+
+__device__ __forceinline__ void mm_layer(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin, float* out,
+                                         int ldout, int Kp, int wave, int lane) {
+  const int ntiles = pad64(L.n) / 16;
+  if (wave + kMlpWaves < ntiles) {
+    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
+  } else if (wave < ntiles) {
+    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
+  } else {
+    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
+  }
+}
+
+// The same with the output tiles left in z (zero for a tile the wave does not own), nothing in LDS.
+__device__ __forceinline__ void mm_layer_tiles(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin,
+                                               int Kp, int wave, int lane, f32x4_t (&z)[2]) {
+  const int ntiles = pad64(L.n) / 16;
+  z[0] = z[1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  if (wave + kMlpWaves < ntiles) {
+    TileSink<2> f;
+    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
+    z[0] = f.z[0];
+    z[1] = f.z[1];
+  } else if (wave < ntiles) {
+    TileSink<1> f;
+    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
+    z[0] = f.z[0];
+  } else {
+    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
+  }
+}
+
+__global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+  const int64_t m0 = (int64_t)blockIdx.x * kMlpRows;
+  const int rows = (int)min<int64_t>(kMlpRows, a.M - m0);
+  float* const xs = sm;
+  float* const ha = xs + kMlpRows * a.ldx;
+  float* const hb = ha + kMlpRows * a.ldh;
+  float* const gs = hb + kMlpRows * a.ldh;
+  float* const gt = gs + kMlpRows * kMmLdG;
+  float* const mt = gt + kMlpRows * kMmMaxGates;
+  const int width = a.width, E = a.E, K = a.K, De = a.De, Dt = a.Dt, H = a.H;
+  const int K0p = pad64(width);
+  const bool live = wave < rows;
+  const int64_t b = m0 + wave;
+
+  // 1. the row gather (mlp_gather_kernel's stage): indices first, the values after
+  float v[kMmCols / 64];
+  int64_t r[kMmCols / 64];
+  int sg[kMmCols / 64];
+#pragma unroll
+  for (int i = 0; i < kMmCols / 64; ++i) {
+    const int c = lane + 64 * i;
+    sg[i] = live && c < width ? a.col_seg[c] : 255;
+    r[i] = b;
+    if (sg[i] != 255) {
+      const rk_segment& g = a.segs[sg[i]];
+      if (g.idx) {
+        r[i] = g.idx[b * g.idx_stride];
+        if (r[i] < 0 || r[i] >= g.rows) {
+          flag_oob(a.flags);
+          r[i] = -1;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kMmCols / 64; ++i) {
+    v[i] = 0.f;
+    if (sg[i] != 255 && r[i] >= 0) {
+      const rk_segment& g = a.segs[sg[i]];
+      v[i] = g.src[r[i] * g.src_ld + a.col_off[lane + 64 * i]];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);  // the gather's loads stay ahead of the weight ring
+
+  LayerPipe pipe;
+  auto expert = [&](int e, int l) { return mm_view(a.layers[e * De + l], l ? a.layers[e * De + l - 1].n : width); };
+  auto tower = [&](int k, int l) {
+    return mm_view(a.layers[E * De + k * Dt + l], l ? a.layers[E * De + k * Dt + l - 1].n : H);
+  };
+  // The lane index behind an empty asm, taken once per layer: what a layer derives from it (LDS and
+  // weight addresses, output offsets) is then computed where it is used.  Derived from `lane` itself
+  // the compiler hoists all of it out of the expert / task loops and spills it around every layer.
+  auto lane_now = [&]() {
+    int x = lane;
+    asm volatile("" : "+v"(x));
+    return x;
+  };
+  auto close_layer = [&]() {
+    mlp_lds_barrier();
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  // 2. the gates: one GEMM over the K stacked gate weights, then softmax over e per (row, task)
+  const rk_mlp_layer LG = mm_view(a.gate, width);
+  mm_prepare(pipe, LG, width, wave, lane);
+#pragma unroll
+  for (int i = 0; i < kMmCols / 64; ++i) {
+    const int c = lane + 64 * i;
+    if (c < K0p) xs[wave * a.ldx + c] = v[i];  // dead rows and pad columns stage zeros
+  }
+  mlp_lds_barrier();
+  mm_layer(pipe, LG, xs, a.ldx, gs, kMmLdG, K0p, wave, lane);
+  {
+    const rk_mlp_layer L0 = expert(0, 0);
+    mm_prepare(pipe, L0, width, wave, lane);
+  }
+  close_layer();
+  if (tid < kMlpRows * K) {
+    const int row = tid / K, k = tid % K;
+    float* const p = gs + row * kMmLdG + k * E;
+    float mx = p[0];
+    for (int e = 1; e < E; ++e) mx = fmaxf(mx, p[e]);
+    float s = 0.f;
+    for (int e = 0; e < E; ++e) {
+      const float ex = expf(p[e] - mx);
+      p[e] = ex;
+      s += ex;
+    }
+    for (int e = 0; e < E; ++e) {
+      const float w = p[e] / s;
+      gt[(e * K + k) * kMlpRows + row] = w;
+      if (a.gate_probs && row < rows) a.gate_probs[((m0 + row) * K + k) * E + e] = w;
+    }
+  }
+  mlp_lds_barrier();
+
+  const int Hp = pad64(H), ntH = Hp / 16;
+  for (int k0 = 0; k0 < K; k0 += a.T) {
+    const int kg = min(a.T, K - k0);
+    const bool more = k0 + a.T < K;  // another pass over the experts follows
+
+    // 3. the experts; the mix after the last layer's epilogue
+    for (int e = 0; e < E; ++e) {
+      for (int l = 0; l < De; ++l) {
+        const int ln = lane_now();
+        const rk_mlp_layer L = expert(e, l);
+        const int Kp = pad64(l ? a.layers[e * De + l - 1].n : width);
+        const float* in = l == 0 ? xs : (l & 1) ? ha : hb;
+        float* out = (l & 1) ? hb : ha;
+        if (l + 1 < De) {
+          mm_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
+          const rk_mlp_layer N = expert(e, l + 1);
+          mm_prepare(pipe, N, L.n, wave, ln);
+        } else {
+          f32x4_t z[2];
+          mm_layer_tiles(pipe, L, in, l == 0 ? a.ldx : a.ldh, Kp, wave, ln, z);
+          if (e + 1 < E || (more && !(a.has_head && Dt > 0))) {
+            const rk_mlp_layer N = expert(e + 1 < E ? e + 1 : 0, 0);
+            mm_prepare(pipe, N, width, wave, ln);
+          } else if (a.has_head && Dt > 0) {
+            const rk_mlp_layer N = tower(k0, 0);
+            mm_prepare(pipe, N, H, wave, ln);
+          }
+          const int q4 = (ln >> 4) * 4;  // the lane's first row
+          for (int i = 0; i < kg; ++i) {
+            const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(gt + (e * K + k0 + i) * kMlpRows + q4);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const int t = wave + kMlpWaves * j;
+              if (t < ntH) {
+                f32x4_t* const mp = reinterpret_cast<f32x4_t*>(mt + (i * Hp + 16 * t + (ln & 15)) * kMlpRows + q4);
+                f32x4_t m = {0.f, 0.f, 0.f, 0.f};
+                if (e) m = *mp;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) m[q] = __builtin_fmaf(gv[q], z[j][q], m[q]);
+                *mp = m;
+              }
+            }
+          }
+        }
+        close_layer();
+      }
+    }
+
+    // 4. per task: the mixture to LDS row-major (and `mixed`), the tower, the head
+    for (int kk = 0; kk < kg; ++kk) {
+      const int k = k0 + kk;
+      const int lm = lane_now();
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int t = wave + kMlpWaves * j;
+        if (t < ntH) {
+          const int n = 16 * t + (lm & 15);
+          const f32x4_t mv = *reinterpret_cast<const f32x4_t*>(mt + (kk * Hp + n) * kMlpRows + (lm >> 4) * 4);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int row = (lm >> 4) * 4 + q;
+            if (a.has_head) ha[row * a.ldh + n] = mv[q];  // pad columns hold zeros: the tower's zero K pad
+            if (a.mixed && n < H && row < rows) a.mixed[((m0 + row) * K + k) * H + n] = mv[q];
+          }
+        }
+      }
+      if (!a.has_head) continue;
+      mlp_lds_barrier();
+      for (int l = 0; l < Dt; ++l) {
+        const int ln = lane_now();
+        const rk_mlp_layer L = tower(k, l);
+        const int Kp = pad64(l ? a.layers[E * De + k * Dt + l - 1].n : H);
+        const float* in = (l & 1) ? hb : ha;
+        float* out = (l & 1) ? ha : hb;
+        mm_layer(pipe, L, in, a.ldh, out, a.ldh, Kp, wave, ln);
+        if (l + 1 < Dt) {
+          const rk_mlp_layer N = tower(k, l + 1);
+          mm_prepare(pipe, N, L.n, wave, ln);
+        } else if (kk + 1 < kg) {
+          const rk_mlp_layer N = tower(k + 1, 0);
+          mm_prepare(pipe, N, H, wave, ln);
+        } else if (more) {
+          const rk_mlp_layer N = expert(0, 0);
+          mm_prepare(pipe, N, width, wave, ln);
+        }
+        close_layer();
+      }
+      const float* fin = (Dt & 1) ? hb : ha;
+      const int Kh = Dt ? a.layers[E * De + k * Dt + Dt - 1].n : H;
+      if (live) {  // one wave per row
+        const float* hw = a.head_w[k];
+        float p = 0.f;
+        for (int n = lm; n < Kh; n += 64) p = __builtin_fmaf(fin[wave * a.ldh + n], hw[n], p);
+        p = wave_sum(p);
+        if (lm == 0) {
+          const float logit = p + a.head_b[k][0];
+          if (a.logits) a.logits[b * K + k] = logit;
+          if (a.probs) a.probs[b * K + k] = sigmoid_fast(logit);
+        }
+      }
+      mlp_lds_barrier();  // the next task's mixture overwrites ha
+    }
+  }
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+RK_API int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                           const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth,
+                           const float* gate_w, const float* gate_b, int32_t num_tasks, const rk_mmoe_layer* towers,
+                           int32_t tower_depth, const float* const* head_w, const float* const* head_b, float* logits,
+                           float* probs, float* mixed, float* gate_probs, void* stream) {
+  if (!segs || !experts || !gate_w || batch < 0 || nseg <= 0 || width <= 0 || num_experts <= 0 || num_tasks <= 0 ||
+      expert_depth <= 0 || tower_depth < 0 || (head_w != nullptr) != (head_b != nullptr) ||
+      (tower_depth > 0 && (!towers || !head_w)))
+    return fail(RK_ERR_INVALID, "rk_mmoe_forward: null pointer or negative size (batch %lld)", (long long)batch);
+  if (!head_w && (logits || probs)) return fail(RK_ERR_INVALID, "rk_mmoe_forward: logits / probs need the heads");
+  if (!(head_w ? (logits || probs || mixed || gate_probs) : (mixed || gate_probs)))
+    return fail(RK_ERR_INVALID, "rk_mmoe_forward: no output");
+  if (nseg > kMmSegs || width > kMmCols || num_experts > kMmMaxExperts || num_tasks > kMmMaxTasks ||
+      num_tasks * num_experts > kMmMaxGates || expert_depth > kMmMaxDepth || tower_depth > kMmMaxDepth)
+    return fail(RK_ERR_UNSUPPORTED,
+                "rk_mmoe_forward: %d segments (<= %d) over %d columns (<= %d), %d experts (<= %d) of depth %d (1..%d), "
+                "%d tasks (<= %d, tasks x experts <= %d), tower depth %d (<= %d)",
+                nseg, kMmSegs, width, kMmCols, num_experts, kMmMaxExperts, expert_depth, kMmMaxDepth, num_tasks,
+                kMmMaxTasks, kMmMaxGates, tower_depth, kMmMaxDepth);
+  MmoeArgs a = {};
+  int wide = kMlpPad;  // the widest hidden activation, padded
+  auto take = [&](const rk_mmoe_layer& d, rk_mmoe_layer& out, const char* what, int i, int l) {
+    if (!d.w || !aligned16(d.w) || d.n <= 0)
+      return fail(RK_ERR_INVALID, "rk_mmoe_forward: %s %d layer %d: weight null or misaligned, n = %d", what, i, l,
+                  d.n);
+    if (d.n > kMlpMaxN || (d.act != RK_ACT_NONE && d.act != RK_ACT_RELU))
+      return fail(RK_ERR_UNSUPPORTED, "rk_mmoe_forward: %s %d layer %d: n = %d (<= %d), activation %d (none / ReLU)",
+                  what, i, l, d.n, kMlpMaxN, d.act);
+    out = d;
+    wide = std::max(wide, pad64(d.n));
+    return (int)RK_OK;
+  };
+  for (int e = 0; e < num_experts; ++e)
+    for (int l = 0; l < expert_depth; ++l)
+      if (int rc = take(experts[e * expert_depth + l], a.layers[e * expert_depth + l], "expert", e, l)) return rc;
+  const int H = experts[expert_depth - 1].n;
+  for (int e = 1; e < num_experts; ++e)
+    if (experts[e * expert_depth + expert_depth - 1].n != H)
+      return fail(RK_ERR_INVALID, "rk_mmoe_forward: expert %d ends %d wide, expert 0 %d", e,
+                  experts[e * expert_depth + expert_depth - 1].n, H);
+  const int t0 = num_experts * expert_depth;
+  for (int k = 0; k < num_tasks; ++k) {
+    for (int l = 0; l < tower_depth; ++l)
+      if (int rc = take(towers[k * tower_depth + l], a.layers[t0 + k * tower_depth + l], "tower", k, l)) return rc;
+    if (head_w) {
+      if (!head_w[k] || !head_b[k]) return fail(RK_ERR_INVALID, "rk_mmoe_forward: head %d null", k);
+      a.head_w[k] = head_w[k];
+      a.head_b[k] = head_b[k];
+    }
+  }
+  if (!aligned16(gate_w)) return fail(RK_ERR_INVALID, "rk_mmoe_forward: gate image misaligned");
+  a.gate = rk_mmoe_layer{gate_w, gate_b, num_tasks * num_experts, RK_ACT_NONE};
+  for (int c = 0; c < kMmCols; ++c) {
+    a.col_seg[c] = 255;
+    a.col_off[c] = 0;
+  }
+  for (int i = 0; i < nseg; ++i) {
+    const rk_segment& sg = segs[i];
+    if (!sg.src || sg.dim <= 0 || sg.out_col < 0 || sg.out_col + sg.dim > width || (sg.idx && sg.rows <= 0) ||
+        sg.dim > 255)
+      return fail(RK_ERR_INVALID, "rk_mmoe_forward: segment %d invalid", i);
+    a.segs[i] = sg;
+    for (int c = sg.out_col; c < sg.out_col + sg.dim; ++c) {  // the last covering segment wins
+      a.col_seg[c] = (uint8_t)i;
+      a.col_off[c] = (uint8_t)(c - sg.out_col);
+    }
+  }
+  a.M = batch;
+  a.width = width;
+  a.E = num_experts;
+  a.K = num_tasks;
+  a.De = expert_depth;
+  a.Dt = tower_depth;
+  a.H = H;
+  a.has_head = head_w != nullptr;
+  a.ldx = pad64(width) + kMlpLdPad;
+  a.ldh = wide + kMlpLdPad;
+  a.logits = logits;
+  a.probs = probs;
+  a.mixed = mixed;
+  a.gate_probs = gate_probs;
+  // LDS: the activation buffers, the gates, and the mixtures of as many tasks as still fit
+  const size_t base = (size_t)kMlpRows * (a.ldx + 2 * a.ldh + kMmLdG + kMmMaxGates) * sizeof(float);
+  const size_t per_task = (size_t)kMlpRows * pad64(H) * sizeof(float);
+  if (base + per_task > 160 * 1024)
+    return fail(RK_ERR_UNSUPPORTED, "rk_mmoe_forward: widths need %zu B of LDS", base + per_task);
+  a.T = (int)std::min<size_t>(num_tasks, (160 * 1024 - base) / per_task);
+  const size_t shm = base + a.T * per_task;
+  a.flags = device_flags();
+  if (!a.flags) return fail(RK_ERR_RUNTIME, "rk_mmoe_forward: device not initialised (rk_init)");
+  if (batch == 0) return RK_OK;
+  const int64_t blocks = (batch + kMlpRows - 1) / kMlpRows;
+  if (blocks > INT32_MAX) return fail(RK_ERR_UNSUPPORTED, "rk_mmoe_forward: batch too large");
+  raise_lds_limit((const void*)mmoe_kernel, 160 * 1024);
+  mmoe_kernel<<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(a);
+  return check_launch("rk_mmoe_forward");
+}

@@ -22,7 +22,7 @@ RK_ERR_UNSUPPORTED = 4  # include/rankops.h
 RK_FLAG_INDEX_OOB = 1
 RK_ACT_NONE, RK_ACT_RELU, RK_ACT_LEAKY, RK_ACT_DICE, RK_ACT_PRELU = 0, 1, 2, 3, 4
 RK_MAX_SEGMENTS = 64
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class Segment(ctypes.Structure):
@@ -112,6 +112,10 @@ class SparseAdamTensor(ctypes.Structure):
 class PackBlock(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("add", c_void_p), ("dst", c_void_p), ("ld_src", c_int64), ("ld_add", c_int64),
                 ("rows", c_int64), ("dim", c_int32), ("reserved", c_int32)]
+
+
+class MmoeLayer(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("bias", c_void_p), ("n", c_int32), ("act", c_int32)]
 
 
 RK_MLP_MAX_LAYERS = 8
@@ -434,6 +438,9 @@ SIGNATURES = {
     "rk_cin_wgrad_workspace_floats": (c_int64, [c_int32, POINTER(c_int32), c_int32]),
     "rk_cin_wgrad": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int64, POINTER(c_int32), c_int32, c_void_p,
                                     c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int64, c_void_p]),
+    "rk_mmoe_forward": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
+                                       c_void_p, c_void_p, c_int32, POINTER(MmoeLayer), c_int32, POINTER(c_void_p),
+                                       POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rk_shard_gather_rows_split": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_void_p, c_int32, c_int64,
                                                   c_int64, c_int64, c_void_p, c_void_p]),
     "rk_shard_fm_assemble": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p,

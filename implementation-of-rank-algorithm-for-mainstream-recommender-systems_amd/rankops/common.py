@@ -417,6 +417,22 @@ def fused_mlp_fits(k0: int, widths) -> bool:
     return 16 * (need0 + 8 + need1 + 8) * 4 <= 160 * 1024  # rows padded by kMlpLdPad (mlp_core.h)
 
 
+def mmoe_fits(width: int, num_segments: int, num_experts: int, num_tasks: int, expert_units, tower_units) -> bool:
+    """Whether rk_mmoe_forward takes this shape (the mirror of its envelope and LDS check, csrc/mmoe.hip):
+    width <= 256 in at most 16 segments, E <= 16, K <= 8, K E <= 64, 1..3 expert layers, 0..3 tower layers,
+    every hidden width <= 512, and the activation buffers, the gates and one task's mixture within 160 KiB."""
+    expert_units, tower_units = list(expert_units), list(tower_units)
+    if not (0 < width <= 256 and 0 < num_segments <= 16 and 0 < num_experts <= 16 and 0 < num_tasks <= 8
+            and num_tasks * num_experts <= 64 and 1 <= len(expert_units) <= 3 and len(tower_units) <= 3):
+        return False
+    units = expert_units + tower_units
+    if min(units) <= 0 or max(units) > 512:
+        return False
+    ldx, ldh = _pad64(width) + 8, max(64, max(_pad64(n) for n in units)) + 8  # rows padded by kMlpLdPad
+    base = 16 * (ldx + 2 * ldh + (64 + 8) + 64) * 4
+    return base + 16 * _pad64(expert_units[-1]) * 4 <= 160 * 1024
+
+
 class PackedWeights:
     """Packed weight images (rk_mlp_pack_weight, or the `pack` given), held weakly per weight
     tensor object and rebuilt when its storage or version changes (load_state_dict, .to(),

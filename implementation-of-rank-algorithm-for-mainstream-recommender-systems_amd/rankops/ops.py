@@ -1633,3 +1633,130 @@ def fm_combine_backward(dprob, dtotal, dfm1_in, dfm2_in, ddeep_in, prob, fm1, fm
                                      ptr(fm1), ptr(fm2), ptr(deep), ptr(final_w), prob.shape[0], ptr(dfm1), ptr(dfm2),
                                      ptr(ddeep), ptr(dfinal_w), ptr(dfinal_b), _lib.stream_of(prob)),
           "rk_fm_combine_backward")
+
+
+# ---------------------------------------------------------------- MMoE (rk_mmoe_forward)
+
+# argument slots of rk_mmoe_forward patched per call (mmoe_forward_args)
+MMOE_LOGITS_SLOT, MMOE_PROBS_SLOT, MMOE_MIXED_SLOT, MMOE_GATES_SLOT = 14, 15, 16, 17
+
+
+def _mmoe_layer_array(stacks):
+    """[[(image, bias or None, n, act)…]…] -> one rk_mmoe_layer array, stack-major."""
+    flat = [l for stack in stacks for l in stack]
+    arr = (_lib.MmoeLayer * max(1, len(flat)))()
+    for d, (image, bias, n, act) in zip(arr, flat):
+        d.w, d.bias, d.n, d.act = image.data_ptr(), ptr(bias), int(n), ACT[act] if isinstance(act, str) else int(act)
+    return arr
+
+
+def mmoe_forward_args(segs, width, batch, experts, gate_image, gate_bias, num_tasks, towers, heads, device, *,
+                      logits=None, probs=None, mixed=None, gate_probs=None):
+    """The rk_mmoe_forward argument list (the stream last, None) and the ctypes arrays it points into.
+    experts: E stacks of equal depth, towers: K stacks of equal depth (or None), each a list of
+    (pack_mlp_weight image, bias or None, n, act); gate_image: the image of the K gate weights stacked
+    to [K E, width], gate_bias [K E] or None; heads: K (w [last width], b [1]) or None.  logits [14],
+    probs [15], mixed [16], gate_probs [17] and the stream [-1] are the per-call slots of a cached
+    forward."""
+    _lib.ensure_device(device)
+    arr = _as_seg_array(segs)
+    depth = len(experts[0]) if experts else 0
+    if any(len(s) != depth for s in experts):
+        raise ValueError("rankops.mmoe: every expert must have the same number of layers")
+    ex = _mmoe_layer_array(experts)
+    tdepth, tw, hw, hb = 0, None, None, None
+    if heads is not None:
+        towers = towers if towers is not None else [[] for _ in range(num_tasks)]
+        if len(towers) != num_tasks or len(heads) != num_tasks:
+            raise ValueError(f"rankops.mmoe: {num_tasks} gates need {num_tasks} towers and heads")
+        tdepth = len(towers[0])
+        if any(len(s) != tdepth for s in towers):
+            raise ValueError("rankops.mmoe: every tower must have the same number of layers")
+        tw = _mmoe_layer_array(towers) if tdepth else None
+        hw = (ctypes.c_void_p * num_tasks)(*[w.data_ptr() for w, _ in heads])
+        hb = (ctypes.c_void_p * num_tasks)(*[b.data_ptr() for _, b in heads])
+    args = [arr, len(arr), width, batch, ex, len(experts), depth, gate_image.data_ptr(), ptr(gate_bias), num_tasks,
+            tw, tdepth, hw, hb, ptr(logits), ptr(probs), ptr(mixed), ptr(gate_probs), None]
+    return args, (arr, ex, tw, hw, hb)
+
+
+def _mmoe_stack(layers, k_in, what):
+    """[(W, b)…] -> ([(image, bias, n, 'relu')…], output width), every Linear followed by ReLU."""
+    out = []
+    for l, (w, b) in enumerate(layers):
+        as_f32(w, f"{what} layer {l} weight")
+        if w.dim() != 2 or w.shape[1] != k_in:
+            raise ValueError(f"rankops.mmoe: {what} layer {l} weight must be [n, {k_in}], got {tuple(w.shape)}")
+        if b is not None and (as_f32(b, f"{what} layer {l} bias").dim() != 1 or b.shape[0] != w.shape[0]
+                              or not b.is_contiguous()):
+            raise ValueError(f"rankops.mmoe: {what} layer {l} bias must be a contiguous [{w.shape[0]}] tensor")
+        out.append((pack_mlp_weight(w), b.detach() if b is not None else None, w.shape[0], "relu"))
+        k_in = w.shape[0]
+    return out, k_in
+
+
+def mmoe(x: torch.Tensor, experts, gates, towers=None):
+    """Multi-gate mixture of experts on rows x [B, width] (float32, unit column stride, any row stride
+    >= width), in one launch (rk_mmoe_forward):
+
+        f_e = experts[e](x)                  experts: E lists of (W, b) — Linear + ReLU each, b may be None
+        g_k = softmax_e(x W_k^T + b_k)       gates: K (W [E, width], b or None)
+        m_k = sum_e g_k[e] f_e
+        logit_k = towers[k](m_k)             towers: K (hidden [(W, b)…], (w_out [1, ·], b_out)), hidden layers
+                                             Linear + ReLU
+
+    Returns (mixed [B, K, H], gate_probs [B, K, E]); with towers also (logits [B, K], probs [B, K]).
+    Eval only (no autograd)."""
+    as_f32(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"rankops.mmoe: x must be [B, width] with unit column stride, got {tuple(x.shape)}")
+    B, width = x.shape
+    dev = x.device
+    E, K = len(experts), len(gates)
+    if E == 0 or K == 0:
+        raise ValueError("rankops.mmoe: at least one expert and one gate")
+    stacks, H = [], None
+    for e, layers in enumerate(experts):
+        if len(layers) == 0:
+            raise ValueError(f"rankops.mmoe: expert {e} has no layer")
+        st, h = _mmoe_stack(layers, width, f"expert {e}")
+        if H is not None and h != H:
+            raise ValueError(f"rankops.mmoe: expert {e} ends {h} wide, expert 0 {H}")
+        stacks.append(st)
+        H = h
+    for k, (w, b) in enumerate(gates):
+        as_f32(w, f"gate {k} weight")
+        if tuple(w.shape) != (E, width) or (b is not None and tuple(as_f32(b, f"gate {k} bias").shape) != (E,)):
+            raise ValueError(f"rankops.mmoe: gate {k} must be (W [{E}, {width}], b [{E}] or None)")
+    gate_image = pack_mlp_weight(torch.cat([w.detach() for w, _ in gates], 0))
+    gate_bias = None
+    if any(b is not None for _, b in gates):
+        gate_bias = torch.cat([b.detach() if b is not None else torch.zeros(E, device=dev) for _, b in gates], 0)
+    tstacks = heads = None
+    if towers is not None:
+        if len(towers) != K:
+            raise ValueError(f"rankops.mmoe: {K} gates need {K} towers, got {len(towers)}")
+        tstacks, heads = [], []
+        for k, (hidden, (w_out, b_out)) in enumerate(towers):
+            st, last = _mmoe_stack(hidden, H, f"tower {k}")
+            as_f32(w_out, f"tower {k} output weight")
+            as_f32(b_out, f"tower {k} output bias")
+            if w_out.numel() != last or b_out.numel() != 1:
+                raise ValueError(f"rankops.mmoe: tower {k} output must be (w [1, {last}], b [1])")
+            tstacks.append(st)
+            heads.append((w_out.detach().reshape(-1).contiguous(), b_out.detach().reshape(1)))
+    mixed = torch.empty(B, K, H, device=dev, dtype=torch.float32)
+    gate_probs = torch.empty(B, K, E, device=dev, dtype=torch.float32)
+    logits = probs = None
+    if towers is not None:
+        logits = torch.empty(B, K, device=dev, dtype=torch.float32)
+        probs = torch.empty(B, K, device=dev, dtype=torch.float32)
+    if B > 0:
+        # (a segment holds at most 255 columns: the kernel's column map is one byte per column)
+        segs = [dense_segment(x, min(128, width - c), c, c) for c in range(0, width, 128)]
+        args, _keep = mmoe_forward_args(segs, width, B, stacks, gate_image, gate_bias, K,
+                                        tstacks, heads, dev, logits=logits, probs=probs, mixed=mixed,
+                                        gate_probs=gate_probs)
+        args[-1] = _lib.raw_stream(dev)
+        check(_lib.load().rk_mmoe_forward(*args), "rk_mmoe_forward")
+    return (mixed, gate_probs) if towers is None else (mixed, gate_probs, logits, probs)

@@ -52,6 +52,9 @@
  *                      reference lists the model, its script is not in the snapshot)
  *   rk_cin_forward_train, rk_cin_pack_weight_t, rk_cin_backward, rk_cin_wgrad  xDeepFM training:
  *                      the CIN forward keeping its maps, its data backward and weight gradients
+ *   rk_mmoe_forward    MMoE (multi-gate mixture of experts) eval forward in one launch: row gather,
+ *                      gates + softmax, experts with the mix in their last epilogue, towers, heads
+ *                      (the reference lists the model, its script is not in the snapshot)
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
  *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
  *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
@@ -100,7 +103,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 3
+#define RK_ABI_VERSION 4
 
 #define RK_OK 0
 #define RK_ERR_INVALID 1     /* bad argument (shape, null pointer, limit) */
@@ -730,6 +733,41 @@ int rk_cin_forward(const rk_segment* second_order, const rk_segment* first_order
                    const int32_t* layer_sizes, int32_t num_layers, int32_t activation,
                    const float* out_w, const float* out_b, float* deep_in, int64_t ld_deep, float* fm1,
                    float* pooled, int64_t ld_pooled, float* cin_logit, void* stream);
+
+/* ---- MMoE: multi-gate mixture of experts (Ma et al., KDD 2018), eval forward ---- */
+/* One Linear (+ ReLU) of an expert or a tower: w = the rk_mlp_pack_weight image of W [n, K] (K = the
+ * previous layer's n, or the row width / the experts' output width for a first layer), bias [n] or
+ * NULL, act RK_ACT_NONE or RK_ACT_RELU.                                                          */
+typedef struct rk_mmoe_layer {
+  const float* w;
+  const float* bias;
+  int32_t n;
+  int32_t act;
+} rk_mmoe_layer;
+
+/* The whole MMoE eval forward in one launch.  Per row b, with x = the `width` columns gathered from
+ * segs (rk_mlp_forward_gather's column map; out-of-range ids read zero rows and raise
+ * RK_FLAG_INDEX_OOB):
+ *   f_e = experts[e](x)                       experts[e * expert_depth + l], l = 0 .. expert_depth - 1;
+ *                                             every expert ends H wide
+ *   g_k = softmax_e(x . gate_w[k E + e] + gate_b[k E + e])    gate_w: the rk_mlp_pack_weight image of the
+ *                                             num_tasks gate weights stacked to [num_tasks * num_experts,
+ *                                             width]; gate_b [num_tasks * num_experts] or NULL
+ *   m_k = sum_e g_k[e] f_e                    e ascending, FP32, no atomics: two launches give the same bits
+ *   logit_k = towers[k](m_k) . head_w[k] + head_b[k][0]      towers[k * tower_depth + l]; head_w[k] [last width]
+ *   prob_k = sigmoid(logit_k)
+ * Outputs, each may be NULL: logits, probs [batch, num_tasks]; mixed [batch, num_tasks, H] (m_k);
+ * gate_probs [batch, num_tasks, num_experts] (g_k), all contiguous.  head_w = head_b = NULL (then towers
+ * = NULL, tower_depth = 0, logits = probs = NULL) stops after the mix.  [batch, E, H] is never formed.
+ * Envelope: nseg <= 16 segments of at most 255 columns each, width <= 256, num_experts <= 16, num_tasks <= 8, num_tasks * num_experts <= 64,
+ * 1 <= expert_depth <= 3, 0 <= tower_depth <= 3, every n <= 512, activations none / ReLU (else
+ * RK_ERR_UNSUPPORTED); NULL or shape errors and batch < 0: RK_ERR_INVALID; both before any launch.
+ * batch == 0: RK_OK, no launch.                                                                   */
+int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                    const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth,
+                    const float* gate_w, const float* gate_b, int32_t num_tasks, const rk_mmoe_layer* towers,
+                    int32_t tower_depth, const float* const* head_w, const float* const* head_b, float* logits,
+                    float* probs, float* mixed, float* gate_probs, void* stream);
 
 /* ---- xDeepFM training: the CIN's train forward, data backward and weight gradient ---- */
 /* rk_cin_forward that also writes every layer's feature maps for the backward:

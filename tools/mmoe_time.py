@@ -1,0 +1,176 @@
+"""Times of the MMoE eval forward at B 4096 and 32,768 with the wechat tables, for 4 and 8 experts
+(3 tasks, experts 256-128, towers 64), three ways, in one process:
+
+  (a) kernel    rk_mmoe_forward, the one launch rankops.MMoE runs
+  (b) torch     the float32 torch-ROCm formulation of the same module (embedding lookups, cat, the
+                experts' and towers' nn.Sequential, softmax, einsum, sigmoid)
+  (c) composed  the same forward from the launches the engine had before this kernel: rk_concat_gather,
+                one rk_mlp_forward per expert, torch matmul + softmax for the gates and einsum for the mix,
+                one rk_mlp_forward per tower (with its head).  This composition lives here only.
+
+Every leg is captured in a hipGraph once (after warm calls on a side stream) and timed as replays
+between device events; the legs alternate — a, b, c, a, b, c, … — and the median over the rounds is
+reported with the fastest and slowest round, whose spread is the noise a ratio has to beat.  The three
+are compared with each other before anything is timed.
+
+From the shapes the tool computes the forward's flops per sample (experts, gates, mix, towers, heads) and
+reports the kernel's rate as a share of the 157.3 TF FP32 matrix peak of the MI355X (the MFMA FP32 peak,
+not a measured ceiling).  `--batches 2048,8192` measures other batch sizes.  Needs a GPU; prints one JSON
+line at the end."""
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402  (sets sys.path for rankops and tests/)
+import torch  # noqa: E402
+
+import helpers as H  # noqa: E402
+import rankops  # noqa: E402
+from rankops import common, ops  # noqa: E402
+
+from dien_time import shader_clock  # noqa: E402
+
+FP32_MATRIX_PEAK_TF = 157.3
+ROUNDS = 7
+REPLAYS = 20
+
+
+def replay_us(graph):
+    st = torch.cuda.current_stream()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    graph.replay()
+    start.record(st)
+    for _ in range(REPLAYS):
+        graph.replay()
+    end.record(st)
+    end.synchronize()
+    return 1e3 * start.elapsed_time(end) / REPLAYS
+
+
+def flops_per_sample(model):
+    def stack(width, units):
+        total = 0
+        for n in units:
+            total += 2 * width * n
+            width = n
+        return total, width
+    E, K = model.num_experts, len(model.task_names)
+    ex, H_ = stack(model.input_dim, model.expert_hidden_units)
+    tw, last = stack(H_, model.tower_hidden_units)
+    return E * ex + 2 * model.input_dim * K * E + 2 * K * E * H_ + K * (tw + 2 * last)
+
+
+def torch_forward(model, dense, cat):
+    x = torch.cat([dense] + [emb(cat[n]) for n, emb in model.embeddings.items()], dim=1)
+    f = torch.stack([expert(x) for expert in model.experts], dim=1)
+    g = torch.stack([torch.softmax(gate(x), dim=1) for gate in model.gates], dim=1)
+    m = torch.einsum("bke,beh->bkh", g, f)
+    logits = torch.cat([out(tower(m[:, k])) for k, (tower, out) in enumerate(zip(model.towers, model.tower_outputs))],
+                       dim=1)
+    return torch.sigmoid(logits), logits
+
+
+def composed_forward(model, dense, cat):
+    """Leg (c): its buffers and marshalled layers, and the function that runs it."""
+    B, dev = dense.shape[0], dense.device
+    E, K, Hw = model.num_experts, len(model.task_names), model.expert_hidden_units[-1]
+    segs = [ops.dense_segment(dense, model.num_dense_features, 0)]
+    col = model.num_dense_features
+    for n, emb in model.embeddings.items():
+        segs.append(ops.table_segment(emb.weight, cat[n], col))
+        col += emb.embedding_dim
+    x = torch.empty(B, model.input_dim, device=dev)
+    f = torch.empty(B, E, Hw, device=dev)
+    logits, probs = torch.empty(K, B, device=dev), torch.empty(K, B, device=dev)
+
+    def layers(seq):
+        return [ops.make_mlp_layer(l.weight, common.PACKED(l.weight), bias=l.bias, act="relu")
+                for l in seq if isinstance(l, torch.nn.Linear)]
+    experts = [layers(seq) for seq in model.experts]
+    towers = [layers(seq) for seq in model.towers]
+    heads = [ops.make_epilogue(head_w=o.weight, head_b=o.bias, head_logit=logits[k], head_prob=probs[k])
+             for k, o in enumerate(model.tower_outputs)]
+    gate_w = torch.cat([g.weight.detach() for g in model.gates], 0)
+    gate_b = torch.cat([g.bias.detach() for g in model.gates], 0)
+
+    def run():
+        ops.concat_gather(segs, B, x)
+        for e in range(E):
+            ops.mlp_forward(x, experts[e], None, f[:, e])
+        g = torch.softmax(torch.addmm(gate_b, x, gate_w.t()).view(B, K, E), dim=2)
+        m = torch.einsum("bke,beh->bkh", g, f)
+        for k in range(K):
+            ops.mlp_forward(m[:, k], towers[k], heads[k])
+        return probs, logits
+    run.keep = (segs, experts, towers, heads)
+    return run
+
+
+def measure(E, B):
+    torch.manual_seed(42)
+    model = rankops.MMoE(None, num_experts=E, vocab_sizes=H.WECHAT_VOCAB).cuda().eval()
+    inp = H.to_device(H.dcn_inputs(B, H.WECHAT_VOCAB, 1000), "cuda")
+    dense, cat = inp["dense"], inp["category"]
+    dev = dense.device
+    names, idx = model._indices(cat)
+    built = model._build(dense, names, idx)
+    out = model._outputs(B, dev)
+
+    def kernel():
+        model._run(built, out, ops._lib.raw_stream(dev))
+        return out
+    composed = composed_forward(model, dense, cat)
+    fns = {"kernel": kernel, "torch": lambda: torch_forward(model, dense, cat), "composed": composed}
+    with torch.no_grad():
+        prob_a, logit_a = [t.clone() for t in kernel()]
+        prob_b, logit_b = torch_forward(model, dense, cat)
+        prob_c, logit_c = [t.t().clone() for t in composed()]
+    torch.cuda.synchronize()
+    err_b = float(((logit_a - logit_b).abs() / (1 + logit_b.abs())).max())
+    err_c = float(((logit_a - logit_c).abs() / (1 + logit_c.abs())).max())
+    assert err_b <= 1e-4 and err_c <= 1e-4, f"legs differ: kernel vs torch {err_b}, kernel vs composed {err_c}"
+    assert float((prob_a - prob_b).abs().max()) <= 1e-4
+    graphs = {k: bench.graph_of(fn)[0] for k, fn in fns.items()}
+    times = {k: [] for k in graphs}
+    for _ in range(ROUNDS):
+        for k, g in graphs.items():
+            times[k].append(replay_us(g))
+    r = {}
+    for k, t in times.items():
+        r[f"{k}_us"] = {"median": round(statistics.median(t), 2), "min": round(min(t), 2), "max": round(max(t), 2)}
+    med = {k: statistics.median(t) for k, t in times.items()}
+    flops = flops_per_sample(model)
+    r["flops_per_sample"] = flops
+    r["kernel_tflops"] = round(flops * B / med["kernel"] / 1e6, 2)
+    r["share_of_fp32_matrix_peak"] = round(flops * B / med["kernel"] / 1e6 / FP32_MATRIX_PEAK_TF, 4)
+    r["torch_over_kernel"] = round(med["torch"] / med["kernel"], 2)
+    r["composed_over_kernel"] = round(med["composed"] / med["kernel"], 2)
+    r["kernel_vs_torch_max_rel_err"], r["kernel_vs_composed_max_rel_err"] = err_b, err_c
+    del graphs, model
+    torch.cuda.empty_cache()
+    return r
+
+
+def main():
+    assert torch.cuda.is_available(), "mmoe_time needs a ROCm GPU"
+    rankops.load_library()
+    result = {"device": torch.cuda.get_device_name(0), "fp32_matrix_peak_tf": FP32_MATRIX_PEAK_TF,
+              "sclk_before": shader_clock()}
+    batches = (4096, 32768)
+    if "--batches" in sys.argv[1:]:
+        batches = tuple(int(b) for b in sys.argv[sys.argv.index("--batches") + 1].split(","))
+    for E in (4, 8):
+        for B in batches:
+            r = measure(E, B)
+            result[f"E{E}_B{B}"] = r
+            print(f"E {E} B {B}: " + ", ".join(f"{k} {v}" for k, v in r.items()), flush=True)
+    result["sclk_after"] = shader_clock()
+    assert rankops.error_flags() == 0
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
