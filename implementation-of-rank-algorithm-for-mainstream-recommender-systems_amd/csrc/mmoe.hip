@@ -31,6 +31,7 @@
 // gate logits), gt [64][16] (the gate weights, gt[(e K + k) 16 + row]), mt [T][pad64(H)][16]
 // (mt[(i pad64(H) + n) 16 + row]).
 #include "mlp_core.h"
+#include "train_common.h"
 
 namespace rk {
 
@@ -62,6 +63,26 @@ struct MmoeArgs {
   uint32_t* flags;
 };
 static_assert(sizeof(MmoeArgs) <= 4096, "kernel arguments beyond 4 KiB");
+
+// The train forward's additions (rk_mmoe_forward_train): dropout behind every ReLU and the buffers the
+// backward reads.  Every per-layer buffer holds the layer of all experts (tasks) side by side: expert
+// e's layer l at columns e * pitch_e[l] of eact[l] [B, E * pitch_e[l]], tower k's layer l at columns
+// k * pitch_t[l] of tact[l] [B, K * pitch_t[l]]; a pitch is the width rounded up to 4 and the columns
+// between hold zeros.  `mixed` has pitch_m floats per (row, task), x_out ldx_out per row.
+// Dropout site s (expert e layer l: e De + l, tower k layer l: E De + k Dt + l) keeps element
+// (b, j) of its [B, n] output iff dropout_keep(seed + s, *slot, b n + j, threshold).
+struct MmoeTrainArgs : MmoeArgs {
+  float* x_out;
+  float* eact[kMmMaxDepth];
+  float* tact[kMmMaxDepth];
+  int pitch_e[kMmMaxDepth], pitch_t[kMmMaxDepth];
+  int ldx_out, pitch_m;
+  uint32_t threshold;
+  float scale;
+  uint64_t seed;
+  const int64_t* slot;
+};
+static_assert(sizeof(MmoeTrainArgs) <= 4096, "kernel arguments beyond 4 KiB");
 
 // The rk_mlp_layer view of a compact descriptor over an input of K columns (Linear + bias + act).
 __device__ __forceinline__ rk_mlp_layer mm_view(const rk_mmoe_layer& d, int K) {
@@ -124,7 +145,28 @@ __device__ __forceinline__ void mm_layer_tiles(LayerPipe& pipe, const rk_mlp_lay
   }
 }
 
-__global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
+// A finished hidden layer in LDS (16 rows of n columns, after the layer's barrier) for the train
+// forward: dropout applied in place (the next layer reads it), the result stored to its column block
+// of the layer's HBM buffer, zeros up to the pitch.  All threads; the caller's barrier follows.
+__device__ __forceinline__ void mm_train_store(const MmoeTrainArgs& a, float* h, int n, int site, float* dst,
+                                               int64_t ld, int pitch, int64_t m0, int rows, uint64_t stream,
+                                               int tid) {
+  for (int i = tid; i < kMlpRows * pitch; i += kMlpThreads) {
+    const int row = i / pitch, j = i - row * pitch;
+    float y = 0.f;
+    if (j < n) {
+      y = h[row * a.ldh + j];
+      if (a.threshold) {
+        y = dropout_keep(a.seed + (uint64_t)site, stream, (uint64_t)(m0 + row) * n + j, a.threshold) ? y * a.scale : 0.f;
+        h[row * a.ldh + j] = y;
+      }
+    }
+    if (row < rows) dst[(m0 + row) * ld + j] = y;
+  }
+}
+
+template <bool TRAIN>
+__global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TRAIN, MmoeTrainArgs, MmoeArgs> a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
   const int64_t m0 = (int64_t)blockIdx.x * kMlpRows;
@@ -166,6 +208,15 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
     if (sg[i] != 255 && r[i] >= 0) {
       const rk_segment& g = a.segs[sg[i]];
       v[i] = g.src[r[i] * g.src_ld + a.col_off[lane + 64 * i]];
+    }
+  }
+  uint64_t stream = 0;
+  if constexpr (TRAIN) {
+    if (a.threshold) stream = (uint64_t)*a.slot;
+#pragma unroll
+    for (int i = 0; i < kMmCols / 64; ++i) {
+      const int c = lane + 64 * i;
+      if (live && c < a.ldx_out) a.x_out[b * a.ldx_out + c] = v[i];  // (zeros past the width)
     }
   }
   __builtin_amdgcn_sched_barrier(0);  // the gather's loads stay ahead of the weight ring
@@ -239,9 +290,19 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
           mm_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
           const rk_mlp_layer N = expert(e, l + 1);
           mm_prepare(pipe, N, L.n, wave, ln);
+          if constexpr (TRAIN) {
+            close_layer();
+            mm_train_store(a, out, L.n, e * De + l, a.eact[l] + e * a.pitch_e[l], (int64_t)E * a.pitch_e[l],
+                           a.pitch_e[l], m0, rows, stream, tid);
+          }
         } else {
+          // (train: the last layer goes through LDS like the others, so that dropout and the store
+          // of f_e run after its barrier; the register epilogue with both went to scratch)
           f32x4_t z[2];
-          mm_layer_tiles(pipe, L, in, l == 0 ? a.ldx : a.ldh, Kp, wave, ln, z);
+          if constexpr (TRAIN)
+            mm_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
+          else
+            mm_layer_tiles(pipe, L, in, l == 0 ? a.ldx : a.ldh, Kp, wave, ln, z);
           if (e + 1 < E || (more && !(a.has_head && Dt > 0))) {
             const rk_mlp_layer N = expert(e + 1 < E ? e + 1 : 0, 0);
             mm_prepare(pipe, N, width, wave, ln);
@@ -250,6 +311,18 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
             mm_prepare(pipe, N, H, wave, ln);
           }
           const int q4 = (ln >> 4) * 4;  // the lane's first row
+          if constexpr (TRAIN) {
+            close_layer();
+            mm_train_store(a, out, H, e * De + l, a.eact[l] + e * a.pitch_e[l], (int64_t)E * a.pitch_e[l],
+                           a.pitch_e[l], m0, rows, stream, tid);
+            mlp_lds_barrier();
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const int n = 16 * (wave + kMlpWaves * j) + (ln & 15);
+#pragma unroll
+              for (int q = 0; q < 4; ++q) z[j][q] = n < Hp ? out[(q4 + q) * a.ldh + n] : 0.f;
+            }
+          }
           for (int i = 0; i < kg; ++i) {
             const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(gt + (e * K + k0 + i) * kMlpRows + q4);
 #pragma unroll
@@ -284,7 +357,12 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
           for (int q = 0; q < 4; ++q) {
             const int row = (lm >> 4) * 4 + q;
             if (a.has_head) ha[row * a.ldh + n] = mv[q];  // pad columns hold zeros: the tower's zero K pad
-            if (a.mixed && n < H && row < rows) a.mixed[((m0 + row) * K + k) * H + n] = mv[q];
+            if constexpr (TRAIN) {
+              if (a.mixed && n < a.pitch_m && row < rows)
+                a.mixed[((m0 + row) * K + k) * a.pitch_m + n] = n < H ? mv[q] : 0.f;
+            } else {
+              if (a.mixed && n < H && row < rows) a.mixed[((m0 + row) * K + k) * H + n] = mv[q];
+            }
           }
         }
       }
@@ -308,6 +386,11 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
           mm_prepare(pipe, N, width, wave, ln);
         }
         close_layer();
+        if constexpr (TRAIN) {
+          mm_train_store(a, out, L.n, E * De + k * Dt + l, a.tact[l] + k * a.pitch_t[l], (int64_t)K * a.pitch_t[l],
+                         a.pitch_t[l], m0, rows, stream, tid);
+          mlp_lds_barrier();
+        }
       }
       const float* fin = (Dt & 1) ? hb : ha;
       const int Kh = Dt ? a.layers[E * De + k * Dt + Dt - 1].n : H;
@@ -327,37 +410,90 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(MmoeArgs a) {
   }
 }
 
+// rk_mlp_pack_weight's image (mlp.hip, mlp_pack_kernel) of many weights in one launch: grid
+// (256-element blocks of the largest image, weight).
+constexpr int kPackMaxItems = 96;
+struct PackItems {
+  rk_pack_item item[kPackMaxItems];
+};
+static_assert(sizeof(PackItems) <= 4096, "kernel arguments beyond 4 KiB");
+
+__global__ __launch_bounds__(256) void mlp_pack_many_kernel(PackItems p) {
+  const rk_pack_item& it = p.item[blockIdx.y];
+  const int np = pad64(it.n), kp = pad64(it.k);
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)np * kp) return;
+  const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+  const int64_t blk = i >> 8;
+  const int kch = kp / 16;
+  const int t = (int)(blk / kch), c = (int)(blk % kch);
+  const int r = 16 * t + (lane & 15), col = 16 * c + 4 * (lane >> 4) + e;
+  it.out[i] = (r < it.n && col < it.k) ? it.w[(int64_t)r * it.ldw + col] : 0.f;
+}
+
 }  // namespace rk
 
 using namespace rk;
 
-RK_API int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
-                           const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth,
-                           const float* gate_w, const float* gate_b, int32_t num_tasks, const rk_mmoe_layer* towers,
-                           int32_t tower_depth, const float* const* head_w, const float* const* head_b, float* logits,
-                           float* probs, float* mixed, float* gate_probs, void* stream) {
+RK_API int rk_mlp_pack_weights(const rk_pack_item* items, int32_t count, void* stream) {
+  if (count < 0 || (count > 0 && !items)) return fail(RK_ERR_INVALID, "rk_mlp_pack_weights: bad arguments");
+  for (int i = 0; i < count; ++i)
+    if (!items[i].w || !items[i].out || items[i].n <= 0 || items[i].k <= 0 || items[i].ldw < items[i].k ||
+        !aligned16(items[i].out))
+      return fail(RK_ERR_INVALID, "rk_mlp_pack_weights: item %d: null / misaligned pointer or bad shape", i);
+  for (int i0 = 0; i0 < count; i0 += kPackMaxItems) {
+    PackItems p = {};
+    const int c = std::min(kPackMaxItems, count - i0);
+    int64_t most = 0;
+    for (int i = 0; i < c; ++i) {
+      p.item[i] = items[i0 + i];
+      most = std::max<int64_t>(most, (int64_t)pad64(p.item[i].n) * pad64(p.item[i].k));
+    }
+    mlp_pack_many_kernel<<<dim3((unsigned)((most + 255) / 256), (unsigned)c), 256, 0, (hipStream_t)stream>>>(p);
+  }
+  return check_launch("rk_mlp_pack_weights");
+}
+
+namespace {
+
+// The train entry's own arguments (null for the eval entry).
+struct TrainOut {
+  double p;
+  uint64_t seed;
+  const int64_t* slot;
+  float* x_out;
+  float* const* expert_acts;
+  float* const* tower_acts;
+};
+
+int pad4(int v) { return (v + 3) / 4 * 4; }
+
+int mmoe_launch(const char* name, const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth, const float* gate_w,
+                const float* gate_b, int32_t num_tasks, const rk_mmoe_layer* towers, int32_t tower_depth,
+                const float* const* head_w, const float* const* head_b, float* logits, float* probs, float* mixed,
+                float* gate_probs, const TrainOut* train, void* stream) {
   if (!segs || !experts || !gate_w || batch < 0 || nseg <= 0 || width <= 0 || num_experts <= 0 || num_tasks <= 0 ||
       expert_depth <= 0 || tower_depth < 0 || (head_w != nullptr) != (head_b != nullptr) ||
       (tower_depth > 0 && (!towers || !head_w)))
-    return fail(RK_ERR_INVALID, "rk_mmoe_forward: null pointer or negative size (batch %lld)", (long long)batch);
-  if (!head_w && (logits || probs)) return fail(RK_ERR_INVALID, "rk_mmoe_forward: logits / probs need the heads");
+    return fail(RK_ERR_INVALID, "%s: null pointer or negative size (batch %lld)", name, (long long)batch);
+  if (!head_w && (logits || probs)) return fail(RK_ERR_INVALID, "%s: logits / probs need the heads", name);
   if (!(head_w ? (logits || probs || mixed || gate_probs) : (mixed || gate_probs)))
-    return fail(RK_ERR_INVALID, "rk_mmoe_forward: no output");
+    return fail(RK_ERR_INVALID, "%s: no output", name);
   if (nseg > kMmSegs || width > kMmCols || num_experts > kMmMaxExperts || num_tasks > kMmMaxTasks ||
       num_tasks * num_experts > kMmMaxGates || expert_depth > kMmMaxDepth || tower_depth > kMmMaxDepth)
-    return fail(RK_ERR_UNSUPPORTED,
-                "rk_mmoe_forward: %d segments (<= %d) over %d columns (<= %d), %d experts (<= %d) of depth %d (1..%d), "
-                "%d tasks (<= %d, tasks x experts <= %d), tower depth %d (<= %d)",
+    return fail(RK_ERR_UNSUPPORTED, "%s: %d segments (<= %d) over %d columns (<= %d), %d experts (<= %d) of depth %d (1..%d), "
+                "%d tasks (<= %d, tasks x experts <= %d), tower depth %d (<= %d)", name,
                 nseg, kMmSegs, width, kMmCols, num_experts, kMmMaxExperts, expert_depth, kMmMaxDepth, num_tasks,
                 kMmMaxTasks, kMmMaxGates, tower_depth, kMmMaxDepth);
-  MmoeArgs a = {};
+  MmoeTrainArgs a = {};
   int wide = kMlpPad;  // the widest hidden activation, padded
-  auto take = [&](const rk_mmoe_layer& d, rk_mmoe_layer& out, const char* what, int i, int l) {
+  auto take = [&](const rk_mmoe_layer& d, rk_mmoe_layer& out, const char* what, int i, int l) -> int {
     if (!d.w || !aligned16(d.w) || d.n <= 0)
-      return fail(RK_ERR_INVALID, "rk_mmoe_forward: %s %d layer %d: weight null or misaligned, n = %d", what, i, l,
+      return fail(RK_ERR_INVALID, "%s: %s %d layer %d: weight null or misaligned, n = %d", name, what, i, l,
                   d.n);
     if (d.n > kMlpMaxN || (d.act != RK_ACT_NONE && d.act != RK_ACT_RELU))
-      return fail(RK_ERR_UNSUPPORTED, "rk_mmoe_forward: %s %d layer %d: n = %d (<= %d), activation %d (none / ReLU)",
+      return fail(RK_ERR_UNSUPPORTED, "%s: %s %d layer %d: n = %d (<= %d), activation %d (none / ReLU)", name,
                   what, i, l, d.n, kMlpMaxN, d.act);
     out = d;
     wide = std::max(wide, pad64(d.n));
@@ -369,19 +505,19 @@ RK_API int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, 
   const int H = experts[expert_depth - 1].n;
   for (int e = 1; e < num_experts; ++e)
     if (experts[e * expert_depth + expert_depth - 1].n != H)
-      return fail(RK_ERR_INVALID, "rk_mmoe_forward: expert %d ends %d wide, expert 0 %d", e,
+      return fail(RK_ERR_INVALID, "%s: expert %d ends %d wide, expert 0 %d", name, e,
                   experts[e * expert_depth + expert_depth - 1].n, H);
   const int t0 = num_experts * expert_depth;
   for (int k = 0; k < num_tasks; ++k) {
     for (int l = 0; l < tower_depth; ++l)
       if (int rc = take(towers[k * tower_depth + l], a.layers[t0 + k * tower_depth + l], "tower", k, l)) return rc;
     if (head_w) {
-      if (!head_w[k] || !head_b[k]) return fail(RK_ERR_INVALID, "rk_mmoe_forward: head %d null", k);
+      if (!head_w[k] || !head_b[k]) return fail(RK_ERR_INVALID, "%s: head %d null", name, k);
       a.head_w[k] = head_w[k];
       a.head_b[k] = head_b[k];
     }
   }
-  if (!aligned16(gate_w)) return fail(RK_ERR_INVALID, "rk_mmoe_forward: gate image misaligned");
+  if (!aligned16(gate_w)) return fail(RK_ERR_INVALID, "%s: gate image misaligned", name);
   a.gate = rk_mmoe_layer{gate_w, gate_b, num_tasks * num_experts, RK_ACT_NONE};
   for (int c = 0; c < kMmCols; ++c) {
     a.col_seg[c] = 255;
@@ -391,7 +527,7 @@ RK_API int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, 
     const rk_segment& sg = segs[i];
     if (!sg.src || sg.dim <= 0 || sg.out_col < 0 || sg.out_col + sg.dim > width || (sg.idx && sg.rows <= 0) ||
         sg.dim > 255)
-      return fail(RK_ERR_INVALID, "rk_mmoe_forward: segment %d invalid", i);
+      return fail(RK_ERR_INVALID, "%s: segment %d invalid", name, i);
     a.segs[i] = sg;
     for (int c = sg.out_col; c < sg.out_col + sg.dim; ++c) {  // the last covering segment wins
       a.col_seg[c] = (uint8_t)i;
@@ -416,15 +552,80 @@ RK_API int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, 
   const size_t base = (size_t)kMlpRows * (a.ldx + 2 * a.ldh + kMmLdG + kMmMaxGates) * sizeof(float);
   const size_t per_task = (size_t)kMlpRows * pad64(H) * sizeof(float);
   if (base + per_task > 160 * 1024)
-    return fail(RK_ERR_UNSUPPORTED, "rk_mmoe_forward: widths need %zu B of LDS", base + per_task);
+    return fail(RK_ERR_UNSUPPORTED, "%s: widths need %zu B of LDS", name, base + per_task);
   a.T = (int)std::min<size_t>(num_tasks, (160 * 1024 - base) / per_task);
   const size_t shm = base + a.T * per_task;
   a.flags = device_flags();
-  if (!a.flags) return fail(RK_ERR_RUNTIME, "rk_mmoe_forward: device not initialised (rk_init)");
+  if (!a.flags) return fail(RK_ERR_RUNTIME, "%s: device not initialised (rk_init)", name);
+  if (train) {
+    if (!(train->p >= 0.0 && train->p < 1.0) || (train->p > 0.0 && !train->slot) || !train->x_out || !train->expert_acts ||
+        (tower_depth > 0 && !train->tower_acts) || !mixed || !gate_probs)
+      return fail(RK_ERR_INVALID, "%s: dropout_p outside [0, 1), or a null stream slot / saved buffer", name);
+    for (int l = 0; l < expert_depth; ++l) {
+      for (int e = 1; e < num_experts; ++e)
+        if (experts[e * expert_depth + l].n != experts[l].n)
+          return fail(RK_ERR_INVALID, "%s: expert %d layer %d is %d wide, expert 0's %d", name, e, l,
+                      experts[e * expert_depth + l].n, experts[l].n);
+      if (!train->expert_acts[l] || !aligned16(train->expert_acts[l]))
+        return fail(RK_ERR_INVALID, "%s: expert_acts[%d] null or misaligned", name, l);
+      a.eact[l] = train->expert_acts[l];
+      a.pitch_e[l] = pad4(experts[l].n);
+    }
+    for (int l = 0; l < tower_depth; ++l) {
+      for (int k = 1; k < num_tasks; ++k)
+        if (towers[k * tower_depth + l].n != towers[l].n)
+          return fail(RK_ERR_INVALID, "%s: tower %d layer %d is %d wide, tower 0's %d", name, k, l,
+                      towers[k * tower_depth + l].n, towers[l].n);
+      if (!train->tower_acts[l] || !aligned16(train->tower_acts[l]))
+        return fail(RK_ERR_INVALID, "%s: tower_acts[%d] null or misaligned", name, l);
+      a.tact[l] = train->tower_acts[l];
+      a.pitch_t[l] = pad4(towers[l].n);
+    }
+    for (int i = 0; i < num_experts * expert_depth + num_tasks * tower_depth; ++i)
+      if (a.layers[i].act != RK_ACT_RELU) return fail(RK_ERR_UNSUPPORTED, "%s: every hidden layer must be ReLU", name);
+    if (!aligned16(train->x_out) || !aligned16(mixed))
+      return fail(RK_ERR_INVALID, "%s: x_out / mixed misaligned", name);
+    a.x_out = train->x_out;
+    a.ldx_out = pad4(width);
+    a.pitch_m = pad4(H);
+    a.threshold = dropout_threshold(train->p);
+    a.scale = (float)(1.0 / (1.0 - train->p));
+    a.seed = train->seed;
+    a.slot = train->slot;
+  }
   if (batch == 0) return RK_OK;
   const int64_t blocks = (batch + kMlpRows - 1) / kMlpRows;
-  if (blocks > INT32_MAX) return fail(RK_ERR_UNSUPPORTED, "rk_mmoe_forward: batch too large");
-  raise_lds_limit((const void*)mmoe_kernel, 160 * 1024);
-  mmoe_kernel<<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(a);
-  return check_launch("rk_mmoe_forward");
+  if (blocks > INT32_MAX) return fail(RK_ERR_UNSUPPORTED, "%s: batch too large", name);
+  if (train) {
+    raise_lds_limit((const void*)mmoe_kernel<true>, 160 * 1024);
+    mmoe_kernel<true><<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(a);
+  } else {
+    raise_lds_limit((const void*)mmoe_kernel<false>, 160 * 1024);
+    mmoe_kernel<false><<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(static_cast<const MmoeArgs&>(a));
+  }
+  return check_launch(name);
+}
+
+}  // namespace
+
+RK_API int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                           const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth,
+                           const float* gate_w, const float* gate_b, int32_t num_tasks, const rk_mmoe_layer* towers,
+                           int32_t tower_depth, const float* const* head_w, const float* const* head_b, float* logits,
+                           float* probs, float* mixed, float* gate_probs, void* stream) {
+  return mmoe_launch("rk_mmoe_forward", segs, nseg, width, batch, experts, num_experts, expert_depth, gate_w, gate_b,
+                     num_tasks, towers, tower_depth, head_w, head_b, logits, probs, mixed, gate_probs, nullptr, stream);
+}
+
+RK_API int rk_mmoe_forward_train(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                                 const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth,
+                                 const float* gate_w, const float* gate_b, int32_t num_tasks,
+                                 const rk_mmoe_layer* towers, int32_t tower_depth, const float* const* head_w,
+                                 const float* const* head_b, double dropout_p, uint64_t seed, const int64_t* stream_slot,
+                                 float* x_out, float* const* expert_acts, float* const* tower_acts, float* logits,
+                                 float* probs, float* mixed, float* gate_probs, void* stream) {
+  const TrainOut t = {dropout_p, seed, stream_slot, x_out, expert_acts, tower_acts};
+  return mmoe_launch("rk_mmoe_forward_train", segs, nseg, width, batch, experts, num_experts, expert_depth, gate_w,
+                     gate_b, num_tasks, towers, tower_depth, head_w, head_b, logits, probs, mixed, gate_probs, &t,
+                     stream);
 }

@@ -157,6 +157,75 @@ __global__ __launch_bounds__(256) void gemm_kernel(int64_t M, int64_t N, int64_t
   }
 }
 
+// G problems of one shape in one launch (rk_gemm_grouped): grid (m tiles, n tiles, G), group g's
+// operands by pointer, the whole reduction per workgroup (no split, no atomics).  The epilogue masks
+// the *output*: C = (A . B) * mask_scale * [C_mask > 0] (C_mask with its own row stride), so a dz buffer is
+// written masked once and read plain by everything after it.
+constexpr int kGemmMaxGroups = 16;
+struct GemmGroups {
+  const float* A[kGemmMaxGroups];
+  const float* B[kGemmMaxGroups];
+  float* C[kGemmMaxGroups];
+  const float* C_mask[kGemmMaxGroups];
+};
+
+template <bool TA, bool TB>
+__global__ __launch_bounds__(256) void gemm_grouped_kernel(GemmGroups gp, int64_t M, int64_t N, int64_t R, int64_t lda,
+                                                           int64_t ldb, int64_t ldc, int64_t ldmask,
+                                                           float mask_scale, int accumulate) {
+  __shared__ float As[kGR * kGLD];
+  __shared__ float Bs[kGR * kGLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int g = blockIdx.z;
+  const float* __restrict__ A = gp.A[g];
+  const float* __restrict__ B = gp.B[g];
+  const int64_t m0 = (int64_t)blockIdx.x * kGT, n0 = (int64_t)blockIdx.y * kGT;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  float va[kGV], vb[kGV];
+  if (R > 0) {
+    stage_load<TA>(A, lda, nullptr, M, R, m0, 0, tid, va);
+    stage_load<TB>(B, ldb, nullptr, N, R, n0, 0, tid, vb);
+  }
+  for (int64_t r0 = 0; r0 < R; r0 += kGR) {
+    stage_store<TA>(As, tid, va);
+    stage_store<TB>(Bs, tid, vb);
+    __syncthreads();
+    if (r0 + kGR < R) {
+      stage_load<TA>(A, lda, nullptr, M, R, m0, r0 + kGR, tid, va);
+      stage_load<TB>(B, ldb, nullptr, N, R, n0, r0 + kGR, tid, vb);
+    }
+    const float* a_col = As + wm * 32 + (lane & 31);
+    const float* b_col = Bs + wn * 32 + (lane & 31);
+    const int k1 = lane >> 5;
+    float av[kGR / 2], bv[kGR / 2];
+#pragma unroll
+    for (int k = 0; k < kGR / 2; ++k) {
+      av[k] = a_col[(2 * k + k1) * kGLD];
+      bv[k] = b_col[(2 * k + k1) * kGLD];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < kGR / 2; ++k) acc = mfma32(av[k], bv[k], acc);
+    __syncthreads();
+  }
+  float* __restrict__ C = gp.C[g];
+  const float* __restrict__ mask = gp.C_mask[g];
+  const int64_t n = n0 + wn * 32 + (lane & 31);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t m = m0 + wm * 32 + acc_row(r, lane);
+    if (m < M && n < N) {
+      float v = acc[r];
+      if (mask) v = mask[m * ldmask + n] > 0.f ? v * mask_scale : 0.f;
+      float* c = C + m * ldc + n;
+      *c = accumulate ? *c + v : v;
+    }
+  }
+}
+
 __global__ void zero2d_kernel(float* __restrict__ p, int64_t rows, int64_t cols, int64_t ld) {
   const int64_t n = rows * cols;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -485,6 +554,45 @@ RK_API int rk_gemm(int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64
   RK_GEMM_CASE(true, true)
 #undef RK_GEMM_CASE
   return check_launch("rk_gemm");
+}
+
+RK_API int rk_gemm_grouped(int32_t G, int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t R,
+                           const float* const* A, int64_t lda, const float* const* B, int64_t ldb, float* const* C,
+                           int64_t ldc, const float* const* C_mask, int64_t ldmask, float mask_scale,
+                           int32_t accumulate, void* stream) {
+  if (G <= 0 || M < 0 || N < 0 || R < 0 || !C || ldc < N || (R > 0 && (!A || !B)) || (C_mask && ldmask < N))
+    return fail(RK_ERR_INVALID, "rk_gemm_grouped: bad shape / null pointer array");
+  if (G > kGemmMaxGroups) return fail(RK_ERR_UNSUPPORTED, "rk_gemm_grouped: %d groups (<= %d)", G, kGemmMaxGroups);
+  // (a transposed A is a weight gradient: rk_gemm_wgrad_grouped; its instantiations here spilled to scratch)
+  if (trans_a) return fail(RK_ERR_UNSUPPORTED, "rk_gemm_grouped: trans_a is not supported (rk_gemm_wgrad_grouped)");
+  if (lda < (trans_a ? M : R) || ldb < (trans_b ? N : R))
+    return fail(RK_ERR_INVALID, "rk_gemm_grouped: leading dimension too small (lda %lld, ldb %lld)", (long long)lda,
+                (long long)ldb);
+  GemmGroups gp = {};
+  for (int g = 0; g < G; ++g) {
+    if (!C[g] || (R > 0 && (!A[g] || !B[g])) || (C_mask && !C_mask[g]))
+      return fail(RK_ERR_INVALID, "rk_gemm_grouped: group %d: null operand", g);
+    if (((uintptr_t)C[g] | (uintptr_t)(R > 0 ? A[g] : nullptr) | (uintptr_t)(R > 0 ? B[g] : nullptr) |
+         (uintptr_t)(C_mask ? C_mask[g] : nullptr)) & 3)
+      return fail(RK_ERR_INVALID, "rk_gemm_grouped: group %d: pointer not aligned to a float", g);
+    gp.A[g] = R > 0 ? A[g] : nullptr;
+    gp.B[g] = R > 0 ? B[g] : nullptr;
+    gp.C[g] = C[g];
+    gp.C_mask[g] = C_mask ? C_mask[g] : nullptr;
+  }
+  if (M == 0 || N == 0) return RK_OK;
+  const int64_t tm = (M + kGT - 1) / kGT, tn = (N + kGT - 1) / kGT;
+  if (tm > INT32_MAX || tn > 65535) return fail(RK_ERR_UNSUPPORTED, "rk_gemm_grouped: output too large");
+  const dim3 grid((unsigned)tm, (unsigned)tn, (unsigned)G);
+  hipStream_t st = (hipStream_t)stream;
+#define RK_GEMM_CASE(TA_, TB_)                                                                                    \
+  if (!!trans_a == TA_ && !!trans_b == TB_)                                                                       \
+    gemm_grouped_kernel<TA_, TB_><<<grid, 256, 0, st>>>(gp, M, N, R, lda, ldb, ldc, ldmask, mask_scale,     \
+                                                        accumulate);
+  RK_GEMM_CASE(false, false)
+  RK_GEMM_CASE(false, true)
+#undef RK_GEMM_CASE
+  return check_launch("rk_gemm_grouped");
 }
 
 RK_API int rk_relu_backward(const float* dy, const float* y, float* out, int64_t n, int32_t accumulate, void* stream) {

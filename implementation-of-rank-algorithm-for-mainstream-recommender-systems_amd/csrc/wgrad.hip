@@ -75,113 +75,39 @@ __global__ __launch_bounds__(kWgThreads) void wgrad_kernel(int64_t N, int64_t K,
                                                            const float* __restrict__ A_mask,
                                                            const float* __restrict__ B, int64_t ldb,
                                                            float* __restrict__ ws, float* __restrict__ wsb) {
-  __shared__ float As2[2][kWgT * kWgP];  // double-buffered k-major images (139 KB, one workgroup per CU)
-  __shared__ float Bs2[2][kWgT * kWgP];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wm = w & 3, wk = w >> 2;
-#ifdef RK_WGRAD_STAMP  // diagnostic build only (tools/wgrad_clock.cpp): per-workgroup clock stamps
-  uint64_t t0 = 0, r0s = 0;
-  if (tid == 0) {
-    t0 = __builtin_amdgcn_s_memtime();
-    r0s = __builtin_amdgcn_s_memrealtime();
-  }
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
-  const int n0 = blockIdx.y * kWgT, k0 = blockIdx.z * kWgT;
-  const int64_t rb = (int64_t)blockIdx.x * rps;
-  const int64_t re = min<int64_t>(R, rb + rps);
-  f32x16 acc0, acc1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
-  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-  const bool sums = wsb && blockIdx.z == 0;
-  f32x4 va[4], vb[4], ma[4], mb[4];
-  // lane half h = lane >> 5 takes reduction rows 8g + 4h + e at MFMA e of row group g (the same rows
-  // for the A and B operands, so the k-permutation cancels in the sum)
-  const int a_off = (32 * wm + (lane & 31)) * kWgP + 4 * (lane >> 5);
-  const int b_off = (64 * wk + (lane & 31)) * kWgP + 4 * (lane >> 5);
-  // prologue: step 0 into buffer 0, step 1's loads in flight
-  wg_load<MASK>(A, lda, A_mask, rb, re, n0, (int)N, tid, va, ma);
-  wg_load<false>(B, ldb, nullptr, rb, re, k0, (int)K, tid, vb, mb);
-  if (sums)
-    wg_store<MASK, true>(As2[0], tid, va, ma, rb, re, n0, (int)N, bsum);
-  else
-    wg_store<MASK, false>(As2[0], tid, va, ma, rb, re, n0, (int)N, bsum);
-  wg_store<false, false>(Bs2[0], tid, vb, mb, rb, re, k0, (int)K, bsum);
-  if (rb + kWgR < re) {
-    wg_load<MASK>(A, lda, A_mask, rb + kWgR, re, n0, (int)N, tid, va, ma);
-    wg_load<false>(B, ldb, nullptr, rb + kWgR, re, k0, (int)K, tid, vb, mb);
-  }
-  __syncthreads();
-  int cb = 0;
-  // one barrier per step: step s computes from buffer s & 1 while step s + 1's rows (loaded during
-  // step s - 1) are written into the other buffer between the MFMA groups
-  for (int64_t r0 = rb; r0 < re; r0 += kWgR, cb ^= 1) {
-    const float* a_col = As2[cb] + a_off;
-    const float* b_col = Bs2[cb] + b_off;
-    const bool more = r0 + kWgR < re;
-    f32x4 a[2], b0[2], b1[2];
-    a[0] = *reinterpret_cast<const f32x4*>(a_col);
-    b0[0] = *reinterpret_cast<const f32x4*>(b_col);
-    b1[0] = *reinterpret_cast<const f32x4*>(b_col + 32 * kWgP);
-#pragma unroll
-    for (int g = 0; g < kWgR / 8; ++g) {
-      const int cur = g & 1, nxt = cur ^ 1;
-      if (g + 1 < kWgR / 8) {
-        a[nxt] = *reinterpret_cast<const f32x4*>(a_col + 8 * (g + 1));
-        b0[nxt] = *reinterpret_cast<const f32x4*>(b_col + 8 * (g + 1));
-        b1[nxt] = *reinterpret_cast<const f32x4*>(b_col + 32 * kWgP + 8 * (g + 1));
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc0 = mfma32(a[cur][e], b0[cur][e], acc0);
-        acc1 = mfma32(a[cur][e], b1[cur][e], acc1);
-      }
-      if (g == 1 && more) {  // the next step's rows have had a whole step to arrive
-        if (sums)
-          wg_store<MASK, true>(As2[cb ^ 1], tid, va, ma, r0 + kWgR, re, n0, (int)N, bsum);
-        else
-          wg_store<MASK, false>(As2[cb ^ 1], tid, va, ma, r0 + kWgR, re, n0, (int)N, bsum);
-        wg_store<false, false>(Bs2[cb ^ 1], tid, vb, mb, r0 + kWgR, re, k0, (int)K, bsum);
-        if (r0 + 2 * kWgR < re) {
-          wg_load<MASK>(A, lda, A_mask, r0 + 2 * kWgR, re, n0, (int)N, tid, va, ma);
-          wg_load<false>(B, ldb, nullptr, r0 + 2 * kWgR, re, k0, (int)K, tid, vb, mb);
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // partial tile: lane holds C[n0 + 32 wm + acc_row(r)][k0 + 64 wk + (lane & 31) (+32)]
-  float* out = ws + (int64_t)blockIdx.x * N * K;
-  const int64_t k = k0 + 64 * wk + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t n = n0 + 32 * wm + acc_row(r, lane);
-    if (n < N) {
-      if (k < K) out[n * K + k] = acc0[r];
-      if (k + 32 < K) out[n * K + k + 32] = acc1[r];
-    }
-  }
-#ifdef RK_WGRAD_STAMP
-  if (tid == 0) {
-    const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    extern __device__ uint64_t g_wgrad_stamp[];
-    uint64_t* st = g_wgrad_stamp + 4 * (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-    st[0] = t0; st[1] = t1; st[2] = r0s; st[3] = r1;
-  }
-#endif
-  if (sums) {  // fold the 16 row groups holding the same four columns (threads t, t + 32, ...)
-    __syncthreads();
-    float* red = As2[0];  // [16][128]
-    *reinterpret_cast<f32x4*>(red + (tid >> 5) * kWgT + 4 * (tid & 31)) = bsum;
-    __syncthreads();
-    if (tid < kWgT && n0 + tid < N) {
-      float s = 0.f;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) s += red[g * kWgT + tid];
-      wsb[(int64_t)blockIdx.x * N + n0 + tid] = s;
-    }
-  }
+#define RK_WG_TILE_N blockIdx.y
+#define RK_WG_TILE_K blockIdx.z
+#include "wgrad_tile.h"
+#undef RK_WG_TILE_N
+#undef RK_WG_TILE_K
+}
+
+// G problems of one shape in one launch (rk_gemm_wgrad_grouped): grid (splits, n tiles x k tiles, G);
+// group g's operands by pointer, its partials in its own stretch of the workspace.
+constexpr int kWgMaxGroups = 16;
+struct WgradGroups {
+  const float* A[kWgMaxGroups];
+  const float* B[kWgMaxGroups];
+  float* C[kWgMaxGroups];
+  float* row_sums[kWgMaxGroups];
+};
+
+__global__ __launch_bounds__(kWgThreads) void wgrad_grouped_kernel(WgradGroups gp, int64_t N, int64_t K, int64_t R,
+                                                                   int64_t rps, int64_t lda, int64_t ldb,
+                                                                   float* __restrict__ ws_all, int64_t ws_group,
+                                                                   int64_t splits, int with_sums) {
+  constexpr bool MASK = false;
+  const int nt = (int)((N + kWgT - 1) / kWgT);
+  const float* __restrict__ A = gp.A[blockIdx.z];
+  const float* __restrict__ B = gp.B[blockIdx.z];
+  const float* A_mask = nullptr;
+  float* __restrict__ ws = ws_all + blockIdx.z * ws_group;
+  float* __restrict__ wsb = with_sums ? ws + splits * N * K : nullptr;
+#define RK_WG_TILE_N (blockIdx.y % nt)
+#define RK_WG_TILE_K (blockIdx.y / nt)
+#include "wgrad_tile.h"
+#undef RK_WG_TILE_N
+#undef RK_WG_TILE_K
 }
 
 // C[n][k] (+)= sum_s ws[s][n][k] (float4 per lane, the 16 waves of a workgroup split s, fixed-order
@@ -190,39 +116,22 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
                                                             int64_t S, int64_t N, int64_t K, float* __restrict__ C,
                                                             int64_t ldc, float* __restrict__ row_sums, int accumulate,
                                                             int64_t c_blocks) {
-  __shared__ f32x4 red[16][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const bool bias = blockIdx.x >= c_blocks;
-  const int64_t count4 = bias ? N / 4 : N * K / 4;
-  const int64_t e = (bias ? blockIdx.x - c_blocks : blockIdx.x) * 64 + lane;  // float4 index
-  const float* src = bias ? wsb : ws;
-  const int64_t stride = bias ? N : N * K;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (e < count4) {
-#pragma unroll 4
-    for (int64_t sp = w; sp < S; sp += 16) s += *reinterpret_cast<const f32x4*>(src + sp * stride + 4 * e);
-  }
-  red[w][lane] = s;
-  __syncthreads();
-  if (w == 0 && e < count4) {
-    f32x4 t = red[0][lane];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) t += red[i][lane];
-    if (bias) {
-      float* d = row_sums + 4 * e;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) d[c] = accumulate ? d[c] + t[c] : t[c];
-    } else {
-      const int64_t n = (4 * e) / K, k = (4 * e) % K;  // K % 4 == 0: the 4 values share a row
-      float* d = C + n * ldc + k;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) d[c] = accumulate ? d[c] + t[c] : t[c];
-    }
-  }
+#include "wgrad_reduce.h"
 }
 
-static int64_t wgrad_splits(int64_t N, int64_t K, int64_t R) {
-  const int64_t tiles = ((N + kWgT - 1) / kWgT) * ((K + kWgT - 1) / kWgT);
+// grid (c_blocks + bias blocks, G)
+__global__ __launch_bounds__(1024) void wgrad_reduce_grouped_kernel(WgradGroups gp, const float* __restrict__ ws_all,
+                                                                    int64_t ws_group, int64_t S, int64_t N, int64_t K,
+                                                                    int64_t ldc, int accumulate, int64_t c_blocks) {
+  const float* __restrict__ ws = ws_all + blockIdx.y * ws_group;
+  const float* __restrict__ wsb = ws + S * N * K;
+  float* __restrict__ C = gp.C[blockIdx.y];
+  float* __restrict__ row_sums = gp.row_sums[blockIdx.y];
+#include "wgrad_reduce.h"
+}
+
+static int64_t wgrad_splits(int64_t N, int64_t K, int64_t R, int64_t G = 1) {
+  const int64_t tiles = G * ((N + kWgT - 1) / kWgT) * ((K + kWgT - 1) / kWgT);
   // one workgroup per CU and output tile.  Two per CU (4 waves / SIMD) measured no faster
   // (tools/wgrad_clock.cpp: 40.7 us for half the rows vs 42.9 us), and the partial tiles double.
   const int64_t want = std::max<int64_t>(1, num_cus() / tiles);
@@ -275,4 +184,58 @@ RK_API int rk_gemm_wgrad(int64_t N, int64_t K, int64_t R, const float* A, int64_
   wgrad_reduce_kernel<<<(unsigned)(c_blocks + b_blocks), 1024, 0, st>>>(workspace, wsb, R > 0 ? splits : 1, N, K, C,
                                                                        ldc, row_sums, accumulate, c_blocks);
   return check_launch("rk_gemm_wgrad");
+}
+
+RK_API int64_t rk_gemm_wgrad_grouped_workspace_floats(int32_t G, int64_t N, int64_t K, int64_t R) {
+  if (G <= 0 || N <= 0 || K <= 0 || R < 0) return 0;
+  return G * wgrad_splits(N, K, R, G) * (N * K + N);
+}
+
+RK_API int rk_gemm_wgrad_grouped(int32_t G, int64_t N, int64_t K, int64_t R, const float* const* A, int64_t lda,
+                                 const float* const* B, int64_t ldb, float* const* C, int64_t ldc,
+                                 float* const* row_sums, int32_t accumulate, float* workspace,
+                                 int64_t workspace_floats, void* stream) {
+  if (G <= 0 || N <= 0 || K <= 0 || R < 0 || !A || !B || !C || ldc < K || lda < N || ldb < K)
+    return fail(RK_ERR_INVALID, "rk_gemm_wgrad_grouped: bad shape / operand");
+  if (G > kWgMaxGroups) return fail(RK_ERR_UNSUPPORTED, "rk_gemm_wgrad_grouped: %d groups (<= %d)", G, kWgMaxGroups);
+  WgradGroups gp = {};
+  uintptr_t align = reinterpret_cast<uintptr_t>(workspace);
+  for (int g = 0; g < G; ++g) {
+    if (!C[g] || (R > 0 && (!A[g] || !B[g])) || (row_sums && !row_sums[g]))
+      return fail(RK_ERR_INVALID, "rk_gemm_wgrad_grouped: group %d: null operand", g);
+    gp.A[g] = A[g];
+    gp.B[g] = B[g];
+    gp.C[g] = C[g];
+    gp.row_sums[g] = row_sums ? row_sums[g] : nullptr;
+    align |= reinterpret_cast<uintptr_t>(A[g]) | reinterpret_cast<uintptr_t>(B[g]) | reinterpret_cast<uintptr_t>(C[g]) |
+             reinterpret_cast<uintptr_t>(gp.row_sums[g]);
+  }
+  if ((N | K | lda | ldb | ldc) % 4 || (align & 15))
+    return fail(RK_ERR_UNSUPPORTED, "rk_gemm_wgrad_grouped: needs N, K, lda, ldb, ldc multiples of 4 and 16-B "
+                                    "aligned pointers");
+  const int64_t need = rk_gemm_wgrad_grouped_workspace_floats(G, N, K, R);
+  if (!workspace || workspace_floats < need)
+    return fail(RK_ERR_INVALID, "rk_gemm_wgrad_grouped: workspace of %lld floats, needs %lld",
+                (long long)workspace_floats, (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t S = wgrad_splits(N, K, R, G);
+  int64_t rps = (R + S - 1) / S;
+  rps = std::max<int64_t>(kWgR, (rps + kWgR - 1) / kWgR * kWgR);
+  const int64_t splits = std::max<int64_t>(1, (R + rps - 1) / rps);
+  const int64_t ws_group = S * (N * K + N);  // splits <= S
+  const int64_t tiles = ((N + kWgT - 1) / kWgT) * ((K + kWgT - 1) / kWgT);
+  if (tiles > 65535) return fail(RK_ERR_UNSUPPORTED, "rk_gemm_wgrad_grouped: output too large");
+  if (R > 0) {
+    const dim3 grid((unsigned)splits, (unsigned)tiles, (unsigned)G);
+    wgrad_grouped_kernel<<<grid, kWgThreads, 0, st>>>(gp, N, K, R, rps, lda, ldb, workspace, ws_group, splits,
+                                                      row_sums != nullptr);
+  } else {
+    (void)hipMemsetAsync(workspace, 0, sizeof(float) * (size_t)(G * ws_group), st);
+  }
+  const int64_t c_blocks = (N * K / 4 + 63) / 64;
+  const int64_t b_blocks = row_sums ? (N / 4 + 63) / 64 : 0;
+  const dim3 rgrid((unsigned)(c_blocks + b_blocks), (unsigned)G);
+  wgrad_reduce_grouped_kernel<<<rgrid, 1024, 0, st>>>(gp, workspace, ws_group, R > 0 ? splits : 1, N, K, ldc, accumulate,
+                                                      c_blocks);
+  return check_launch("rk_gemm_wgrad_grouped");
 }

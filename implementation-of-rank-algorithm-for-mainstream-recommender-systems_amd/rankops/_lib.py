@@ -22,7 +22,7 @@ RK_ERR_UNSUPPORTED = 4  # include/rankops.h
 RK_FLAG_INDEX_OOB = 1
 RK_ACT_NONE, RK_ACT_RELU, RK_ACT_LEAKY, RK_ACT_DICE, RK_ACT_PRELU = 0, 1, 2, 3, 4
 RK_MAX_SEGMENTS = 64
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Segment(ctypes.Structure):
@@ -112,6 +112,10 @@ class SparseAdamTensor(ctypes.Structure):
 class PackBlock(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("add", c_void_p), ("dst", c_void_p), ("ld_src", c_int64), ("ld_add", c_int64),
                 ("rows", c_int64), ("dim", c_int32), ("reserved", c_int32)]
+
+
+class PackItem(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("out", c_void_p), ("ldw", c_int64), ("n", c_int32), ("k", c_int32)]
 
 
 class MmoeLayer(ctypes.Structure):
@@ -441,6 +445,25 @@ SIGNATURES = {
     "rk_mmoe_forward": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
                                        c_void_p, c_void_p, c_int32, POINTER(MmoeLayer), c_int32, POINTER(c_void_p),
                                        POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rk_mlp_pack_weights": (ctypes.c_int, [POINTER(PackItem), c_int32, c_void_p]),
+    "rk_mmoe_forward_train": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
+                                             c_void_p, c_void_p, c_int32, POINTER(MmoeLayer), c_int32, POINTER(c_void_p),
+                                             POINTER(c_void_p), ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p,
+                                             POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
+    "rk_mmoe_mix_backward": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p,
+                                            c_int64, c_int32, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_int64,
+                                            c_int32, c_void_p]),
+    "rk_mmoe_head_backward": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                             POINTER(c_void_p), c_void_p, c_float, c_void_p, c_int32, c_void_p, c_int32,
+                                             c_void_p]),
+    "rk_gemm_grouped": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, POINTER(c_void_p), c_int64,
+                                       POINTER(c_void_p), c_int64, POINTER(c_void_p), c_int64, POINTER(c_void_p),
+                                       c_int64, c_float, c_int32, c_void_p]),
+    "rk_gemm_wgrad_grouped": (ctypes.c_int, [c_int32, c_int64, c_int64, c_int64, POINTER(c_void_p), c_int64,
+                                             POINTER(c_void_p), c_int64, POINTER(c_void_p), c_int64, POINTER(c_void_p),
+                                             c_int32, c_void_p, c_int64, c_void_p]),
+    "rk_gemm_wgrad_grouped_workspace_floats": (c_int64, [c_int32, c_int64, c_int64, c_int64]),
     "rk_shard_gather_rows_split": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_void_p, c_int32, c_int64,
                                                   c_int64, c_int64, c_void_p, c_void_p]),
     "rk_shard_fm_assemble": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p,

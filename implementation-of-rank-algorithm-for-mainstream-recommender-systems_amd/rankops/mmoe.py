@@ -5,7 +5,8 @@ The reference's README lists the model; its script is not in the snapshot, so th
 one, in the conventions of the reference's DCN (algorithm/DCN/dcn.py):
 
 `MMoE(vocab_dir, num_experts=4, expert_hidden_units=(256, 128), tower_hidden_units=(64,),
-      task_names=("read_comment", "like", "click_avatar"), dropout_rate=0.1, *, vocab_sizes=None)`
+      task_names=("read_comment", "like", "click_avatar"), dropout_rate=0.1, *, vocab_sizes=None,
+      trainable=False, sparse_grad=False)`
 `forward(dense [B, 16], category {6 x [B]}) -> (probabilities [B, K], logits [B, K])`, column k = task_names[k].
 
 Modules are created in this order (it fixes the seeded values and the state_dict keys):
@@ -20,13 +21,24 @@ In eval mode (Dropout the identity), with x = cat[dense, embeddings]:
 
 One launch, rk_mmoe_forward (csrc/mmoe.hip): the row gather, the K gates as one GEMM and their
 softmax, the experts with the mix behind each one's last layer, the towers and the heads; the
-[B, E, H] expert outputs, the gates and the mixtures never reach HBM.  Train mode raises
-NotImplementedError (the backward of the mix and the gates is not built); CPU tensors raise the
-engine's "ROCm GPU" error; a configuration outside the kernel's envelope (common.mmoe_fits) is an error,
-not a fallback.
+[B, E, H] expert outputs, the gates and the mixtures never reach HBM.  CPU tensors raise the engine's
+"ROCm GPU" error; a configuration outside the kernel's envelope (common.mmoe_fits) is an error, not a
+fallback.
 
-`rankops.mmoe(x, experts, gates, towers=None)` is the same kernel on plain tensors (ops.mmoe); this
-module is callable so that `rankops.mmoe` is both the module and that function.
+Training is opt-in: `MMoE(..., trainable=True)` in train mode returns (probabilities, logits) attached to
+autograd (rankops.train._MMoETrain): rk_mmoe_forward_train, the same kernel with Dropout live behind
+every ReLU and the activations kept, then the backward of the heads, towers, mix, gates and experts in a
+number of launches that does not depend on E or K (ops.mmoe_backward), and the embedding gradients;
+under no_grad it runs the same forward and keeps nothing; `sparse_grad=True` hands the tables sparse
+COO gradients (rankops.SparseAdam).  The default (trainable=False) raises NotImplementedError in train
+mode, as before.  Neither flag adds, reorders or re-initialises a parameter.  Dropout masks are the
+engine's counter hash: with De = len(expert_hidden_units), Dt = len(tower_hidden_units) and (seed, slot)
+of the forward (model._dropout), expert e layer l drew `ops.dropout_mask(seed + e * De + l, slot, B, n, p)`
+and tower k layer l `ops.dropout_mask(seed + E * De + k * Dt + l, slot, B, n, p)` (element b * n + j).
+
+`rankops.mmoe(x, experts, gates, towers=None)` is the same kernel on plain tensors (ops.mmoe),
+differentiable when an input requires grad; this module is callable so that `rankops.mmoe` is both the
+module and that function.
 """
 from __future__ import annotations
 
@@ -36,7 +48,7 @@ import types
 import torch
 import torch.nn as nn
 
-from . import common, ops
+from . import common, ops, train
 from .common import EngineModule, check_eval, table_rows
 
 DEFAULT_TASKS = ("read_comment", "like", "click_avatar")
@@ -54,8 +66,11 @@ def _stack(width, units, dropout_rate):
 
 class MMoE(EngineModule):
     def __init__(self, vocab_dir, num_experts=4, expert_hidden_units=(256, 128), tower_hidden_units=(64,),
-                 task_names=DEFAULT_TASKS, dropout_rate=0.1, *, vocab_sizes=None):
+                 task_names=DEFAULT_TASKS, dropout_rate=0.1, *, vocab_sizes=None, trainable=False, sparse_grad=False):
         super().__init__()
+        self.trainable = bool(trainable)      # train mode runs the HIP train forward / backward (rankops.train)
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
+        self.dropout_rate = float(dropout_rate)
         expert_hidden_units = tuple(int(h) for h in expert_hidden_units)
         tower_hidden_units = tuple(int(h) for h in tower_hidden_units)
         task_names = tuple(task_names)
@@ -177,14 +192,22 @@ class MMoE(EngineModule):
         return run
 
     def forward(self, dense, category):
-        check_eval(self)
+        if not self.trainable:
+            check_eval(self)  # train mode is opt-in (trainable=True)
         dense = ops.as_f32(dense, "dense")
         if dense.dim() != 2 or dense.shape[1] < self.num_dense_features:
             raise ValueError(f"MMoE.forward: dense must be [B, {self.num_dense_features}], got {tuple(dense.shape)}")
         names, idx = self._indices(category)
         B, dev = dense.shape[0], dense.device
-        if B == 0:
+        if B == 0 and not self.training:
             return common.empty_rows(dev, 2, (0, len(self.task_names)))
+        if self.training:  # Dropout live, HIP backward (rankops.train); an empty batch: zero gradients
+            if not self.fits():
+                raise RuntimeError("MMoE: configuration outside rk_mmoe_forward's envelope (common.mmoe_fits)")
+            if any(t.dim() != 1 or t.shape[0] != B for t in idx):
+                raise ValueError("MMoE.forward: every category feature must be a 1-D tensor of the batch's length")
+            grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+            return train.mmoe_train_forward(self, dense, names, idx, grad)
         stream = ops._lib.raw_stream(dev)
         own = all(t is category[n] for t, n in zip(idx, names))  # no converted copies: addresses are the caller's
         if common.EAGER_CACHE and own:

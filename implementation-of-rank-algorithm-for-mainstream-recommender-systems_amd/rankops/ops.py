@@ -1680,8 +1680,9 @@ def mmoe_forward_args(segs, width, batch, experts, gate_image, gate_bias, num_ta
     return args, (arr, ex, tw, hw, hb)
 
 
-def _mmoe_stack(layers, k_in, what):
-    """[(W, b)…] -> ([(image, bias, n, 'relu')…], output width), every Linear followed by ReLU."""
+def _mmoe_stack(layers, k_in, what, pack=True):
+    """[(W, b)…] -> ([(image, bias, n, 'relu')…], output width), every Linear followed by ReLU.  pack=False
+    (an empty batch: nothing is launched) checks the shapes and leaves the images None."""
     out = []
     for l, (w, b) in enumerate(layers):
         as_f32(w, f"{what} layer {l} weight")
@@ -1690,9 +1691,295 @@ def _mmoe_stack(layers, k_in, what):
         if b is not None and (as_f32(b, f"{what} layer {l} bias").dim() != 1 or b.shape[0] != w.shape[0]
                               or not b.is_contiguous()):
             raise ValueError(f"rankops.mmoe: {what} layer {l} bias must be a contiguous [{w.shape[0]}] tensor")
-        out.append((pack_mlp_weight(w), b.detach() if b is not None else None, w.shape[0], "relu"))
+        out.append((pack_mlp_weight(w) if pack else None, b.detach() if b is not None else None, w.shape[0], "relu"))
         k_in = w.shape[0]
     return out, k_in
+
+
+# ---------------------------------------------------------------- MMoE training ("Training")
+
+def p4(v: int) -> int:
+    return (v + 3) // 4 * 4
+
+
+def _ptrs(values):
+    return (ctypes.c_void_p * len(values))(*values)
+
+
+def pack_mlp_weights(pairs, stream):
+    """rk_mlp_pack_weights: [(weight [n, k] with unit column stride, image [pad64(n), pad64(k)])…], one launch."""
+    if not pairs:
+        return
+    arr = (_lib.PackItem * len(pairs))()
+    for it, (w, out) in zip(arr, pairs):
+        it.w, it.out, it.ldw, it.n, it.k = w.data_ptr(), out.data_ptr(), w.stride(0), w.shape[0], w.shape[1]
+    check(_lib.load().rk_mlp_pack_weights(arr, len(pairs), stream), "rk_mlp_pack_weights")
+
+
+def mlp_image(n, k, device):
+    return torch.empty((n + 63) // 64 * 64, (k + 63) // 64 * 64, device=device, dtype=torch.float32)
+
+
+def gemm_grouped(trans_a, trans_b, M, N, R, A, lda, B, ldb, C, ldc, stream, *, C_mask=None, ldmask=0, mask_scale=1.0,
+                 accumulate=False):
+    """rk_gemm_grouped; A, B, C, C_mask are lists of device addresses (fptr), one per group."""
+    check(_lib.load().rk_gemm_grouped(len(C), int(trans_a), int(trans_b), M, N, R, _ptrs(A), lda, _ptrs(B), ldb,
+                                      _ptrs(C), ldc, _ptrs(C_mask) if C_mask is not None else None, ldmask,
+                                      mask_scale, int(accumulate), stream), "rk_gemm_grouped")
+
+
+def gemm_wgrad_grouped(N, K, R, A, lda, B, ldb, C, ldc, row_sums, device, stream, accumulate=False):
+    """rk_gemm_wgrad_grouped over lists of device addresses, with the shared wgrad workspace."""
+    lib = _lib.load()
+    G = len(C)
+    nws = lib.rk_gemm_wgrad_grouped_workspace_floats(G, N, K, R)
+    ws = _wgrad_workspace(nws, device, stream)
+    check(lib.rk_gemm_wgrad_grouped(G, N, K, R, _ptrs(A), lda, _ptrs(B), ldb, _ptrs(C), ldc,
+                                    _ptrs(row_sums) if row_sums is not None else None, int(accumulate), ptr(ws),
+                                    ws.numel(), stream), "rk_gemm_wgrad_grouped")
+
+
+def mmoe_mix_backward(B, E, K, H, dmixed, ld_dm, pitch_dm, f, ld_f, pitch_f, gate_probs, mask_scale, dgl, ld_dgl, dz,
+                      ld_dz, pitch_dz, stream):
+    """rk_mmoe_mix_backward; dmixed, f, dgl, dz are device addresses or tensors."""
+    a = [t.data_ptr() if isinstance(t, torch.Tensor) else t for t in (dmixed, f, gate_probs, dgl, dz)]
+    check(_lib.load().rk_mmoe_mix_backward(B, E, K, H, a[0], ld_dm, pitch_dm, a[1], ld_f, pitch_f, a[2], mask_scale,
+                                           a[3], ld_dgl, a[4], ld_dz, pitch_dz, stream), "rk_mmoe_mix_backward")
+
+
+def mmoe_head_backward(B, K, n, pitch, dlogits, dprobs, probs, head_w, t, mask_scale, g_out, dt, accumulate, stream):
+    check(_lib.load().rk_mmoe_head_backward(B, K, n, pitch, ptr(dlogits), ptr(dprobs), ptr(probs),
+                                            _ptrs([w.data_ptr() for w in head_w]), ptr(t), mask_scale, ptr(g_out),
+                                            g_out.stride(0), ptr(dt), int(accumulate), stream),
+          "rk_mmoe_head_backward")
+
+
+class MmoeShape:
+    """Widths of one MMoE: the row, E experts of units eu, K tasks with towers of units tu."""
+
+    def __init__(self, width, E, K, eu, tu, heads: bool):
+        self.width, self.E, self.K, self.eu, self.tu, self.heads = width, E, K, tuple(eu), tuple(tu), heads
+        self.H = self.eu[-1]
+        # a width off the 4 grid: its buffers are padded to the grid (the forward and the backward kernels
+        # write zeros there) and its gradients are cut out of padded results
+        self.padded = any(v % 4 for v in (width, E * K) + self.eu + self.tu)
+        self.zw = E * p4(self.eu[0]) + p4(K * E)   # columns of dZ0 = [dz_{0,0} | … | dz_{E-1,0} | dgate_logits]
+        self.zw_padded = self.zw != E * self.eu[0] + K * E   # dZ0 has pad columns of its own (zero-filled)
+
+
+def mmoe_stacked_weight(sh: MmoeShape, experts, gates):
+    """[W_{0,0}; …; W_{E-1,0}; W_gate_0; …] as one [zw, p4(width)] matrix (rows and columns on the 4 grid,
+    zeros between): layer 0 of every expert and the K gates read the same x, so their data gradient is
+    one GEMM against it, their weight gradients one product, and its tail is the stacked gate weight."""
+    first = [layers[0][0].detach() for layers in experts] + [w.detach() for w, _ in gates]
+    pad = torch.nn.functional.pad
+    cols = p4(sh.width) - sh.width
+    if not sh.zw_padded:  # rows already on the grid: one cat, one pad of the columns if the width is off it
+        out = torch.cat(first, 0)
+        return pad(out, (0, cols)) if cols else out
+    # (a fixed number of launches whatever E and K: stack, pad, cat, pad, cat)
+    n0, KE = sh.eu[0], sh.K * sh.E
+    top = pad(torch.stack(first[:sh.E], 0), (0, cols, 0, p4(n0) - n0)).view(sh.E * p4(n0), p4(sh.width))
+    tail = pad(torch.cat(first[sh.E:], 0), (0, cols, 0, p4(KE) - KE))
+    return torch.cat([top, tail], 0)
+
+
+def mmoe_forward_train(segs, sh: MmoeShape, B, stacks, gate_image, gate_bias, tstacks, heads, device, p, seed, slot):
+    """rk_mmoe_forward_train: one launch; returns the saved buffers (include/rankops.h) as a dict."""
+    new = torch.empty  # (the kernel writes the pad columns)
+    f32 = dict(device=device, dtype=torch.float32)
+    E, K = sh.E, sh.K
+    s = dict(x=new(B, p4(sh.width), **f32), eacts=[new(B, E * p4(n), **f32) for n in sh.eu],
+             tacts=[new(B, K * p4(n), **f32) for n in sh.tu], mixed=new(B, K * p4(sh.H), **f32),
+             gate_probs=torch.empty(B, K, E, **f32), logits=None, probs=None)
+    if heads is not None:
+        s["logits"], s["probs"] = torch.empty(B, K, **f32), torch.empty(B, K, **f32)
+    if B == 0:
+        return s
+    args, keep = mmoe_forward_args(segs, sh.width, B, stacks, gate_image, gate_bias, K, tstacks, heads, device)
+    ea = _ptrs([t.data_ptr() for t in s["eacts"]])
+    ta = _ptrs([t.data_ptr() for t in s["tacts"]]) if sh.tu else None
+    call = args[:14] + [float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(slot), s["x"].data_ptr(), ea, ta, ptr(s["logits"]),
+                        ptr(s["probs"]), s["mixed"].data_ptr(), s["gate_probs"].data_ptr(), _lib.raw_stream(device)]
+    check(_lib.load().rk_mmoe_forward_train(*call), "rk_mmoe_forward_train")
+    return s
+
+
+def mmoe_backward(sh: MmoeShape, B, s, wst, experts, gates, towers, p, d_mixed, d_logits, d_probs, need_dx, device):
+    """The MMoE backward from the buffers of mmoe_forward_train (s), the stacked layer-0 / gate weight
+    (wst) and the plain weights (experts: E lists of (W, b); gates: K (W, b); towers: K (hidden, (w, b)) or
+    None).  d_mixed [B, K, H], d_logits, d_probs [B, K]: the incoming gradients, each may be None.
+    Returns (dx [B, width] or None, expert grads [[(dW, db)…]…], gate grads [(dW, db)…], tower grads
+    [([(dW, db)…], (dw, db))…] or None); a db is returned for every layer (callers drop those of bias-free
+    layers).  The launches do not depend on E or K: per layer one rk_gemm_wgrad_grouped and one
+    rk_gemm_grouped over the experts (tasks); layer 0 of all experts and the gates as one rk_gemm_wgrad and
+    one rk_gemm; no float atomics, fixed-order sums."""
+    E, K, H, width = sh.E, sh.K, sh.H, sh.width
+    De, Dt = len(sh.eu), len(sh.tu)
+    pe, pt, pm, w4 = [p4(n) for n in sh.eu], [p4(n) for n in sh.tu], p4(H), p4(width)
+    f32 = dict(device=device, dtype=torch.float32)
+    # Pad columns: the head and mix kernels write zeros into theirs; rk_gemm_grouped leaves those of its
+    # outputs unwritten, which only reach rows of padded weight gradients that are cut away (the next
+    # grouped GEMM reduces over the exact width).  dZ0's own pad columns are read by the stacked data
+    # gradient, so dZ0 is zero-filled when it has any.
+    new = torch.empty
+    st = _lib.raw_stream(device)
+    scale = 1.0 / (1.0 - p)
+    lib = _lib.load()
+
+    def wgrad(N, Kd, A, lda, Bm, ldb):
+        dW, db = torch.empty(N, Kd, **f32), torch.empty(N, **f32)
+        nws = _wgrad_ws_floats(lib, N, Kd, B)
+        ws = _wgrad_workspace(nws, device, st)
+        check(lib.rk_gemm_wgrad(N, Kd, B, A.data_ptr(), lda, None, Bm.data_ptr(), ldb, dW.data_ptr(), Kd, db.data_ptr(), 0,
+                                ws.data_ptr(), ws.numel(), st), "rk_gemm_wgrad")
+        return dW, db
+
+    def incoming():  # d_mixed [B, K, H] in the saved layout [B, K pm], a private copy (it is added to)
+        if pm == H:
+            return d_mixed.reshape(B, K * H).clone()
+        buf = torch.zeros(B, K, pm, **f32)
+        buf[:, :, :H] = d_mixed
+        return buf.view(B, K * pm)
+
+    tower_grads = None
+    dmix = None
+    if towers is not None and (d_logits is not None or d_probs is not None):
+        last, plast = (sh.tu[-1], pt[-1]) if Dt else (H, pm)
+        feed = s["tacts"][-1] if Dt else s["mixed"]            # the heads' input, [B, K plast]
+        pk = p4(K)
+        g = torch.empty(B, pk, **f32)
+        own = Dt == 0 and d_mixed is not None
+        dz = incoming() if own else new(B, K * plast, **f32)
+        mmoe_head_backward(B, K, last, plast, d_logits, d_probs, s["probs"], [w for _, (w, _) in towers],
+                           s["tacts"][-1] if Dt else None, scale, g, dz, own, st)
+        hd, hb = wgrad(pk, K * plast, g, pk, feed, K * plast)  # the heads' dw are its diagonal blocks
+        head_grads = [(hd[k, k * plast:k * plast + last].view(1, last), hb[k:k + 1]) for k in range(K)]
+        hidden_grads = [[None] * Dt for _ in range(K)]
+        for l in range(Dt - 1, -1, -1):
+            n, n_in, p_in = sh.tu[l], (sh.tu[l - 1] if l else H), (pt[l - 1] if l else pm)
+            inp = s["tacts"][l - 1] if l else s["mixed"]
+            dW, db = torch.empty(K, pt[l], p4(n_in), **f32), torch.empty(K, pt[l], **f32)
+            gemm_wgrad_grouped(pt[l], p4(n_in), B, [fptr(dz, k * pt[l]) for k in range(K)], K * pt[l],
+                               [fptr(inp, k * p_in) for k in range(K)], K * p_in, [dW[k].data_ptr() for k in range(K)],
+                               p4(n_in), [db[k].data_ptr() for k in range(K)], device, st)
+            dW, db = dW[:, :n, :n_in].contiguous(), db[:, :n].contiguous()  # (no launch unless padded)
+            for k in range(K):
+                hidden_grads[k][l] = (dW[k], db[k])
+            add = l == 0 and d_mixed is not None
+            d_in = incoming() if add else new(B, K * p_in, **f32)
+            ws_ = [towers[k][0][l][0] for k in range(K)]
+            gemm_grouped(False, True, B, n_in, n, [fptr(dz, k * pt[l]) for k in range(K)], K * pt[l],
+                         [w.data_ptr() for w in ws_], ws_[0].stride(0), [fptr(d_in, k * p_in) for k in range(K)],
+                         K * p_in, st, C_mask=[fptr(inp, k * p_in) for k in range(K)] if l else None, ldmask=K * p_in,
+                         mask_scale=scale, accumulate=add)
+            dz = d_in
+        dmix = dz
+        tower_grads = [(hidden_grads[k], head_grads[k]) for k in range(K)]
+    elif d_mixed is not None:
+        dmix = incoming()
+    if towers is not None and tower_grads is None:  # the heads saw no gradient
+        tower_grads = [([(torch.zeros_like(W), torch.zeros(W.shape[0], **f32)) for W, _ in hidden],
+                        (torch.zeros_like(w), torch.zeros(1, **f32))) for hidden, (w, _) in towers]
+    if dmix is None:
+        dmix = torch.zeros(B, K * pm, **f32)
+
+    # the mix and the gates' softmax; with one expert layer its dz goes straight into dZ0
+    dZ0 = (torch.zeros if sh.zw_padded else torch.empty)(B, sh.zw, **f32)
+    if De == 1:
+        dz, ld_dz = dZ0, sh.zw
+    else:
+        dz, ld_dz = new(B, E * pe[-1], **f32), E * pe[-1]
+    mmoe_mix_backward(B, E, K, H, dmix, K * pm, pm, s["eacts"][-1], E * pe[-1], pe[-1], s["gate_probs"], scale,
+                      fptr(dZ0, E * pe[0]), sh.zw, dz, ld_dz, pe[-1], st)
+    expert_grads = [[None] * De for _ in range(E)]
+    for l in range(De - 1, 0, -1):
+        n, n_in = sh.eu[l], sh.eu[l - 1]
+        inp = s["eacts"][l - 1]
+        dW, db = torch.empty(E, pe[l], pe[l - 1], **f32), torch.empty(E, pe[l], **f32)
+        gemm_wgrad_grouped(pe[l], pe[l - 1], B, [fptr(dz, e * pe[l]) for e in range(E)], ld_dz,
+                           [fptr(inp, e * pe[l - 1]) for e in range(E)], E * pe[l - 1],
+                           [dW[e].data_ptr() for e in range(E)], pe[l - 1], [db[e].data_ptr() for e in range(E)],
+                           device, st)
+        dW, db = dW[:, :n, :n_in].contiguous(), db[:, :n].contiguous()
+        for e in range(E):
+            expert_grads[e][l] = (dW[e], db[e])
+        if l == 1:
+            d_in, ld_in = dZ0, sh.zw
+        else:
+            d_in, ld_in = new(B, E * pe[l - 1], **f32), E * pe[l - 1]
+        ws_ = [experts[e][l][0] for e in range(E)]
+        gemm_grouped(False, True, B, n_in, n, [fptr(dz, e * pe[l]) for e in range(E)], ld_dz,
+                     [w.data_ptr() for w in ws_], ws_[0].stride(0), [fptr(d_in, e * pe[l - 1]) for e in range(E)],
+                     ld_in, st, C_mask=[fptr(inp, e * pe[l - 1]) for e in range(E)], ldmask=E * pe[l - 1],
+                     mask_scale=scale)
+        dz, ld_dz = d_in, ld_in
+    # layer 0 of every expert and the K gates: one weight-gradient product, one data-gradient GEMM
+    dWs, dbs = wgrad(sh.zw, w4, dZ0, sh.zw, s["x"], w4)
+    n0, r0 = sh.eu[0], E * pe[0]
+    dW0 = dWs[:r0].view(E, pe[0], w4)[:, :n0, :width].contiguous()   # one cut for all experts, one for all gates
+    db0 = dbs[:r0].view(E, pe[0])[:, :n0].contiguous()
+    dWg = dWs[r0:r0 + K * E, :width].contiguous().view(K, E, width)
+    dbg = dbs[r0:r0 + K * E].view(K, E)
+    for e in range(E):
+        expert_grads[e][0] = (dW0[e], db0[e])
+    gate_grads = [(dWg[k], dbg[k]) for k in range(K)]
+    dx = None
+    if need_dx:
+        dx = torch.empty(B, width, **f32)
+        gemm(False, True, B, width, sh.zw, dZ0, sh.zw, wst, wst.stride(0), dx, split=1)
+    return dx, expert_grads, gate_grads, tower_grads
+
+
+class _MmoeFn(torch.autograd.Function):
+    """rankops.mmoe with autograd: rk_mmoe_forward_train without dropout, mmoe_backward.  Inputs after the
+    fixed arguments: x, then every weight and bias of `layout` flattened (None for an absent bias)."""
+
+    @staticmethod
+    def forward(ctx, sh, launch, x, *flat):
+        s = launch()
+        ctx.sh, ctx.s, ctx.flat, ctx.B = sh, s, flat, x.shape[0]
+        B, K, H, E = x.shape[0], sh.K, sh.H, sh.E
+        mixed = s["mixed"].view(B, K, p4(H))[:, :, :H]
+        outs = (mixed, s["gate_probs"]) + ((s["logits"], s["probs"]) if sh.heads else ())
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
+        return outs
+
+    @staticmethod
+    def backward(ctx, d_mixed, d_gates, d_logits=None, d_probs=None):
+        sh, s, flat, B = ctx.sh, ctx.s, ctx.flat, ctx.B
+        if d_gates is not None:
+            raise NotImplementedError("rankops.mmoe: a gradient flowing into gate_probs is not supported "
+                                      "(differentiate mixed, logits or probs)")
+        experts, gates, towers, wst = s["weights"]
+        dev = s["x"].device
+        if B == 0:
+            return (None, None, torch.zeros(0, sh.width, device=dev)) + tuple(
+                None if t is None else torch.zeros_like(t) for t in flat)
+        like = lambda g, shape: None if g is None else g.to(torch.float32).reshape(shape).contiguous()
+        dx, eg, gg, tg = mmoe_backward(sh, B, s, wst, experts, gates, towers, 0.0, like(d_mixed, (B, sh.K, sh.H)),
+                                       like(d_logits, (B, sh.K)), like(d_probs, (B, sh.K)), ctx.needs_input_grad[2],
+                                       dev)
+        out = []
+        for e in range(sh.E):
+            for l in range(len(sh.eu)):
+                out += list(eg[e][l])
+        for k in range(sh.K):
+            out += list(gg[k])
+        if towers is not None:
+            for k in range(sh.K):
+                for l in range(len(sh.tu)):
+                    out += list(tg[k][0][l])
+                out += list(tg[k][1])
+        grads = [None if t is None else g.reshape(t.shape) for t, g in zip(flat, out)]
+        return (None, None, dx, *grads)
+
+
+def _mmoe_wants_grad(x, experts, gates, towers):
+    ts = [x] + [t for layers in experts for wb in layers for t in wb] + [t for wb in gates for t in wb]
+    if towers is not None:
+        ts += [t for hidden, out in towers for wb in list(hidden) + [out] for t in wb]
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
 def mmoe(x: torch.Tensor, experts, gates, towers=None):
@@ -1706,7 +1993,11 @@ def mmoe(x: torch.Tensor, experts, gates, towers=None):
                                              Linear + ReLU
 
     Returns (mixed [B, K, H], gate_probs [B, K, E]); with towers also (logits [B, K], probs [B, K]).
-    Eval only (no autograd)."""
+    Differentiable whenever x or any weight or bias requires grad (rk_mmoe_forward_train without dropout
+    and the grouped backward, DESIGN.md §4d "Training"): gradients for x, every expert, gate and tower
+    (W, b) and the output layers, from the incoming gradients of mixed, logits and probs.  A gradient
+    flowing into gate_probs raises NotImplementedError.  With nothing requiring grad the call is the eval
+    launch, bit for bit."""
     as_f32(x, "x")
     if x.dim() != 2 or x.stride(1) != 1:
         raise ValueError(f"rankops.mmoe: x must be [B, width] with unit column stride, got {tuple(x.shape)}")
@@ -1719,7 +2010,7 @@ def mmoe(x: torch.Tensor, experts, gates, towers=None):
     for e, layers in enumerate(experts):
         if len(layers) == 0:
             raise ValueError(f"rankops.mmoe: expert {e} has no layer")
-        st, h = _mmoe_stack(layers, width, f"expert {e}")
+        st, h = _mmoe_stack(layers, width, f"expert {e}", B > 0)
         if H is not None and h != H:
             raise ValueError(f"rankops.mmoe: expert {e} ends {h} wide, expert 0 {H}")
         stacks.append(st)
@@ -1728,9 +2019,9 @@ def mmoe(x: torch.Tensor, experts, gates, towers=None):
         as_f32(w, f"gate {k} weight")
         if tuple(w.shape) != (E, width) or (b is not None and tuple(as_f32(b, f"gate {k} bias").shape) != (E,)):
             raise ValueError(f"rankops.mmoe: gate {k} must be (W [{E}, {width}], b [{E}] or None)")
-    gate_image = pack_mlp_weight(torch.cat([w.detach() for w, _ in gates], 0))
+    gate_image = pack_mlp_weight(torch.cat([w.detach() for w, _ in gates], 0)) if B > 0 else None
     gate_bias = None
-    if any(b is not None for _, b in gates):
+    if B > 0 and any(b is not None for _, b in gates):
         gate_bias = torch.cat([b.detach() if b is not None else torch.zeros(E, device=dev) for _, b in gates], 0)
     tstacks = heads = None
     if towers is not None:
@@ -1738,13 +2029,35 @@ def mmoe(x: torch.Tensor, experts, gates, towers=None):
             raise ValueError(f"rankops.mmoe: {K} gates need {K} towers, got {len(towers)}")
         tstacks, heads = [], []
         for k, (hidden, (w_out, b_out)) in enumerate(towers):
-            st, last = _mmoe_stack(hidden, H, f"tower {k}")
+            st, last = _mmoe_stack(hidden, H, f"tower {k}", B > 0)
             as_f32(w_out, f"tower {k} output weight")
             as_f32(b_out, f"tower {k} output bias")
             if w_out.numel() != last or b_out.numel() != 1:
                 raise ValueError(f"rankops.mmoe: tower {k} output must be (w [1, {last}], b [1])")
             tstacks.append(st)
             heads.append((w_out.detach().reshape(-1).contiguous(), b_out.detach().reshape(1)))
+    if _mmoe_wants_grad(x, experts, gates, towers):
+        eu = [w.shape[0] for w, _ in experts[0]]
+        tu = [w.shape[0] for w, _ in towers[0][0]] if towers is not None else []
+        if any([w.shape[0] for w, _ in layers] != eu for layers in experts) or (
+                towers is not None and any([w.shape[0] for w, _ in hidden] != tu for hidden, _ in towers)):
+            raise ValueError("rankops.mmoe: with autograd all experts (towers) must have the same widths")
+        sh = MmoeShape(width, E, K, eu, tu, towers is not None)
+        dexp = [[(w.detach(), b) for w, b in layers] for layers in experts]
+        dgat = [(w.detach(), b) for w, b in gates]
+        dtow = None if towers is None else [([(w.detach(), b) for w, b in hidden], (wo.detach().reshape(-1), bo))
+                                            for hidden, (wo, bo) in towers]
+        wst = mmoe_stacked_weight(sh, dexp, dgat) if B > 0 else None  # (an empty batch launches nothing)
+        segs = [dense_segment(x.detach(), min(128, width - c), c, c) for c in range(0, width, 128)]
+
+        def launch():
+            s = mmoe_forward_train(segs, sh, B, stacks, gate_image, gate_bias, tstacks, heads, dev, 0.0, 0, None)
+            s["weights"] = (dexp, dgat, dtow, wst)
+            return s
+        flat = [t for layers in experts for wb in layers for t in wb] + [t for wb in gates for t in wb]
+        if towers is not None:
+            flat += [t for hidden, out in towers for wb in list(hidden) + [out] for t in wb]
+        return _MmoeFn.apply(sh, launch, x, *flat)
     mixed = torch.empty(B, K, H, device=dev, dtype=torch.float32)
     gate_probs = torch.empty(B, K, E, device=dev, dtype=torch.float32)
     logits = probs = None

@@ -654,6 +654,146 @@ def xdeepfm_train_forward(model, names, idx, grad: bool = True):
     return _XDeepFMTrain.apply(model, names, idx, *params)
 
 
+# ---------------------------------------------------------------- MMoE
+
+def _mmoe_lists(model):
+    """(experts, gates, towers) of a rankops.MMoE in ops.mmoe_backward's form, detached."""
+    lin = model._linears
+    experts = [[(l.weight.detach(), l.bias) for l in lin(seq)] for seq in model.experts]
+    gates = [(g.weight.detach(), g.bias) for g in model.gates]
+    towers = [([(l.weight.detach(), l.bias) for l in lin(seq)], (o.weight.detach().reshape(-1), o.bias))
+              for seq, o in zip(model.towers, model.tower_outputs)]
+    return experts, gates, towers
+
+
+def _mmoe_front(model, dense, names, idx):
+    """The train forward: every image the kernel reads repacked on the stream into the model's own buffers
+    (one torch.cat for the stacked layer-0 / gate weight, one for the gate biases, one
+    rk_mlp_pack_weights for all images; a hipGraph replay follows the optimizer), the dropout stream
+    advanced (rk_rng_next), then rk_mmoe_forward_train.  Returns (shape, saved buffers)."""
+    B, dev = dense.shape[0], dense.device
+    E, K = model.num_experts, len(model.task_names)
+    sh = ops.MmoeShape(model.input_dim, E, K, model.expert_hidden_units, model.tower_hidden_units, True)
+    experts, gates, towers = _mmoe_lists(model)
+    wst = ops.mmoe_stacked_weight(sh, experts, gates)
+    gate_b = torch.cat([g.bias.detach() for g in model.gates], 0)
+    own = model.__dict__.setdefault("_train_images", {})
+    if own.get("device") != dev:
+        own.clear()
+        own["device"] = dev
+    pairs, stacks, tstacks = [], [], []
+
+    def image(key, w):
+        img = own.get(key)
+        if img is None:
+            img = own[key] = ops.mlp_image(w.shape[0], w.shape[1], dev)
+        pairs.append((w, img))
+        return img
+    for e, layers in enumerate(experts):
+        stacks.append([(image(("e", e, l), w), b, w.shape[0], "relu") for l, (w, b) in enumerate(layers)])
+    for k, (hidden, _) in enumerate(towers):
+        tstacks.append([(image(("t", k, l), w), b, w.shape[0], "relu") for l, (w, b) in enumerate(hidden)])
+    gate_rows = wst[E * ops.p4(sh.eu[0]):E * ops.p4(sh.eu[0]) + K * E, :sh.width]  # the stacked gates: wst's tail
+    gate_image = image("g", gate_rows)
+    stream = ops._lib.raw_stream(dev)
+    ops.pack_mlp_weights(pairs, stream)
+    p = float(model.dropout_rate)
+    seed, slot = 0, None
+    if p > 0:
+        seed, slot = model.__dict__.setdefault("_dropout", DropoutStreams()).next(dev)
+    segs = [ops.dense_segment(dense, model.num_dense_features, 0)]
+    col = model.num_dense_features
+    for n, i in zip(names, idx):
+        emb = model.embeddings[n]
+        segs.append(ops.table_segment(emb.weight, i, col))
+        col += emb.embedding_dim
+    heads = [(w, b) for _, (w, b) in towers]
+    s = ops.mmoe_forward_train(segs, sh, B, stacks, gate_image, gate_b, tstacks, heads, dev, p, seed, slot)
+    s["weights"] = (experts, gates, towers, wst)
+    s["dropout"] = (seed, slot)
+    return sh, s
+
+
+class _MMoETrain(torch.autograd.Function):
+    """MMoE forward + backward in train mode: rk_mmoe_forward_train (one launch: gather, gates, experts with
+    dropout, mix, towers, heads, every activation kept), then ops.mmoe_backward (heads, towers, mix and
+    gates, experts, the stacked layer 0, each a fixed number of launches whatever E and K) and the
+    embedding gradients.  Inputs after the fixed arguments: the tables, then every expert Linear's
+    (weight, bias) expert-major, the gates', every tower Linear's, the output layers'."""
+
+    @staticmethod
+    def forward(ctx, model, dense, names, idx, *params):
+        sh, s = _mmoe_front(model, dense, names, idx)
+        ctx.model, ctx.sh, ctx.s, ctx.names, ctx.idx, ctx.B = model, sh, s, names, idx, dense.shape[0]
+        ctx.set_materialize_grads(False)
+        return s["probs"], s["logits"]
+
+    @staticmethod
+    def backward(ctx, dprob, dlogit):
+        model, sh, s, B = ctx.model, ctx.sh, ctx.s, ctx.B
+        dev = s["x"].device
+        experts, gates, towers, wst = s["weights"]
+        if dprob is None and dlogit is None:
+            dlogit = torch.zeros(B, sh.K, device=dev, dtype=torch.float32)
+        dx, eg, gg, tg = ops.mmoe_backward(sh, B, s, wst, experts, gates, towers, float(model.dropout_rate), None,
+                                           _grad_out(dlogit, s["logits"]), _grad_out(dprob, s["probs"]), True, dev)
+        tables = [model.embeddings[n].weight for n in ctx.names]
+        g_tab = embedding_grads(tables, ctx.idx, model.num_dense_features, dx, sparse=model.sparse_grad)
+        out = list(g_tab)
+        for e in range(sh.E):
+            for l in range(len(sh.eu)):
+                out += list(eg[e][l])
+        for k in range(sh.K):
+            out += list(gg[k])
+        for k in range(sh.K):
+            for l in range(len(sh.tu)):
+                out += list(tg[k][0][l])
+        for k in range(sh.K):
+            out += [tg[k][1][0], tg[k][1][1]]
+        return (None, None, None, None, *out)
+
+
+class _MMoEEmpty(torch.autograd.Function):
+    """MMoE's train forward over an empty batch: empty outputs attached to the parameters, whose
+    gradients are zeros (what the reference's loop gets from autograd); no kernel of the engine runs."""
+
+    @staticmethod
+    def forward(ctx, K, device, *params):
+        ctx.params = params
+        return (torch.empty(0, K, device=device, dtype=torch.float32),
+                torch.empty(0, K, device=device, dtype=torch.float32))
+
+    @staticmethod
+    def backward(ctx, dprob, dlogit):
+        return (None, None, *[torch.zeros_like(p) for p in ctx.params])
+
+
+def mmoe_train_forward(model, dense, names, idx, grad: bool = True):
+    """MMoE train-mode forward: (probabilities [B, K], logits [B, K]) attached to _MMoETrain when `grad`;
+    otherwise the same launches with nothing kept.  An empty batch returns empty outputs (attached, with
+    zero gradients, when `grad`) without running the engine."""
+    if dense.shape[0] == 0:
+        if not grad:
+            return common.empty_rows(dense.device, 2, (0, len(model.task_names)))
+        return _MMoEEmpty.apply(len(model.task_names), dense.device, *[p for p in model.parameters() if p.requires_grad])
+    if not grad:
+        _, s = _mmoe_front(model, dense, names, idx)
+        return s["probs"], s["logits"]
+    lin = model._linears
+    params = [model.embeddings[n].weight for n in names]
+    for seq in model.experts:
+        for l in lin(seq):
+            params += [l.weight, l.bias]
+    for g in model.gates:
+        params += [g.weight, g.bias]
+    for seq in model.towers:
+        for l in lin(seq):
+            params += [l.weight, l.bias]
+    for o in model.tower_outputs:
+        params += [o.weight, o.bias]
+    return _MMoETrain.apply(model, dense, names, idx, *params)
+
+
 # ---------------------------------------------------------------- DIN
 
 def din_units(model):

@@ -62,6 +62,8 @@
  *   training (loss.backward() + optimizer.step() of the train() loops, dcn.py:196-201):
  *   rk_gemm            the Linear backward GEMMs (dX = dZ W, dW = dZ^T X, db)   dcn.py:147-150
  *   rk_gemm_wgrad      dW = dZ^T X, db over long reductions (one tile owner per row slab)
+ *   rk_gemm_grouped, rk_gemm_wgrad_grouped   G same-shaped Linear backwards in one launch each
+ *   rk_mmoe_forward_train, rk_mmoe_mix_backward, rk_mmoe_head_backward   MMoE training
  *   rk_logit_head_backward  output_layer + sigmoid backward      dcn.py:177-179
  *   rk_dcn_cross_backward   cross_layer backward w.r.t. x0        dcn.py:46-49
  *   rk_relu_backward   ReLU backward (residual_unit's outer ReLU) deepcrossing.py:41
@@ -103,7 +105,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 4
+#define RK_ABI_VERSION 5
 
 #define RK_OK 0
 #define RK_ERR_INVALID 1     /* bad argument (shape, null pointer, limit) */
@@ -769,6 +771,73 @@ int rk_mmoe_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t
                     int32_t tower_depth, const float* const* head_w, const float* const* head_b, float* logits,
                     float* probs, float* mixed, float* gate_probs, void* stream);
 
+/* ---- MMoE training ("Training") ---- */
+/* rk_mlp_pack_weight of `count` weights in one launch per 96 of them (a train step repacks every
+ * image it reads on the stream, so that a hipGraph replay follows the optimizer): out = the
+ * [pad64(n), pad64(k)] image of w [n, k] (row stride ldw), 16-B aligned.                        */
+typedef struct rk_pack_item {
+  const float* w;
+  float* out;
+  int64_t ldw;
+  int32_t n;
+  int32_t k;
+} rk_pack_item;
+int rk_mlp_pack_weights(const rk_pack_item* items, int32_t count, void* stream);
+
+/* rk_mmoe_forward in train mode, still one launch: dropout (probability dropout_p in [0, 1), scale
+ * 1 / (1 - p)) behind every ReLU, and everything the backward reads kept.  Every hidden layer must be
+ * ReLU, all experts (towers) must have the same widths layer by layer.  Dropout site s = e *
+ * expert_depth + l for expert e layer l, num_experts * expert_depth + k * tower_depth + l for tower k
+ * layer l; element (b, j) of a site's [batch, n] output is kept iff the counter hash of
+ * rk_dropout_mask(seed + s, stream_slot, ...) keeps element b * n + j (stream_slot may be NULL
+ * when dropout_p == 0).  With p4(v) = v rounded up to
+ * a multiple of 4, the saved buffers (16-B aligned, columns between a width and its p4 zero) are
+ *   x_out          [batch, p4(width)]                      the gathered rows
+ *   expert_acts[l] [batch, num_experts * p4(n_l)]          expert e's layer l (after ReLU and dropout) at
+ *                                                          columns e * p4(n_l); l = expert_depth - 1 is f_e
+ *   tower_acts[l]  [batch, num_tasks * p4(n_l)]            tower k's layer l likewise
+ *   mixed          [batch, num_tasks * p4(H)]              m_k at columns k * p4(H) (not [batch, K, H])
+ *   gate_probs     [batch, num_tasks, num_experts]
+ * mixed and gate_probs are required; logits / probs as in rk_mmoe_forward.  With dropout_p == 0 the
+ * logits and probs have rk_mmoe_forward's bits.  Errors and envelope as rk_mmoe_forward.        */
+int rk_mmoe_forward_train(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                          const rk_mmoe_layer* experts, int32_t num_experts, int32_t expert_depth,
+                          const float* gate_w, const float* gate_b, int32_t num_tasks,
+                          const rk_mmoe_layer* towers, int32_t tower_depth, const float* const* head_w,
+                          const float* const* head_b, double dropout_p, uint64_t seed,
+                          const int64_t* stream_slot, float* x_out, float* const* expert_acts,
+                          float* const* tower_acts, float* logits, float* probs, float* mixed,
+                          float* gate_probs, void* stream);
+
+/* Backward of the mix and of the gates' softmax, one launch, rows independent.  Per row b, with
+ * dm_k = dmixed[b * ld_dmixed + k * pitch_dmixed ..] [H], f_e = f[b * ld_f + e * pitch_f ..] [H] (the
+ * experts' last outputs after ReLU and dropout) and g = gate_probs[b] [num_tasks, num_experts]:
+ *   dg[k][e] = sum_h dm_k[h] f_e[h]
+ *   dgate_logits[b * ld_dgl + k * num_experts + e] = g[k][e] (dg[k][e] - sum_e' g[k][e'] dg[k][e'])
+ *   dz[b * ld_dz + e * pitch_dz + h] = (sum_k g[k][e] dm_k[h]) * mask_scale * [f_e[h] > 0]   (h < H; zeros
+ *                                                                                           up to pitch_dz)
+ * Sums in a fixed order, no atomics.  With one expert the gate gradient is exactly 0.  Envelope:
+ * num_experts <= 16, num_tasks <= 8, num_tasks * num_experts <= 64, H <= 512 (RK_ERR_UNSUPPORTED); NULL, a pitch or
+ * leading dimension too small, a pointer not aligned to 4 B: RK_ERR_INVALID; both before any launch.
+ * batch == 0: RK_OK, no launch.                                                                  */
+int rk_mmoe_mix_backward(int64_t batch, int32_t num_experts, int32_t num_tasks, int32_t H, const float* dmixed,
+                         int64_t ld_dmixed, int32_t pitch_dmixed, const float* f, int64_t ld_f, int32_t pitch_f,
+                         const float* gate_probs, float mask_scale, float* dgate_logits, int64_t ld_dgl,
+                         float* dz, int64_t ld_dz, int32_t pitch_dz, void* stream);
+
+/* Backward of the num_tasks heads (Linear(n, 1) + sigmoid) into their inputs, one launch:
+ *   g[b][k] = dlogits[b][k] + dprobs[b][k] p (1 - p)        (either gradient may be NULL, not both;
+ *                                                            dlogits, dprobs, probs [batch, num_tasks])
+ *   g_out[b * ld_g + k] = g[b][k]  (zeros for num_tasks <= k < ld_g)
+ *   dt[b * num_tasks * pitch + k * pitch + j] (+)= g[b][k] head_w[k][j] (j < n; 0 up to pitch),
+ *       times mask_scale * [t[same index] > 0] when t != NULL (the towers' last outputs).
+ * The heads' dw / db are rk_gemm_wgrad(g_out, the towers' outputs): no sum over rows here.
+ * num_tasks, ld_g <= 8 (RK_ERR_UNSUPPORTED); NULL / misaligned pointers: RK_ERR_INVALID.        */
+int rk_mmoe_head_backward(int64_t batch, int32_t num_tasks, int32_t n, int32_t pitch, const float* dlogits,
+                          const float* dprobs, const float* probs, const float* const* head_w, const float* t,
+                          float mask_scale, float* g_out, int32_t ld_g, float* dt, int32_t accumulate,
+                          void* stream);
+
 /* ---- xDeepFM training: the CIN's train forward, data backward and weight gradient ---- */
 /* rk_cin_forward that also writes every layer's feature maps for the backward:
  *   maps[(b * hsum + off_k + n) * dim + d] = x^k[b, n, d],  hsum = sum layer_sizes   (16-B aligned,
@@ -905,6 +974,30 @@ int rk_gemm_wgrad(int64_t N, int64_t K, int64_t R, const float* A, int64_t lda, 
                   const float* B, int64_t ldb, float* C, int64_t ldc, float* row_sums,
                   int32_t accumulate, float* workspace, int64_t workspace_floats, void* stream);
 int64_t rk_gemm_wgrad_workspace_floats(int64_t N, int64_t K, int64_t R);
+
+/* G <= 16 GEMMs of one shape in one launch (the data gradients of G independent Linears): for every
+ * group g, C[g][m * ldc + n] (+)= sum_r opA_g(m, r) opB_g(n, r) with rk_gemm's operand layouts, then
+ * the *output* mask when C_mask != NULL: the product is multiplied by mask_scale * [C_mask[g][m *
+ * ldmask + n] > 0] before it is stored (or added), so a masked dz buffer is formed once.  A, B, C, C_mask are
+ * host arrays of G device pointers (copied into the kernel arguments); groups may be column blocks
+ * of one wider buffer (ldc > N).  The whole reduction runs in one workgroup: no split, no atomics.
+ * trans_a must be 0 (a transposed A is a weight gradient: rk_gemm_wgrad_grouped).  G > 16 or trans_a != 0:
+ * RK_ERR_UNSUPPORTED; a NULL array or entry, a pointer not aligned to 4 B, a leading
+ * dimension too small: RK_ERR_INVALID; nothing is written in either case.                       */
+int rk_gemm_grouped(int32_t G, int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t R,
+                    const float* const* A, int64_t lda, const float* const* B, int64_t ldb, float* const* C,
+                    int64_t ldc, const float* const* C_mask, int64_t ldmask, float mask_scale,
+                    int32_t accumulate, void* stream);
+
+/* rk_gemm_wgrad over G <= 16 groups of one shape in two launches (partials, fixed-order reduce):
+ * C[g][n * ldc + k] (+)= sum_r A[g][r * lda + n] B[g][r * ldb + k], row_sums[g][n] (+)= sum_r A[g][r *
+ * lda + n] (row_sums NULL: none).  Deterministic, no atomics; alignment rules and error codes as
+ * rk_gemm_wgrad, G > 16 RK_ERR_UNSUPPORTED; workspace: rk_gemm_wgrad_grouped_workspace_floats.  */
+int rk_gemm_wgrad_grouped(int32_t G, int64_t N, int64_t K, int64_t R, const float* const* A, int64_t lda,
+                          const float* const* B, int64_t ldb, float* const* C, int64_t ldc,
+                          float* const* row_sums, int32_t accumulate, float* workspace,
+                          int64_t workspace_floats, void* stream);
+int64_t rk_gemm_wgrad_grouped_workspace_floats(int32_t G, int64_t N, int64_t K, int64_t R);
 
 /* out[i] (+)= dy[i] * [y[i] > 0] over n contiguous floats (ReLU backward from its output; the
  * residual path of residual_unit, deepcrossing.py:41).                                        */

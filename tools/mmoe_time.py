@@ -16,7 +16,18 @@ are compared with each other before anything is timed.
 From the shapes the tool computes the forward's flops per sample (experts, gates, mix, towers, heads) and
 reports the kernel's rate as a share of the 157.3 TF FP32 matrix peak of the MI355X (the MFMA FP32 peak,
 not a measured ceiling).  `--batches 2048,8192` measures other batch sizes.  Needs a GPU; prints one JSON
-line at the end."""
+line at the end.
+
+`--train` times one training step instead (forward + backward of BCE-with-logits over the K label columns,
+gradients set to None first, optimizer excluded) at the same four points, two legs by the same method:
+
+  (a) engine    rankops.MMoE(trainable=True) in train mode: rk_mmoe_forward_train and the grouped backward
+  (b) torch     float32 torch autograd of the same module (torch_forward in train mode: nn.Dropout live)
+
+with the same dropout rate (a whole step captured with dien_time.grad_graph_of), and prints the launches of
+one eager step of (a), counted on the host (launches_of: one per library entry point and per torch operator
+that is not a view or an allocation, an approximation of the device's launch count) — their number must not
+depend on E."""
 import json
 import os
 import statistics
@@ -31,7 +42,7 @@ import helpers as H  # noqa: E402
 import rankops  # noqa: E402
 from rankops import common, ops  # noqa: E402
 
-from dien_time import shader_clock  # noqa: E402
+from dien_time import grad_graph_of, shader_clock  # noqa: E402
 
 FP32_MATRIX_PEAK_TF = 157.3
 ROUNDS = 7
@@ -154,6 +165,101 @@ def measure(E, B):
     return r
 
 
+# launches per library call (the rest launch once); torch operators (exact names, overload included) that only
+# make views, allocate or read metadata, so launch nothing
+TWO_LAUNCHES = {"rk_gemm_wgrad": 2, "rk_gemm_wgrad_grouped": 2}
+NO_LAUNCH = {"view.default", "_unsafe_view.default", "reshape.default", "slice.Tensor", "select.int", "detach.default",
+             "alias.default", "empty.memory_format", "empty_like.default", "empty_strided.default",
+             "as_strided.default", "expand.default", "squeeze.dim", "squeeze.default", "unsqueeze.default",
+             "transpose.int", "permute.default", "t.default", "split.Tensor", "unbind.int", "is_same_size.default",
+             "lift_fresh.default", "_sparse_coo_tensor_with_dims_and_tensors.default", "sym_size.int",
+             "sym_stride.int", "sym_numel.default"}
+
+
+class _CountingLib:
+    def __init__(self, lib, names):
+        self._lib, self._names = lib, names
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("rk_") or name.endswith("_floats") or name.endswith("_size"):
+            return fn
+
+        def call(*args):
+            self._names.extend([name] * TWO_LAUNCHES.get(name, 1))
+            return fn(*args)
+        return call
+
+
+def launches_of(step):
+    """The launches of one eager call of `step`, counted on the host: every librankops entry point called
+    (rk_gemm_wgrad and its grouped form count twice: partials and reduction) and every torch operator not
+    named in NO_LAUNCH.  A host count, not a device trace: an operator is taken as one launch whatever it
+    runs underneath, and a fill the library issues itself (the weight-gradient entries' memset for an empty
+    reduction) is not seen.  It serves to compare list lengths between configurations; the list is printed
+    so that every entry can be read.  A list of names in call order."""
+    from torch.utils._python_dispatch import TorchDispatchMode
+    names = []
+    real = ops._lib.load
+
+    class Ops(TorchDispatchMode):
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            name = str(func).replace("aten.", "")
+            if name not in NO_LAUNCH:
+                names.append("torch:" + name)
+            return func(*args, **(kwargs or {}))
+    lib = _CountingLib(real(), names)
+    ops._lib.load = lambda: lib
+    try:
+        with Ops():
+            step()
+    finally:
+        ops._lib.load = real
+    torch.cuda.synchronize()
+    return names
+
+
+def measure_train(E, B):
+    torch.manual_seed(42)
+    engine = rankops.MMoE(None, num_experts=E, vocab_sizes=H.WECHAT_VOCAB, trainable=True).cuda().train()
+    torch.manual_seed(42)
+    plain = rankops.MMoE(None, num_experts=E, vocab_sizes=H.WECHAT_VOCAB).cuda().train()
+    inp = H.to_device(H.dcn_inputs(B, H.WECHAT_VOCAB, 1000), "cuda")
+    dense, cat = inp["dense"], inp["category"]
+    K = len(engine.task_names)
+    labels = (torch.rand(B, K, generator=torch.Generator().manual_seed(3)) < 0.3).float().cuda()
+    crit = torch.nn.BCEWithLogitsLoss()
+
+    def step_of(model, forward):
+        def step():
+            with torch.enable_grad():
+                for prm in model.parameters():
+                    prm.grad = None
+                crit(forward()[1], labels).backward()
+        return step
+    fns = {"engine": step_of(engine, lambda: engine(dense, cat)),
+           "torch": step_of(plain, lambda: torch_forward(plain, dense, cat))}
+    graphs = {k: grad_graph_of(fn) for k, fn in fns.items()}
+    times = {k: [] for k in graphs}
+    for _ in range(ROUNDS):
+        for k, g in graphs.items():
+            times[k].append(replay_us(g))
+    r = {}
+    for k, t in times.items():
+        r[f"{k}_us"] = {"median": round(statistics.median(t), 2), "min": round(min(t), 2), "max": round(max(t), 2)}
+    med = {k: statistics.median(t) for k, t in times.items()}
+    r["torch_over_engine"] = round(med["torch"] / med["engine"], 2)
+    r["torch_over_engine_range"] = [round(min(times["torch"]) / max(times["engine"]), 2),
+                                    round(max(times["torch"]) / min(times["engine"]), 2)]
+    del graphs
+    names = launches_of(fns["engine"])  # after the timing: nothing of the count runs before a capture
+    r["engine_launches"] = len(names)
+    r["engine_launch_list"] = names
+    del engine, plain
+    torch.cuda.empty_cache()
+    return r
+
+
 def main():
     assert torch.cuda.is_available(), "mmoe_time needs a ROCm GPU"
     rankops.load_library()
@@ -164,7 +270,7 @@ def main():
         batches = tuple(int(b) for b in sys.argv[sys.argv.index("--batches") + 1].split(","))
     for E in (4, 8):
         for B in batches:
-            r = measure(E, B)
+            r = measure_train(E, B) if "--train" in sys.argv[1:] else measure(E, B)
             result[f"E{E}_B{B}"] = r
             print(f"E {E} B {B}: " + ", ".join(f"{k} {v}" for k, v in r.items()), flush=True)
     result["sclk_after"] = shader_clock()
