@@ -63,27 +63,42 @@ class AFM(EngineModule):
         )
         self.p = nn.Linear(embedding_dim, 1)
 
+    def _build(self, dense_input, idxs):
+        """The forward's one rk_afm_forward launch bound to `dense_input` and the index tensors `idxs`
+        (category_features order) as a common.Bound; the outputs are patched in per call.  The launch
+        reads the parameters in place."""
+        fields = [ops.table_segment(self.embeddings[col].weight, idx, 0)
+                  for col, idx in zip(self.category_features, idxs)]
+        att1, att2 = self.attention[0], self.attention[2]
+        args = ops.afm_forward_args(fields, self.embedding_dim, dense_input.shape[0], dense_input,
+                                    self.dense_layer.weight, self.dense_layer.bias, att1.weight, att1.bias,
+                                    att2.weight, att2.bias, self.p.weight, self.p.bias, None, None)
+        return common.bound([("rk_afm_forward", args)], dense_input.shape[0], idxs, self._patch)
+
+    @staticmethod
+    def _patch(_ep, args, out):
+        pred, logit = out
+        args[ops.AFM_LOGIT_SLOT], args[ops.AFM_PROB_SLOT] = logit.data_ptr(), pred.data_ptr()
+
+    @staticmethod
+    def _outputs(B, dev):
+        return common.empty_rows(dev, 2, (B, 1))
+
     def forward(self, dense_input, category_input):
         if self.training and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             check_eval(self)  # a train-mode forward without autograd is not implemented
         dense_input = ops.as_f32(dense_input, "dense_input")
-        B = dense_input.shape[0]
-        dev = dense_input.device
+        B, dev = dense_input.shape[0], dense_input.device
         if B == 0 and not self.training:
             return common.empty_rows(dev, 2)
-        fields, idxs = [], []
-        for col in self.category_features:
-            idx = ops.as_index(category_input[col], f"category_input[{col!r}]")
-            fields.append(ops.table_segment(self.embeddings[col].weight, idx, 0))
-            idxs.append(idx)
+        idxs = [ops.as_index(category_input[col], f"category_input[{col!r}]") for col in self.category_features]
         if self.training:  # AFM has no BatchNorm / Dropout: the train forward is the eval math
             return train.afm_train_forward(self, dense_input.contiguous(), idxs)
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        pred = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        att1, att2 = self.attention[0], self.attention[2]
-        ops.afm_forward(fields, self.embedding_dim, B, dense_input, self.dense_layer.weight, self.dense_layer.bias,
-                        att1.weight, att1.bias, att2.weight, att2.bias, self.p.weight, self.p.bias, logit, pred)
-        return pred, logit
+        bound = self._build(dense_input, idxs)
+        out = self._outputs(B, dev)
+        bound.patch(out)
+        common.run_launches(bound.launches, ops._lib.raw_stream(dev))
+        return out
 
     def prepare(self, dense_input, category_input):
         """An eval forward bound to these input tensors (as DCNModel.prepare: the single-kernel analogue
@@ -94,20 +109,5 @@ class AFM(EngineModule):
         if self.training:
             raise RuntimeError("AFM.prepare: eval mode only (call .eval() first)")
         dense_input = ops.as_f32(dense_input, "dense_input")
-        B, dev = dense_input.shape[0], dense_input.device
         idxs = [ops.bound_index(category_input[col], f"category_input[{col!r}]") for col in self.category_features]
-        fields = [ops.table_segment(self.embeddings[col].weight, idx, 0)
-                  for col, idx in zip(self.category_features, idxs)]
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        pred = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        att1, att2 = self.attention[0], self.attention[2]
-        args = ops.afm_forward_args(fields, self.embedding_dim, B, dense_input, self.dense_layer.weight,
-                                    self.dense_layer.bias, att1.weight, att1.bias, att2.weight, att2.bias,
-                                    self.p.weight, self.p.bias, logit, pred)
-        fn, out = ops._lib.load().rk_afm_forward, (pred, logit)
-
-        def run():
-            ops.check(fn(*args), "rk_afm_forward")
-            return out
-        run.keep = (args, fields, idxs, dense_input, category_input)
-        return run
+        return common.prepared(self, self._build(dense_input, idxs), dense_input.device, (dense_input, category_input))

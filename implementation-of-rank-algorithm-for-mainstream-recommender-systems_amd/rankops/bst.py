@@ -217,14 +217,7 @@ class BSTModel(EngineModule):
         B, T = seq_feedid.shape
         dev = dense.device
         d = self.d_model
-        # DNN input row: [dense | category embeddings | pooled transformer output]
-        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
-        col = self.num_dense_features
-        for name, emb in self.embeddings.items():
-            if name in category:
-                idx = ops.as_index(category[name], f"category[{name!r}]")
-                segs.append(ops.table_segment(emb.weight, idx, col))
-                col += emb.embedding_dim
+        segs, col, _idxs = self._segments(dense, category)  # _idxs: converted copies stay alive for the launches
         width = col + d
         nblk = len(self.transformer_blocks)
         row = None
@@ -246,19 +239,13 @@ class BSTModel(EngineModule):
                 raise IndexError(f"BSTTransformer: sequence length {T} exceeds max_len "
                                  f"{blk.position_embedding.num_embeddings}")
         blocks = self._fused_blocks(T)
-        if blocks is not None and d == 16 and common.FUSED_BST_FWD:
-            # the whole forward in one launch (rk_bst_small_forward): row gather, blocks, pooling,
-            # DNN tail and head; outside its envelope the three launches below
-            logits = torch.empty(B, 1, device=dev, dtype=torch.float32)
-            probs = torch.empty(B, 1, device=dev, dtype=torch.float32)
-            mls = [ops.make_mlp_layer(l.linear.weight, common.PACKED(l.linear.weight), **l.epilogue_kwargs())
-                   for l in self._tail]
-            head = ops.make_epilogue(head_w=self.dnn[-1].weight, head_b=self.dnn[-1].bias, head_logit=logits,
-                                     head_prob=probs)
-            if ops.bst_small_forward(segs, col, self.embeddings['feedid'].weight, seq_feedid, seq_length,
-                                     self.transformer_blocks[0].nhead, blocks, self.pooling_method != 'sum', mls,
-                                     head):
-                return probs, logits
+        bound = self._build(segs, col, seq_feedid, seq_length, blocks)
+        if bound is not None:
+            # the whole forward in one launch (rk_bst_small_forward); refused: the three launches below
+            out = self._outputs(B, dev)
+            bound.patch(out)
+            if ops.bst_small_forward(bound.launches[0][1]):
+                return out
         row = torch.empty(B, width, device=dev, dtype=torch.float32)
         ops.concat_gather(segs, B, row)
         if blocks is not None:
@@ -274,6 +261,47 @@ class BSTModel(EngineModule):
         run_tail(row, self._tail, self.dnn[-1], {}, logits, probs)
         return probs, logits
 
+    def _segments(self, dense, category, index=ops.as_index):
+        """The gather segments of the DNN input row [dense | category embeddings | pooled transformer
+        output], the pooled output's column and the index tensors (`index`: ops.as_index, or
+        ops.bound_index for a prepared run)."""
+        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
+        col, idxs = self.num_dense_features, []
+        for name, emb in self.embeddings.items():
+            if name in category:
+                idxs.append(index(category[name], f"category[{name!r}]"))
+                segs.append(ops.table_segment(emb.weight, idxs[-1], col))
+                col += emb.embedding_dim
+        return segs, col, idxs
+
+    def _small_fits(self, blocks) -> bool:
+        """rk_bst_small_forward's envelope on the host side (`blocks`: _fused_blocks'); the kernel
+        checks the rest and answers RK_ERR_UNSUPPORTED."""
+        return bool(blocks) and self.d_model == 16 and common.FUSED_BST_FWD
+
+    def _build(self, segs, col, seq_feedid, seq_length, blocks):
+        """The one-launch forward at the reference script's d_model 16 (rk_bst_small_forward: row
+        gather, blocks, pooling, DNN tail and head) as a common.Bound; None outside its envelope
+        (`blocks`: _fused_blocks').  The outputs are patched in per call (_patch)."""
+        if not self._small_fits(blocks):
+            return None
+        mls, images = common.tail_layers(self._tail)
+        head = ops.make_epilogue(head_w=self.dnn[-1].weight, head_b=self.dnn[-1].bias)
+        args = ops.bst_small_forward_args(segs, col, self.embeddings['feedid'].weight, seq_feedid, seq_length,
+                                          self.transformer_blocks[0].nhead, blocks, self.pooling_method != 'sum',
+                                          mls, head)
+        return common.bound([("rk_bst_small_forward", args)], seq_feedid.shape[0], (images, mls, blocks, segs),
+                            self._patch, head)
+
+    @staticmethod
+    def _patch(ep, _args, out):
+        probs, logits = out
+        ep.head_logit, ep.head_prob = logits.data_ptr(), probs.data_ptr()
+
+    @staticmethod
+    def _outputs(B, dev):
+        return common.empty_rows(dev, 2, (B, 1))
+
     def prepare(self, dense, category, seq_feedid, seq_length):
         """An eval forward bound to these input tensors (as DIN.prepare / DCNModel.prepare: the
         single-kernel analogue of capturing the forward in a hipGraph) at the reference script's
@@ -286,42 +314,15 @@ class BSTModel(EngineModule):
         dense = ops.as_f32(dense, "dense")
         seq_feedid = ops.bound_index(seq_feedid, "seq_feedid", contiguous=True)
         seq_length = ops.bound_index(seq_length, "seq_length")
-        B, T = seq_feedid.shape
-        dev = dense.device
-        blocks = self._fused_blocks(T) if self.transformer_blocks else None
-        if blocks is None or self.d_model != 16 or not common.FUSED_BST_FWD:
+        blocks = self._fused_blocks(seq_feedid.shape[1]) if self.transformer_blocks else None
+        if not self._small_fits(blocks):
             raise RuntimeError("BSTModel.prepare: configuration outside rk_bst_small_forward's envelope")
-        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
-        col = self.num_dense_features
-        idx_keep = []
-        for name, emb in self.embeddings.items():
-            if name in category:
-                idx = ops.bound_index(category[name], f"category[{name!r}]")
-                idx_keep.append(idx)
-                segs.append(ops.table_segment(emb.weight, idx, col))
-                col += emb.embedding_dim
-        logits = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        probs = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        packed = [common.PACKED(l.linear.weight) for l in self._tail]
-        for l in self._tail:  # the images the launch binds are never rewritten in place under it
-            common.PACKED.pin(l.linear.weight)
-        epis = [l.epilogue_kwargs() for l in self._tail]  # folded BatchNorm tensors: kept alive below
-        mls = [ops.make_mlp_layer(l.linear.weight, pk, **ek) for l, pk, ek in zip(self._tail, packed, epis)]
-        head = ops.make_epilogue(head_w=self.dnn[-1].weight, head_b=self.dnn[-1].bias, head_logit=logits,
-                                 head_prob=probs)
-        args = ops.bst_small_forward_args(segs, col, self.embeddings['feedid'].weight, seq_feedid, seq_length,
-                                          self.transformer_blocks[0].nhead, blocks, self.pooling_method != 'sum',
-                                          mls, head)
-        fn, out = ops._lib.load().rk_bst_small_forward, (probs, logits)
-        rc = fn(*args)
-        if rc == ops._lib.RK_ERR_UNSUPPORTED:
+        segs, col, _ = self._segments(dense, category, ops.bound_index)  # the caller's own tensors: kept as inputs
+        bound = self._build(segs, col, seq_feedid, seq_length, blocks)
+        common.pin_tail(self._tail)
+        run = common.prepared(self, bound, dense.device, (dense, category, seq_feedid, seq_length))
+        if not ops.bst_small_forward(bound.launches[0][1]):  # the first launch: the kernel's own envelope check
             raise RuntimeError("BSTModel.prepare: configuration outside rk_bst_small_forward's envelope")
-        ops.check(rc, "rk_bst_small_forward")
-
-        def run():
-            ops.check(fn(*args), "rk_bst_small_forward")
-            return out
-        run.keep = (args, head, mls, packed, epis, blocks, segs, idx_keep, dense, seq_feedid, seq_length, category)
         return run
 
     def blocks_kernel_launcher(self, seq_feedid, seq_length):

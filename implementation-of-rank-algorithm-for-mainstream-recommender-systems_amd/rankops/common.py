@@ -2,11 +2,12 @@
 BatchNorm folding, packed-weight caches and the fused MLP tail."""
 from __future__ import annotations
 
+import functools
 import math
 import os
 import weakref
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -248,8 +249,26 @@ def tensor_sig(t: torch.Tensor):
     return (t.data_ptr(), t.dtype, t.shape, t.stride())
 
 
+class Bound(NamedTuple):
+    """One marshalled eval forward over fixed input tensors: what forward() (through
+    EagerCalls.lookup) and prepare() (through prepared) both run."""
+    launches: list         # [(C entry point, argument list with the stream slot last)]
+    batch: int
+    patch: object          # patch(out, **per_call): writes the output pointers of `out` (and per-call H2
+    #                        weight pointers) into the argument blocks / the head epilogue; model-supplied,
+    #                        functools.partial(model._patch, head epilogue, first argument list)
+    ep: object             # the head epilogue struct where the outputs are patched into one, or None
+    keep: object           # what the argument blocks point into (never the caller's inputs); last, as in
+    #                        the entries this record replaced
+
+
+def bound(launches, batch, keep, patch, ep=None) -> Bound:
+    """A Bound whose patch is the model's _patch(ep, first launch's argument list, out, **per_call)."""
+    return Bound(launches, batch, functools.partial(patch, ep, launches[0][1]), ep, keep)
+
+
 class EagerCalls:
-    """Marshalled C-ABI calls of one model's eval forward, reused across eager forwards.
+    """Bound eval forwards of one model, reused across eager forwards.
 
     The reference's evaluate() / predict loops call the model eagerly once per batch
     (dcn.py:214-239); rebuilding every ctypes segment, layer and epilogue struct per call cost more
@@ -265,6 +284,9 @@ class EagerCalls:
         self._size = size
         self._watch = None  # (generation, [parameters and buffers])
 
+    def __len__(self):
+        return len(self._d)
+
     def watched(self, module: nn.Module):
         if self._watch is None or self._watch[0] != _GENERATION[0]:
             self._watch = (_GENERATION[0], [t for t in module.parameters()] + [t for t in module.buffers()])
@@ -275,14 +297,59 @@ class EagerCalls:
         return ((_GENERATION[0], stream) + tuple(map(tensor_sig, inputs))
                 + tuple((t.data_ptr(), t._version) for t in ws) + tuple(extra))
 
-    def get(self, key):
-        return self._d.get(key)
+    @staticmethod
+    def lookup(module: nn.Module, inputs, stream: int, build, extra=()):
+        """The module's Bound for these input tensors on this stream: the cached one, or build()'s
+        (stored unless it is None).  With EAGER_CACHE off build() runs every time and nothing is kept."""
+        if not EAGER_CACHE:
+            return build()
+        calls = module.__dict__.get("_eager")
+        if calls is None:
+            calls = module.__dict__["_eager"] = EagerCalls()
+        key = calls.key(module, inputs, stream, extra)
+        bound = calls._d.get(key)
+        if bound is None:
+            bound = build()
+            if bound is not None:
+                if len(calls._d) >= calls._size:
+                    calls._d.pop(next(iter(calls._d)))
+                calls._d[key] = bound
+        return bound
 
-    def put(self, key, entry):
-        if len(self._d) >= self._size:
-            self._d.pop(next(iter(self._d)))
-        self._d[key] = entry
-        return entry
+    @staticmethod
+    def drop(module: nn.Module, bound):
+        """Forgets a Bound whose launch the library refused."""
+        calls = module.__dict__.get("_eager")
+        if calls is not None:
+            for key in [k for k, v in calls._d.items() if v is bound]:
+                del calls._d[key]
+
+
+def prepared(module: nn.Module, bound: Bound, device, inputs, **per_call):
+    """prepare()'s `run` over a Bound: the C functions resolved, the stream bound and the outputs
+    (module._outputs) allocated once; run() issues the launches and returns those outputs.
+    run.keep holds the Bound, the outputs, the per-call weights and the caller's inputs."""
+    out = module._outputs(bound.batch, device)
+    bound.patch(out, **per_call)
+    lib, stream = ops._lib.load(), ops._lib.raw_stream(device)
+    calls = []
+    for name, args in bound.launches:
+        args[-1] = stream
+        calls.append((getattr(lib, name), tuple(args), name))
+    check = ops.check
+    if len(calls) == 1:
+        fn, args, name = calls[0]
+
+        def run():
+            check(fn(*args), name)
+            return out
+    else:
+        def run():
+            for fn, args, name in calls:
+                check(fn(*args), name)
+            return out
+    run.keep = (bound, out, per_call, inputs)
+    return run
 
 
 class FoldedBN:
@@ -481,7 +548,7 @@ def empty_rows(device, n: int, shape=(0, 1)):
     """The outputs of an eval forward over an empty batch: n empty float32 tensors of the model's
     output shape.  The reference's torch ops return empty outputs there; the engine launches no
     kernel (an empty tensor's data pointer may be null, which the C ABI rejects)."""
-    return tuple(torch.empty(shape, device=device, dtype=torch.float32) for _ in range(n))
+    return tuple([torch.empty(shape, device=device, dtype=torch.float32) for _ in range(n)])
 
 
 def tiled_layer(K: int, B: int, device, ml) -> bool:
@@ -497,21 +564,14 @@ def run_tail(x: torch.Tensor, layers, head: nn.Linear, head_kwargs: dict, logit:
     """Runs the hidden layers and the final Linear(N, 1) + sigmoid.  Normally one fused
     rk_mlp_forward launch; otherwise per-layer rk_linear with the head fused into the last
     layer's epilogue when its width fits one workgroup (N <= 256)."""
+    tail = tail_launches(x, layers, head, dict(head_kwargs, head_logit=logit, head_prob=prob))
+    if tail is not None:
+        run_launches(tail[0], ops._lib.raw_stream(x.device))
+        return
     h = x
     B = x.shape[0]
     dev = x.device
     head_w = head.weight
-    if FUSED_MLP and fused_mlp_fits(x.shape[1], [l.linear.out_features for l in layers]):
-        mls = [ops.make_mlp_layer(l.linear.weight, PACKED(l.linear.weight), **l.epilogue_kwargs()) for l in layers]
-        ep = ops.make_epilogue(head_w=head_w, head_b=head.bias, head_logit=logit, head_prob=prob, **head_kwargs)
-        # leading wide layers as 2D-tiled GEMMs (tiled_layer), the rest fused
-        i = 0
-        while i < len(mls) - 1 and tiled_layer(h.shape[1], B, dev, mls[i]):
-            y = torch.empty(B, layers[i].linear.out_features, device=dev, dtype=torch.float32)
-            ops.linear_tiled(h, mls[i], y)
-            h, i = y, i + 1
-        ops.mlp_forward(h, mls[i:], ep)
-        return
     for i, layer in enumerate(layers):
         last = i == len(layers) - 1
         lin = layer.linear
@@ -530,18 +590,36 @@ def run_tail(x: torch.Tensor, layers, head: nn.Linear, head_kwargs: dict, logit:
     ops.linear(h, head_w, None, epilogue=ep)
 
 
-def tail_launches(x: torch.Tensor, layers, head: nn.Linear, head_kwargs: dict):
-    """run_tail's fused path as a reusable launch list for EagerCalls: [(C function name, argument
-    list)] with the stream slot last (None), the head epilogue (its output pointers — head_logit,
-    head_prob, head_aux, fm1 / fm2 — are patched per call) and the objects the argument blocks
-    point into.  None when run_tail would not take the fused path."""
-    B, dev = x.shape[0], x.device
-    if not (FUSED_MLP and fused_mlp_fits(x.shape[1], [l.linear.out_features for l in layers])):
-        return None
+def tail_fits(k0: int, layers) -> bool:
+    """Whether the Layer list runs as the fused MLP (rk_mlp_forward and the kernels that embed it)."""
+    return bool(FUSED_MLP and fused_mlp_fits(k0, [l.linear.out_features for l in layers]))
+
+
+def tail_layers(layers):
+    """The rk_mlp_layer records of a Layer list, and what they point into: the packed weight images
+    (PACKED) and the folded BatchNorm / activation tensors."""
     packed = [PACKED(l.linear.weight) for l in layers]
-    mls = [ops.make_mlp_layer(l.linear.weight, pk, **l.epilogue_kwargs()) for l, pk in zip(layers, packed)]
+    kws = [l.epilogue_kwargs() for l in layers]
+    return [ops.make_mlp_layer(l.linear.weight, pk, **kw) for l, pk, kw in zip(layers, packed, kws)], (packed, kws)
+
+
+def pin_tail(layers):
+    """prepare(): the images a prepared run binds are never rewritten in place under it (PackedWeights.pin)."""
+    for l in layers:
+        PACKED.pin(l.linear.weight)
+
+
+def tail_launches(x: torch.Tensor, layers, head: nn.Linear, head_kwargs: dict):
+    """The fused tail as a launch list: [(C function name, argument list)] with the stream slot last
+    (None), the head epilogue (its output pointers — head_logit, head_prob, head_aux, fm1 / fm2 —
+    are patched per call unless head_kwargs carries them) and the objects the argument blocks point
+    into.  None when the widths are outside the fused MLP (run_tail then runs rk_linear per layer)."""
+    B, dev = x.shape[0], x.device
+    if not tail_fits(x.shape[1], layers):
+        return None
+    mls, images = tail_layers(layers)
     ep = ops.make_epilogue(head_w=head.weight, head_b=head.bias, **head_kwargs)
-    launches, keep = [], [packed, mls]
+    launches, keep = [], [images, mls]
     h, i = x, 0
     while i < len(mls) - 1 and tiled_layer(h.shape[1], B, dev, mls[i]):
         y = torch.empty(B, layers[i].linear.out_features, device=dev, dtype=torch.float32)

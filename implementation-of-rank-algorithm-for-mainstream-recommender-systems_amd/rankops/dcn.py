@@ -73,59 +73,41 @@ class DCNModel(EngineModule):
     def _load_vocabulary(self, vocab_dir, filename):
         return load_vocabulary(vocab_dir, filename)
 
-    def _eager_eval(self, dense, category):
-        """The fused eval forward through the EagerCalls cache: on a hit one ctypes call with fresh
-        output pointers (and the per-call H2 weights, if any) patched in; None when the fused
-        path does not apply."""
-        if not common.EAGER_CACHE:
-            return None
-        try:
-            idx = [category[n] for n in self.embeddings]
-        except (KeyError, TypeError):
-            return None
-        if not isinstance(dense, torch.Tensor) or dense.device.type != "cuda" or \
-                not all(isinstance(t, torch.Tensor) for t in idx):
-            return None  # lists / arrays take the normal path (as_index's descriptive errors)
-        dev = dense.device
-        stream = ops._lib.raw_stream(dev)
-        calls = self.__dict__.setdefault("_eager", common.EagerCalls())
-        key = calls.key(self, [dense] + idx, stream, (self.cross_weights.mode,))
-        hit = calls.get(key)
-        if hit is None and self._eager_build(dense, category, key, calls) is None:
-            return None
-        cw, cb = self.cross_weights.get(dev)  # per-call mode: the reference's draws, once per forward
-        args, head, B, _keep = calls.get(key)
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        head.head_logit = logit.data_ptr()
-        head.head_prob = prob.data_ptr()
-        args[4], args[5], args[-1] = cw.data_ptr(), cb.data_ptr(), stream
-        ops.check(ops._lib.load().rk_dcn_forward(*args), "rk_dcn_forward")
-        return prob, logit
-
-    def _eager_build(self, dense, category, key, calls):
-        dense = ops.as_f32(dense, "dense")
-        B, dev = dense.shape[0], dense.device
+    def _segments(self, dense, idx):
         segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
         col = self.num_dense_features
-        for name, emb in self.embeddings.items():
-            idx = category[name]
-            if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.device != dev:
-                return None  # conversions make new tensors per call: the uncached path
-            segs.append(ops.table_segment(emb.weight, ops.as_index(idx, f"category[{name!r}]"), col))
+        for emb, i in zip(self.embeddings.values(), idx):
+            segs.append(ops.table_segment(emb.weight, i, col))
             col += emb.embedding_dim
-        if not (common.FUSED_MLP and len(segs) <= 8 and self.input_dim <= 256
-                and common.fused_mlp_fits(self.input_dim, [l.linear.out_features for l in self._tail])):
+        return segs
+
+    def _build(self, dense, idx):
+        """The one-launch eval forward (rk_dcn_forward: gather + cross stack + MLP tail + head) bound to
+        `dense` and the index tensors `idx` (table order) as a common.Bound; None outside the kernel's
+        envelope, or when an index tensor is not int64 on the device (a converted copy is bound by the
+        uncached path only).  The cross weights and the outputs are patched in per call (_patch)."""
+        B, dev = dense.shape[0], dense.device
+        if not (len(idx) < 8 and self.input_dim <= 256 and common.tail_fits(self.input_dim, self._tail)) \
+                or any(not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev for t in idx):
             return None
-        packed = [common.PACKED(l.linear.weight) for l in self._tail]
-        mls = [ops.make_mlp_layer(l.linear.weight, pk, **l.epilogue_kwargs()) for l, pk in zip(self._tail, packed)]
+        segs = self._segments(dense, idx)
+        mls, images = common.tail_layers(self._tail)
         head = _HeadView(self.output_layer, self.input_dim)
         ep = ops.make_epilogue(head_w=head.weight, head_b=head.bias)
         args = ops.dcn_forward_args(segs, B, self.input_dim, None, None, self.num_cross_layer,
                                     self.output_layer.weight, mls, ep, dev)
-        # the packed images and the head view stay referenced by the entry: the argument block
-        # holds their raw pointers (cross weights and outputs are patched in per call)
-        return calls.put(key, (args, ep, B, (packed, head, segs)))
+        # the packed images and the head view stay referenced: the argument block holds their raw pointers
+        return common.bound([("rk_dcn_forward", args)], B, (images, head, segs), self._patch, ep)
+
+    @staticmethod
+    def _patch(ep, args, out, cw, cb):
+        prob, logit = out
+        ep.head_logit, ep.head_prob = logit.data_ptr(), prob.data_ptr()
+        args[ops.DCN_CROSS_W_SLOT], args[ops.DCN_CROSS_B_SLOT] = cw.data_ptr(), cb.data_ptr()
+
+    @staticmethod
+    def _outputs(B, dev):
+        return torch.empty(B, 1, device=dev, dtype=torch.float32), torch.empty(B, 1, device=dev, dtype=torch.float32)
 
     def prepare(self, dense, category):
         """An eval forward bound to these input tensors (as DIN.prepare: the single-kernel analogue of
@@ -138,72 +120,55 @@ class DCNModel(EngineModule):
         if self.cross_weights.mode != "frozen":
             raise RuntimeError("DCNModel.prepare: per-call interaction weights are redrawn every forward; "
                                "use interaction_weights='frozen'")
-        calls = common.EagerCalls(1)
-        dev = dense.device
-        stream = ops._lib.raw_stream(dev)
-        if self._eager_build(dense, category, 0, calls) is None:
+        dense = ops.as_f32(dense, "dense")
+        bound = self._build(dense, [category[n] for n in self.embeddings])
+        if bound is None:
             raise RuntimeError("DCNModel.prepare: configuration outside rk_dcn_forward's envelope")
-        args, head, B, keep = calls.get(0)
-        for l in self._tail:  # the images the plan binds are never rewritten in place under it
-            common.PACKED.pin(l.linear.weight)
-        cw, cb = self.cross_weights.get(dev)
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        head.head_logit, head.head_prob = logit.data_ptr(), prob.data_ptr()
-        args[4], args[5], args[-1] = cw.data_ptr(), cb.data_ptr(), stream
-        fn, out = ops._lib.load().rk_dcn_forward, (prob, logit)
-
-        def run():
-            ops.check(fn(*args), "rk_dcn_forward")
-            return out
-        run.keep = (keep, head, cw, cb, dense, category)
-        return run
+        common.pin_tail(self._tail)
+        cw, cb = self.cross_weights.get(dense.device)
+        return common.prepared(self, bound, dense.device, (dense, category), cw=cw, cb=cb)
 
     def forward(self, dense, category):
-        if not self.training and ops.as_f32(dense, "dense").shape[0] == 0:
-            self.cross_weights.get(dense.device)  # per-call mode draws every forward, as dcn.py:37-41 does
-            return common.empty_rows(dense.device, 2)
+        dense = ops.as_f32(dense, "dense")
+        B, dev = dense.shape[0], dense.device
+        if not self.training and B == 0:
+            self.cross_weights.get(dev)  # per-call mode draws every forward, as dcn.py:37-41 does
+            return common.empty_rows(dev, 2)
+        stream = ops._lib.raw_stream(dev)
+        bound = None
         if not self.training:
-            out = self._eager_eval(dense, category)
-            if out is not None:
-                return out
+            try:
+                idx = [category[n] for n in self.embeddings]
+            except (KeyError, TypeError):
+                idx = ()
+            # the caller's own tensors: the cached launch (lists / arrays: as_index's errors below)
+            if idx and all(isinstance(t, torch.Tensor) for t in idx):
+                bound = common.EagerCalls.lookup(self, [dense] + idx, stream, lambda: self._build(dense, idx),
+                                                 (self.cross_weights.mode,))
+        if bound is None:
+            idx = []
+            for name in self.embeddings:
+                if name not in category:
+                    raise KeyError(f"DCNModel.forward: category feature {name!r} missing")
+                idx.append(ops.as_index(category[name], f"category[{name!r}]"))
+        cw, cb = self.cross_weights.get(dev)  # per-call mode: the reference's draws, once per forward
         # no BatchNorm / Dropout: the train-mode forward computes what the eval forward does; with
         # autograd recording it also keeps the activations for the HIP backward (rankops.train)
-        dense = ops.as_f32(dense, "dense")
-        B = dense.shape[0]
-        dev = dense.device
-        idx_keep = []
-        for name in self.embeddings:
-            if name not in category:
-                raise KeyError(f"DCNModel.forward: category feature {name!r} missing")
-            idx_keep.append(ops.as_index(category[name], f"category[{name!r}]"))
-        cw, cb = self.cross_weights.get(dev)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return train.dcn_train_forward(self, dense, idx_keep, cw, cb)  # marshals its own segments
-        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
-        col = self.num_dense_features
-        for (name, emb), idx in zip(self.embeddings.items(), idx_keep):
-            segs.append(ops.table_segment(emb.weight, idx, col))
-            col += emb.embedding_dim
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        if (common.FUSED_MLP and len(segs) <= 8 and self.input_dim <= 256
-                and common.fused_mlp_fits(self.input_dim, [l.linear.out_features for l in self._tail])):
-            # one launch: gather + cross stack + MLP tail + head (rk_dcn_forward)
-            mls = [ops.make_mlp_layer(l.linear.weight, common.PACKED(l.linear.weight), **l.epilogue_kwargs())
-                   for l in self._tail]
-            head = _HeadView(self.output_layer, self.input_dim)
-            ep = ops.make_epilogue(head_w=head.weight, head_b=head.bias, head_logit=logit, head_prob=prob)
-            ops.dcn_forward(segs, B, self.input_dim, cw, cb, self.num_cross_layer, self.output_layer.weight, mls, ep,
-                            dev)
-            return prob, logit
+            return train.dcn_train_forward(self, dense, idx, cw, cb)  # marshals its own segments
+        if bound is None:
+            bound = self._build(dense, idx)
+        out = prob, logit = self._outputs(B, dev)
+        if bound is not None:
+            bound.patch(out, cw, cb)
+            common.run_launches(bound.launches, stream)
+            return out
         x0 = torch.empty(B, self.input_dim, device=dev, dtype=torch.float32)
         partial = torch.empty(B, device=dev, dtype=torch.float32)
-        head_w = self.output_layer.weight
-        ops.dcn_cross(segs, B, self.input_dim, cw, cb, self.num_cross_layer, head_w.data_ptr(), x0, partial, dev)
-        head = _HeadView(self.output_layer, self.input_dim)
-        run_tail(x0, self._tail, head, dict(head_partial=partial), logit, prob)
-        return prob, logit
+        ops.dcn_cross(self._segments(dense, idx), B, self.input_dim, cw, cb, self.num_cross_layer,
+                      self.output_layer.weight.data_ptr(), x0, partial, dev)
+        run_tail(x0, self._tail, _HeadView(self.output_layer, self.input_dim), dict(head_partial=partial), logit, prob)
+        return out
 
 
 class _HeadView:

@@ -62,13 +62,50 @@ class DeepCrossingModel(common.EngineModule):
     def _load_vocabulary(self, vocab_dir, filename):
         return load_vocabulary(vocab_dir, filename)
 
-    def _mlp_layers(self, units):
-        """rk_mlp_layer records of the residual units (packed images from common.PACKED)."""
-        layers = []
+    def _fits(self, units) -> bool:
+        """Whether the residual units run as the fused MLP (rk_mlp_forward / rk_mlp_forward_gather)."""
+        widths = [w for _ in units for w in (self.residual_internal_dim, self.input_dim)]
+        return bool(units and common.FUSED_MLP and fused_mlp_fits(self.input_dim, widths))
+
+    @staticmethod
+    def _mlp_layers(units):
+        """rk_mlp_layer records of the residual units, and their packed images (common.PACKED)."""
+        layers, packed = [], []
         for w1, b1, w2, b2 in units:
-            layers.append(ops.make_mlp_layer(w1, common.PACKED(w1), bias=b1, act="relu"))
-            layers.append(ops.make_mlp_layer(w2, common.PACKED(w2), bias=b2, act="relu", residual=1))
-        return layers
+            for w, b, residual in ((w1, b1, 0), (w2, b2, 1)):
+                packed.append(common.PACKED(w))
+                layers.append(ops.make_mlp_layer(w, packed[-1], bias=b, act="relu", residual=residual))
+        return layers, packed
+
+    def _segments(self, dense, idxs):
+        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
+        col = self.num_dense_features
+        for emb, idx in zip(self.embeddings.values(), idxs):
+            segs.append(ops.table_segment(emb.weight, idx, col))
+            col += emb.embedding_dim
+        return segs
+
+    def _build(self, dense, idxs, units):
+        """The one-launch eval forward (rk_mlp_forward_gather: row gather + every residual unit +
+        output_layer + sigmoid) bound to `dense`, the index tensors `idxs` (table order) and the
+        residual weights `units` as a common.Bound; None outside the launch's envelope.  The outputs
+        are patched in per call (_patch)."""
+        if not (self._fits(units) and len(idxs) < 16 and self.input_dim <= 256):
+            return None
+        B, dev = dense.shape[0], dense.device
+        ep = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias)
+        layers, packed = self._mlp_layers(units)
+        args = ops.mlp_forward_gather_args(self._segments(dense, idxs), self.input_dim, B, layers, ep, dev)
+        return common.bound([("rk_mlp_forward_gather", args)], B, (packed, units, idxs), self._patch, ep)
+
+    @staticmethod
+    def _patch(ep, _args, out):
+        prob, logit = out
+        ep.head_logit, ep.head_prob = logit.data_ptr(), prob.data_ptr()
+
+    @staticmethod
+    def _outputs(B, dev):
+        return common.empty_rows(dev, 2, (B, 1))
 
     def prepare(self, dense, category):
         """An eval forward bound to these input tensors (as DCNModel.prepare): returns `run()` that
@@ -84,39 +121,15 @@ class DeepCrossingModel(common.EngineModule):
             raise RuntimeError("DeepCrossingModel.prepare: per-call residual weights are redrawn every forward; "
                                "use interaction_weights='frozen'")
         dense = ops.as_f32(dense, "dense")
-        B, dev = dense.shape[0], dense.device
-        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
-        col, idxs = self.num_dense_features, []
-        for name, emb in self.embeddings.items():
-            idx = ops.bound_index(category[name], f"category[{name!r}]")
-            idxs.append(idx)
-            segs.append(ops.table_segment(emb.weight, idx, col))
-            col += emb.embedding_dim
-        units = self.residual_weights.get(dev)
-        widths = [w for _ in units for w in (self.residual_internal_dim, self.input_dim)]
-        if not (units and common.FUSED_MLP and fused_mlp_fits(self.input_dim, widths) and len(segs) <= 16
-                and self.input_dim <= 256):
+        idxs = [ops.bound_index(category[name], f"category[{name!r}]") for name in self.embeddings]
+        units = self.residual_weights.get(dense.device)
+        bound = self._build(dense, idxs, units)
+        if bound is None:
             raise RuntimeError("DeepCrossingModel.prepare: configuration outside rk_mlp_forward_gather's envelope")
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        head = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias, head_logit=logit,
-                                 head_prob=prob)
         for w1, _, w2, _ in units:  # the images the launch binds are never rewritten in place under it
             common.PACKED.pin(w1)
             common.PACKED.pin(w2)
-        packed = [common.PACKED(w) for w1, _, w2, _ in units for w in (w1, w2)]
-        layers = self._mlp_layers(units)
-        ops._lib.ensure_device(dev)
-        larr = (ops._lib.MlpLayer * len(layers))(*layers)
-        args = (ops._seg_array(segs), len(segs), self.input_dim, B, larr, len(layers), ops.ctypes.byref(head),
-                ops._lib.stream_of(prob))
-        fn, out = ops._lib.load().rk_mlp_forward_gather, (prob, logit)
-
-        def run():
-            ops.check(fn(*args), "rk_mlp_forward_gather")
-            return out
-        run.keep = (args, head, packed, units, segs, idxs, dense, category)
-        return run
+        return common.prepared(self, bound, dense.device, (dense, category))
 
     def forward(self, dense, category):
         # no BatchNorm / Dropout: train mode computes the eval forward; with autograd recording it
@@ -128,44 +141,29 @@ class DeepCrossingModel(common.EngineModule):
         if B == 0 and not recording:
             self.residual_weights.get(dev)  # per-call mode draws every forward (deepcrossing.py:25-42)
             return common.empty_rows(dev, 2)
-        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
-        col = self.num_dense_features
-        for name, emb in self.embeddings.items():
+        idxs = []
+        for name in self.embeddings:
             if name not in category:
                 raise KeyError(f"DeepCrossingModel.forward: category feature {name!r} missing")
-            idx = ops.as_index(category[name], f"category[{name!r}]")
-            segs.append(ops.table_segment(emb.weight, idx, col))
-            col += emb.embedding_dim
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            idx = [ops.as_index(category[name], f"category[{name!r}]") for name in self.embeddings]
-            return train.deepcrossing_train_forward(self, dense, idx, self.residual_weights.get(dev))
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
+            idxs.append(ops.as_index(category[name], f"category[{name!r}]"))
+        units = self.residual_weights.get(dev)
+        if recording:
+            return train.deepcrossing_train_forward(self, dense, idxs, units)
+        out = prob, logit = self._outputs(B, dev)
+        bound = self._build(dense, idxs, units) if common.FUSED_GATHER_MLP else None
+        if bound is not None:
+            bound.patch(out)
+            common.run_launches(bound.launches, ops._lib.raw_stream(dev))
+            return out
         head = dict(head_w=self.output_layer.weight, head_b=self.output_layer.bias, head_logit=logit,
                     head_prob=prob)
-        units = self.residual_weights.get(dev)
         I = self.residual_internal_dim
-        widths = [w for _ in units for w in (I, self.input_dim)]
-        fused = units and common.FUSED_MLP and fused_mlp_fits(self.input_dim, widths)
-        if fused and common.FUSED_GATHER_MLP and len(segs) <= 16 and self.input_dim <= 256:
-            # the row gather, every residual unit, output_layer and sigmoid in one launch
-            layers = self._mlp_layers(units)
-            ops._lib.ensure_device(dev)
-            ops.check(ops._lib.load().rk_mlp_forward_gather(ops._seg_array(segs), len(segs), self.input_dim, B,
-                                                            (ops._lib.MlpLayer * len(layers))(*layers), len(layers),
-                                                            ops.ctypes.byref(ops.make_epilogue(**head)),
-                                                            ops._lib.stream_of(prob)), "rk_mlp_forward_gather")
-            return prob, logit
         x = torch.empty(B, self.input_dim, device=dev, dtype=torch.float32)
-        ops.concat_gather(segs, B, x)
-        if fused:
+        ops.concat_gather(self._segments(dense, idxs), B, x)
+        if self._fits(units):
             # all residual units + output_layer + sigmoid in one launch
-            layers = []
-            for w1, b1, w2, b2 in units:
-                layers.append(ops.make_mlp_layer(w1, common.PACKED(w1), bias=b1, act="relu"))
-                layers.append(ops.make_mlp_layer(w2, common.PACKED(w2), bias=b2, act="relu", residual=1))
-            ops.mlp_forward(x, layers, ops.make_epilogue(**head))
-            return prob, logit
+            ops.mlp_forward(x, self._mlp_layers(units)[0], ops.make_epilogue(**head))
+            return out
         for i, (w1, b1, w2, b2) in enumerate(units):
             last = i == len(units) - 1
             h = torch.empty(B, I, device=dev, dtype=torch.float32)
@@ -181,4 +179,4 @@ class DeepCrossingModel(common.EngineModule):
             ep = ops.make_epilogue(bias=self.output_layer.bias, head_w=const(dev, 1.0), head_b=const(dev, 0.0),
                                    head_logit=logit, head_prob=prob)
             ops.linear(x, self.output_layer.weight, None, epilogue=ep)
-        return prob, logit
+        return out

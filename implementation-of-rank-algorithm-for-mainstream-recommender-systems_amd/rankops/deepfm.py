@@ -23,6 +23,8 @@ gather, the FM sums, the three deep layers on one weight stream and the head per
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 import torch.nn as nn
 
@@ -140,111 +142,67 @@ class DeepFM(EngineModule):
         plan = self._gather_plan(names, category, packed=packed)
         return lambda: self._launch(plan)
 
-    def _eager_eval(self, category):
-        """The eval forward through the EagerCalls cache (common.EagerCalls): the marshalled
-        launches (rk_fm_linear_packed + rk_mlp_forward, or rk_fm_gather_packed + the tail) reused
-        with fresh outputs patched in; rebuilt per call with EAGER_CACHE off.  None off that path."""
-        try:
-            idx = [category[n] for n in self.second_order_embeddings]
-        except (KeyError, TypeError):
-            return None
-        if not all(isinstance(t, torch.Tensor) and t.dtype == torch.int64 for t in idx) or idx[0].device.type != "cuda":
-            return None
-        dev = idx[0].device
-        stream = ops._lib.raw_stream(dev)
-        if common.EAGER_CACHE:
-            calls = self.__dict__.setdefault("_eager", common.EagerCalls())
-            key = calls.key(self, idx, stream)
-            hit = calls.get(key)
-            if hit is None:
-                hit = self._eager_build(category)
-                if hit is None:
-                    return None
-                calls.put(key, hit)
-        else:
-            hit = self._eager_build(category)
-            if hit is None:
-                return None
-        launches, fm_slots, ep, B, _keep = hit
-        fm1 = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        fm2 = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        deep = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        total = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        front = launches[0][1]
-        front[fm_slots[0]], front[fm_slots[1]] = fm1.data_ptr(), fm2.data_ptr()
-        ep.fm1, ep.fm2, ep.head_aux = fm1.data_ptr(), fm2.data_ptr(), deep.data_ptr()
-        ep.head_logit, ep.head_prob = total.data_ptr(), prob.data_ptr()
-        common.run_launches(launches, stream)
-        return prob, total, fm1, fm2, deep
-
-    def _eager_build(self, category):
-        """(launches, fm1/fm2 argument slots of launches[0], head epilogue, B, keep-alive objects)."""
+    def _build(self, category):
+        """The eval forward over the caller's own int64 index tensors as a common.Bound, in one of three
+        flavours: one rk_deepfm_forward launch (FUSED_WHOLE, where a plan is compiled for the shape),
+        rk_fm_linear_packed + the rest of the tail (FUSED_FRONT, where deep layer 0 is tiled), or
+        rk_fm_gather_packed + the tail.  None off that path: unpacked tables, contiguous copies of
+        the indices, or deep layers outside the fused MLP.  The five outputs are patched in per call."""
         names = list(self.second_order_embeddings)
         first = category[names[0]]
-        B, dev, D = first.shape[0], first.device, self.embedding_dim
+        B, dev, k0 = first.shape[0], first.device, len(names) * self.embedding_dim
         head_kwargs = dict(final_w=self.final_layer.weight, final_b=self.final_layer.bias)
-        widths = [l.linear.out_features for l in self._tail]
-        if (FUSED_WHOLE and PACKED_TABLES and first.dim() == 1 and len(names) <= 32
-                and ops.deepfm_whole_plan(len(names) * D, widths)):
-            whole = self._whole_build(names, category, head_kwargs)
-            if whole is not None:
-                return whole
-        l0, fused = self._tail[0], None
-        if FUSED_FRONT and len(self._tail) >= 2 and len(names) <= 32 and first.dim() == 1:
-            w0 = common.PACKED(l0.linear.weight)
-            ml0 = ops.make_mlp_layer(l0.linear.weight, w0, **l0.epilogue_kwargs())
-            fused = common.tiled_layer(len(names) * D, B, dev, ml0)
-        plan = self._gather_plan(names, category, deep=not fused)
-        packed, second, first, D, B, deep_in, fm1, fm2 = plan
-        if not packed or any(t.data_ptr() != category[n].data_ptr() for t, n in zip(first, names)):
+        flat = first.dim() == 1 and len(names) <= 32
+        whole = bool(FUSED_WHOLE and PACKED_TABLES and flat
+                     and ops.deepfm_whole_plan(k0, [l.linear.out_features for l in self._tail]))
+        front = False
+        if not whole and FUSED_FRONT and len(self._tail) >= 2 and flat:
+            ml0, images0 = common.tail_layers(self._tail[:1])
+            front = common.tiled_layer(k0, B, dev, ml0[0])
+        packed, second, idx, D, B, deep_in, _, _ = self._gather_plan(names, category, deep=not (whole or front))
+        if not packed or any(t.data_ptr() != category[n].data_ptr() for t, n in zip(idx, names)):
             return None  # unpacked tables, or contiguous copies of the indices: the uncached path
         ops._lib.ensure_device(dev)
         arr = ops._seg_array(second)
-        if fused:  # rk_fm_linear_packed (gather, fm1, fm2, deep layer 0) + the rest of the tail
-            y = torch.empty(B, l0.linear.out_features, device=dev, dtype=torch.float32)
-            tail = common.tail_launches(y, self._tail[1:], self.deep_output_layer, head_kwargs)
+        if whole:  # rk_deepfm_forward: gather, FM, deep layers and head in one
+            mls, images = common.tail_layers(self._tail)
+            la = (ops._lib.MlpLayer * len(mls))(*mls)
+            ep = ops.make_epilogue(head_w=self.deep_output_layer.weight, head_b=self.deep_output_layer.bias,
+                                   **head_kwargs)
+            launches = [("rk_deepfm_forward", [arr, len(second), D, B, la, len(mls), ops.ctypes.byref(ep), None, None,
+                                               None])]
+            keep = (images, mls, la)
+        else:
+            if front:  # rk_fm_linear_packed (gather, fm1, fm2, deep layer 0) + the rest of the tail
+                x = torch.empty(B, self._tail[0].linear.out_features, device=dev, dtype=torch.float32)
+                first_launch = ("rk_fm_linear_packed", [arr, len(second), D, B, ops.ctypes.byref(ml0[0]), x.data_ptr(),
+                                                        x.stride(0), None, None, None])
+                rest, keep = self._tail[1:], (images0, ml0, x)
+            else:
+                x = deep_in
+                first_launch = ("rk_fm_gather_packed", [arr, len(second), D, B, x.data_ptr(), x.stride(0), None, None,
+                                                        None])
+                rest, keep = self._tail, x
+            tail = common.tail_launches(x, rest, self.deep_output_layer, head_kwargs)
             if tail is None:
                 return None
-            tl, ep, keep = tail
-            front = ["rk_fm_linear_packed", [arr, len(second), D, B, ops.ctypes.byref(ml0), y.data_ptr(), y.stride(0),
-                                             None, None, None]]
-            # keep-alive: what the argument blocks point into (not the caller's index tensors: the
-            # cache key's address / shape / stride check makes those pointers valid on a hit)
-            return [front] + tl, (7, 8), ep, B, (keep, arr, self._images(names), w0, ml0, y)
-        tail = common.tail_launches(deep_in, self._tail, self.deep_output_layer, head_kwargs)
-        if tail is None:
-            return None
-        tl, ep, keep = tail
-        gather = ["rk_fm_gather_packed", [arr, len(second), D, B, deep_in.data_ptr(), deep_in.stride(0), None, None,
-                                          None]]
-        return [gather] + tl, (6, 7), ep, B, (keep, arr, self._images(names), deep_in)
+            launches, ep, keep = [first_launch] + tail[0], tail[1], (keep, tail[2])
+        # keep-alive: what the argument blocks point into, the packed FM tables among them (a cache
+        # rebuild replaces those), but not the caller's index tensors: the cache key's address / shape /
+        # stride check makes those pointers valid on a hit
+        return common.bound(launches, B, (keep, arr, [self.packed_table(n) for n in names]),
+                            functools.partial(self._patch, ops.FM_OUT_SLOTS[launches[0][0]]), ep)
 
-    def _images(self, names):
-        """The device tensors a marshalled launch points into beyond its arguments: the packed FM
-        tables and the folded BatchNorm affines.  A cache rebuild (a later .eval()/.train() or a
-        weight change) replaces them, so a prepared run() must keep its own references."""
-        return ([self.packed_table(n) for n in names],
-                [l.epilogue_kwargs() for l in self._tail])
+    @staticmethod
+    def _patch(slots, ep, args, out):
+        prob, total, fm1, fm2, deep = out
+        args[slots[0]], args[slots[1]] = fm1.data_ptr(), fm2.data_ptr()
+        ep.fm1, ep.fm2, ep.head_aux = fm1.data_ptr(), fm2.data_ptr(), deep.data_ptr()
+        ep.head_logit, ep.head_prob = total.data_ptr(), prob.data_ptr()
 
-    def _whole_build(self, names, category, head_kwargs):
-        """rk_deepfm_forward's launch (gather, FM, deep layers, head in one): the _eager_build tuple,
-        or None off its path."""
-        plan = self._gather_plan(names, category, deep=False)
-        packed, second, first, D, B, _, fm1, fm2 = plan
-        if not packed or any(t.data_ptr() != category[n].data_ptr() for t, n in zip(first, names)):
-            return None
-        dev = fm1.device
-        ops._lib.ensure_device(dev)
-        arr = ops._seg_array(second)
-        weights = [common.PACKED(l.linear.weight) for l in self._tail]
-        kws = [l.epilogue_kwargs() for l in self._tail]
-        mls = [ops.make_mlp_layer(l.linear.weight, w, **kw) for l, w, kw in zip(self._tail, weights, kws)]
-        la = (ops._lib.MlpLayer * len(mls))(*mls)
-        ep = ops.make_epilogue(head_w=self.deep_output_layer.weight, head_b=self.deep_output_layer.bias,
-                               **head_kwargs)
-        launch = ["rk_deepfm_forward", [arr, len(second), D, B, la, len(mls), ops.ctypes.byref(ep), None, None, None]]
-        return [launch], (7, 8), ep, B, (arr, self._images(names), weights, kws, mls, la)
+    @staticmethod
+    def _outputs(B, dev):
+        return common.empty_rows(dev, 5, (B, 1))
 
     def prepare(self, category):
         """An eval forward bound to these input tensors (as DIN.prepare: the single-kernel analogue of
@@ -254,41 +212,32 @@ class DeepFM(EngineModule):
         Binds the current weights: prepare again after changing them."""
         if self.training:
             raise RuntimeError("DeepFM.prepare: eval mode only (call .eval() first)")
-        hit = self._eager_build(category)
-        if hit is None:
+        bound = self._build(category)
+        if bound is None:
             raise RuntimeError("DeepFM.prepare: configuration outside the cached eval path")
-        launches, fm_slots, ep, B, keep = hit
-        for l in self._tail:  # the images the plan binds are never rewritten in place under it
-            common.PACKED.pin(l.linear.weight)
-        dev = category[next(iter(self.second_order_embeddings))].device
-        out = tuple(torch.empty(B, 1, device=dev, dtype=torch.float32) for _ in range(5))
-        prob, total, fm1, fm2, deep = out
-        front = launches[0][1]
-        front[fm_slots[0]], front[fm_slots[1]] = fm1.data_ptr(), fm2.data_ptr()
-        ep.fm1, ep.fm2, ep.head_aux = fm1.data_ptr(), fm2.data_ptr(), deep.data_ptr()
-        ep.head_logit, ep.head_prob = total.data_ptr(), prob.data_ptr()
-        stream = ops._lib.raw_stream(dev)
-        lib = ops._lib.load()
-        calls = []
-        for name, args in launches:
-            args[-1] = stream
-            calls.append((name, getattr(lib, name), args))
-
-        def run():
-            for name, fn, args in calls:
-                ops.check(fn(*args), name)
-            return out
-        run.keep = (keep, ep, category)
-        return run
+        common.pin_tail(self._tail)
+        return common.prepared(self, bound, category[next(iter(self.second_order_embeddings))].device, category)
 
     def forward(self, category):
         first = category.get(next(iter(self.second_order_embeddings)), None) if isinstance(category, dict) else None
         if not self.training and isinstance(first, torch.Tensor) and first.shape[0] == 0:
             return common.empty_rows(ops.require_gpu(first, "category").device, 5)
         if not self.training:
-            out = self._eager_eval(category)
-            if out is not None:
-                return out
+            try:
+                idx = [category[n] for n in self.second_order_embeddings]
+            except (KeyError, TypeError):
+                idx = ()
+            # the caller's own int64 tensors: the cached launches (anything else: as_index's errors below)
+            if idx and all(isinstance(t, torch.Tensor) and t.dtype == torch.int64 for t in idx) \
+                    and idx[0].device.type == "cuda":
+                dev = idx[0].device
+                stream = ops._lib.raw_stream(dev)
+                bound = common.EagerCalls.lookup(self, idx, stream, lambda: self._build(category))
+                if bound is not None:
+                    out = self._outputs(bound.batch, dev)
+                    bound.patch(out)
+                    common.run_launches(bound.launches, stream)
+                    return out
         if self.training and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             check_eval(self)  # a train-mode forward without autograd is not implemented
         names = [c for c in self.second_order_embeddings if c in category]
@@ -300,9 +249,7 @@ class DeepFM(EngineModule):
             return train.deepfm_train_forward(self, names, idx)
         deep_in, fm1, fm2 = self._gather_fm(names, category)
         B, dev = deep_in.shape[0], deep_in.device
-        deep = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        total = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        prob, total, deep = common.empty_rows(dev, 3, (B, 1))
         head_kwargs = dict(fm1=fm1, fm2=fm2, final_w=self.final_layer.weight, final_b=self.final_layer.bias,
                            head_aux=deep)
         run_tail(deep_in, self._tail, self.deep_output_layer, head_kwargs, total, prob)

@@ -17,11 +17,13 @@ The attention MLP is drawn per call like the reference (din.py:61-67) or frozen.
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 import torch.nn as nn
 
 from . import common, ops, train
-from .common import PACKED, fused_mlp_fits
+from .common import fused_mlp_fits
 from .common import EngineModule, InteractionWeights, Layer, check_eval, din_attention_spec, draw_din_attention, \
     load_vocabulary, run_tail, \
     table_rows
@@ -231,16 +233,50 @@ class DIN(EngineModule):
             self._att_img = (k, ops.din_pack_attention(w, H))
         return self._att_img[1]
 
-    def _launch_fused(self, pl, w, logit, prob, l2_reg):
-        layers = [ops.make_mlp_layer(l.linear.weight, PACKED(l.linear.weight), **l.epilogue_kwargs())
-                  for l in self._tail]
-        img = self._att_image(w, pl["H"])
-        head = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias,
-                                 head_logit=logit, head_prob=prob)
-        ops.din_forward(pl["segs"], pl["width"], pl["q_col"], pl["att_col"], self.embeddings[SEQ_KEY].weight,
-                        pl["seq"], pl["seq_len"], pl["H"], w, self.use_softmax, layers, head, pl["B"], pl["dev"],
-                        l2_col0=pl["cat_col0"], l2_scale=float(self.l2_lambda),
-                        l2_out=l2_reg if isinstance(l2_reg, torch.Tensor) else None, att_image=img)
+    def _build(self, pl, entry="rk_din_forward", want_l2=None):
+        """The one-launch forward (row gather, attention, fcn tail, head, l2 partials) over _plan's
+        layout as a common.Bound; None outside the kernel's envelope.  `entry`: rk_din_forward (the
+        stream after the arguments), rk_din_forward_ex (the cached eager entry: phase B's epilogue
+        image, packed once per entry as a prepared plan does, then the stream) or rk_din_forward_plan
+        (an l2 workspace of its own, nothing after the arguments: ops.din_forward_plan).  The H2
+        weights, their image and the outputs are patched in per call (_patch)."""
+        if not pl["fused"]:
+            return None
+        B, dev = pl["B"], pl["dev"]
+        layers, images = common.tail_layers(self._tail)
+        head = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias)
+        args, keep = ops._din_forward_args(pl["segs"], pl["width"], pl["q_col"], pl["att_col"],
+                                           self.embeddings[SEQ_KEY].weight, pl["seq"], pl["seq_len"], pl["H"],
+                                           self.use_softmax, layers, head, B, dev, pl["cat_col0"], float(self.l2_lambda),
+                                           pl["want_l2"] if want_l2 is None else want_l2,
+                                           private_ws=entry == "rk_din_forward_plan")
+        epi = None
+        if entry == "rk_din_forward_ex":
+            epi = ops.pack_epilogue_image(args[ops.DIN_LAYERS_SLOT], args[ops.DIN_NUM_LAYERS_SLOT],
+                                          args[ops.DIN_WIDTH_SLOT], dev)
+            args.append(ops.ptr(epi))
+        if entry != "rk_din_forward_plan":
+            args.append(None)  # the stream
+        # keeps what the argument block points into (segment / layer arrays, packed images, the l2
+        # workspace, the epilogue image last) but not the caller's input tensors: the cache key's
+        # address, shape and stride check already makes the raw input pointers valid on a hit
+        return common.bound([(entry, args)], B, (keep, images, layers, epi),
+                            functools.partial(self._patch, pl["H"]), head)
+
+    def _patch(self, H, ep, args, out, w):
+        """Returns the attention image it bound: the caller keeps it alive across the launches."""
+        prob, logit, l2_reg = out
+        ep.head_logit, ep.head_prob = logit.data_ptr(), prob.data_ptr()
+        args[ops.DIN_H2_SLOTS] = [t.data_ptr() for t in w]
+        args[ops.DIN_L2_OUT_SLOT] = l2_reg.data_ptr() if isinstance(l2_reg, torch.Tensor) else None
+        img = self._att_image(w, H)
+        args[ops.DIN_ATT_IMAGE_SLOT] = img.data_ptr() if img is not None else None
+        return img
+
+    def _outputs(self, B, dev):
+        want_l2 = self.mini_batch_aware_regularization and self.l2_lambda > 0
+        return (torch.empty(B, 1, device=dev, dtype=torch.float32), torch.empty(B, 1, device=dev, dtype=torch.float32),
+                torch.empty((), device=dev, dtype=torch.float32) if want_l2 else 0.0)
 
     def prepare(self, dense, category, sequence, target):
         """An eval forward bound to these input tensors (the single-kernel analogue of capturing
@@ -253,27 +289,16 @@ class DIN(EngineModule):
         pl = self._plan(dense, category, sequence, target)
         if not pl["fused"]:
             raise RuntimeError("DIN.prepare: configuration outside rk_din_forward's envelope")
-        B, dev = pl["B"], pl["dev"]
+        dev = pl["dev"]
         w = self.att_weights.get(dev)
         if self.att_weights.mode != "frozen":
             raise RuntimeError("DIN.prepare: per-call interaction weights are redrawn every forward; "
                                "use interaction_weights='frozen'")
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        want_l2 = pl["want_l2"]
-        l2_reg = torch.empty((), device=dev, dtype=torch.float32) if want_l2 else None
-        packed = [PACKED.pin(l.linear.weight) for l in self._tail]  # never rewritten under the plan
-        layers = [ops.make_mlp_layer(l.linear.weight, pk, **l.epilogue_kwargs()) for l, pk in zip(self._tail, packed)]
-        head = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias,
-                                 head_logit=logit, head_prob=prob)
-        img = self._att_image(w, pl["H"])
-        keep = (pl, w, img, packed, [l.epilogue_kwargs() for l in self._tail], logit, prob, l2_reg,
-                self.embeddings[SEQ_KEY].weight)
-        plan = ops.din_forward_plan(pl["segs"], pl["width"], pl["q_col"], pl["att_col"],
-                                    self.embeddings[SEQ_KEY].weight, pl["seq"], pl["seq_len"], pl["H"], w,
-                                    self.use_softmax, layers, head, B, dev, l2_col0=pl["cat_col0"],
-                                    l2_scale=float(self.l2_lambda), l2_out=l2_reg, att_image=img, keep=keep)
-        out = (prob, logit, l2_reg if want_l2 else 0.0)
+        bound = self._build(pl, "rk_din_forward_plan")
+        common.pin_tail(self._tail)  # never rewritten under the plan
+        out = self._outputs(bound.batch, dev)
+        keep = (bound, out, pl, w, bound.patch(out, w), self.embeddings[SEQ_KEY].weight)
+        plan = ops.din_forward_plan(bound.launches[0][1], keep, dev)
 
         def run():
             plan.launch()
@@ -285,51 +310,19 @@ class DIN(EngineModule):
         """Zero-argument re-launch of this forward's rk_din_forward kernel (no l2 finish), for
         kernel-level timing (bench.py roofline)."""
         pl = self._plan(dense, category, sequence, target)
-        if not pl["fused"]:
+        bound = self._build(pl, want_l2=False)
+        if bound is None:
             raise RuntimeError("DIN configuration outside rk_din_forward's envelope")
-        w = self.att_weights.get(pl["dev"])
-        logit = torch.empty(pl["B"], 1, device=pl["dev"])
-        prob = torch.empty_like(logit)
-        return lambda: self._launch_fused(pl, w, logit, prob, None)
+        dev = pl["dev"]
+        w = self.att_weights.get(dev)
+        logit = torch.empty(pl["B"], 1, device=dev)
+        out = (torch.empty_like(logit), logit, None)
+        name, args = bound.launches[0]
 
-    def _eager_eval(self, dense, category, sequence, target):
-        """The fused eval forward through the EagerCalls cache (see common.EagerCalls): on a hit
-        one rk_din_forward call with fresh outputs (and the per-call H2 weights) patched in; None
-        when the fused path does not apply."""
-        if not common.EAGER_CACHE:
-            return None
-        try:
-            dense_cols = list(dense.values())
-            cats = [category[n] for n in self.embeddings if n in category]
-            ins = dense_cols + cats + [target["feedid"], sequence[SEQ_KEY], sequence[f"{SEQ_KEY}_length"]]
-        except (KeyError, TypeError, AttributeError):
-            return None
-        if not all(isinstance(t, torch.Tensor) for t in ins) or ins[0].device.type != "cuda":
-            return None
-        dev = ins[0].device
-        stream = ops._lib.raw_stream(dev)
-        calls = self.__dict__.setdefault("_eager", common.EagerCalls())
-        key = calls.key(self, ins, stream, (self.att_weights.mode, tuple(dense), tuple(category)))
-        if calls.get(key) is None and self._eager_build(dense, category, sequence, target, key, calls) is None:
-            return None
-        w = self.att_weights.get(dev)  # per-call mode: the reference's draws, once per forward
-        args, head, B, want_l2, H, _keep = calls.get(key)
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        l2_reg = torch.empty((), device=dev, dtype=torch.float32) if want_l2 else 0.0
-        head.head_logit = logit.data_ptr()
-        head.head_prob = prob.data_ptr()
-        img = self._att_image(w, H)
-        args[14:20] = [t.data_ptr() for t in w]
-        args[27] = l2_reg.data_ptr() if want_l2 else None
-        args[28] = img.data_ptr()
-        rc = ops._lib.load().rk_din_forward_ex(*args, stream)
-        if rc == ops._lib.RK_ERR_UNSUPPORTED:  # e.g. past the kernel's LDS budget: the unfused path
-            self._mark_unfusable(sequence[SEQ_KEY].shape[1], H)
-            calls._d.pop(key, None)
-            return None
-        ops.check(rc, "rk_din_forward")
-        return prob, logit, l2_reg
+        def launch(keep=(bound, pl, w, out, bound.patch(out, w))):  # the outputs and the attention image stay alive
+            args[-1] = ops._lib.raw_stream(dev)
+            ops.din_forward(name, args)
+        return launch
 
     def _mark_unfusable(self, T, H):
         """rk_din_forward refused this shape (RK_ERR_UNSUPPORTED, e.g. its LDS carve past 160 KiB with
@@ -339,30 +332,27 @@ class DIN(EngineModule):
             width = l.linear.in_features
         self.__dict__.setdefault("_unfusable", set()).add((width, T, H))
 
-    def _eager_build(self, dense, category, sequence, target, key, calls):
-        if not all(t.dtype == torch.int64 for t in list(category.values()) + [target["feedid"]] + list(sequence.values())):
-            return None  # conversions make new tensors per call: the uncached path
-        pl = self._plan(dense, category, sequence, target)
-        if not pl["fused"] or pl["seq"].data_ptr() != sequence[SEQ_KEY].data_ptr():
+    def _own_inputs(self, dense, category, sequence, target):
+        """The input tensors a cached launch binds by address (the cache key's), or None for
+        anything but GPU tensors (as_index's errors on the uncached path)."""
+        try:
+            ins = list(dense.values()) + [category[n] for n in self.embeddings if n in category] + \
+                [target["feedid"], sequence[SEQ_KEY], sequence[f"{SEQ_KEY}_length"]]
+        except (KeyError, TypeError, AttributeError):
             return None
-        B, dev, H = pl["B"], pl["dev"], pl["H"]
-        want_l2 = pl["want_l2"]
-        packed = [PACKED(l.linear.weight) for l in self._tail]
-        layers = [ops.make_mlp_layer(l.linear.weight, pk, **l.epilogue_kwargs()) for l, pk in zip(self._tail, packed)]
-        head = ops.make_epilogue(head_w=self.output_layer.weight, head_b=self.output_layer.bias)
-        zero = [torch.zeros(1, device=dev)] * 6  # placeholder H2 pointers, patched per call
-        args, keep = ops._din_forward_args(pl["segs"], pl["width"], pl["q_col"], pl["att_col"],
-                                           self.embeddings[SEQ_KEY].weight, pl["seq"], pl["seq_len"], H, zero,
-                                           self.use_softmax, layers, head, B, dev, l2_col0=pl["cat_col0"],
-                                           l2_scale=float(self.l2_lambda), l2_out=zero[0] if want_l2 else None,
-                                           att_image=zero[0])
-        # phase B's epilogue image packed once per entry (the key covers every parameter's
-        # version) and copied into LDS by the kernel (rk_din_forward_ex), as a prepared plan does
-        epi = ops.pack_epilogue_image(args[21], args[22], args[2], dev)
-        # the entry keeps what its argument block points into (segment / layer arrays, packed
-        # images, the l2 workspace) but not the caller's input tensors: the key's address, shape
-        # and stride check already makes the raw input pointers valid on a hit
-        return calls.put(key, (list(args) + [ops.ptr(epi)], head, B, want_l2, H, (keep, packed, layers, epi)))
+        if not all(isinstance(t, torch.Tensor) for t in ins) or ins[0].device.type != "cuda":
+            return None
+        return ins
+
+    def _build_own(self, dense, category, sequence, target):
+        """The cached entry's Bound; None when an input needs conversion (conversions make new tensors
+        per call: the uncached path) or outside the kernel's envelope."""
+        if not all(t.dtype == torch.int64 for t in list(category.values()) + [target["feedid"]] + list(sequence.values())):
+            return None
+        pl = self._plan(dense, category, sequence, target)
+        if pl["seq"].data_ptr() != sequence[SEQ_KEY].data_ptr():
+            return None
+        return self._build(pl, "rk_din_forward_ex")
 
     def forward(self, dense, category, sequence, target):
         tgt = target.get("feedid", None) if isinstance(target, dict) else None
@@ -374,46 +364,51 @@ class DIN(EngineModule):
             prob, logit = common.empty_rows(dev, 2)
             want_l2 = self.mini_batch_aware_regularization and self.l2_lambda > 0
             return prob, logit, (torch.full((), float("nan"), device=dev) if want_l2 else 0.0)
-        if not self.training:
-            out = self._eager_eval(dense, category, sequence, target)
-            if out is not None:
-                return out
+        bound = pl = None
+        ins = self._own_inputs(dense, category, sequence, target) if common.EAGER_CACHE and not self.training else None
+        if ins is not None:  # the cached entry: rk_din_forward_ex with fresh outputs and H2 weights patched in
+            dev = ins[0].device
+            bound = common.EagerCalls.lookup(self, ins, ops._lib.raw_stream(dev),
+                                             lambda: self._build_own(dense, category, sequence, target),
+                                             (self.att_weights.mode, tuple(dense), tuple(category)))
         if self.training and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             check_eval(self)  # a train-mode forward without autograd is not implemented
-        pl = self._plan(dense, category, sequence, target)
-        if self.training:  # Dice/BatchNorm batch statistics, Dropout, HIP backward (rankops.train)
-            if self.embeddings[SEQ_KEY].embedding_dim != pl["H"]:
-                raise NotImplementedError("rankops DIN training: target and history embeddings must share a width")
-            prob, logit, l2 = train.din_train_forward(self, pl, self.att_weights.get(pl["dev"]))
-            return prob, logit, (l2 if pl["want_l2"] else 0.0)
-        B, dev, segs, H = pl["B"], pl["dev"], pl["segs"], pl["H"]
-        cat_col0, q_col, att_col, width = pl["cat_col0"], pl["q_col"], pl["att_col"], pl["width"]
-        seq, seq_len = pl["seq"], pl["seq_len"]
-        T = seq.shape[1]
-        w = self.att_weights.get(dev)
-        logit = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        prob = torch.empty(B, 1, device=dev, dtype=torch.float32)
-        want_l2 = self.mini_batch_aware_regularization and self.l2_lambda > 0
-
-        if pl["fused"]:
-            # the whole forward in one launch (rk_din_forward)
-            l2_reg = torch.empty((), device=dev, dtype=torch.float32) if want_l2 else 0.0
+        if bound is None:
+            pl = self._plan(dense, category, sequence, target)
+            dev = pl["dev"]
+            if self.training:  # Dice/BatchNorm batch statistics, Dropout, HIP backward (rankops.train)
+                if self.embeddings[SEQ_KEY].embedding_dim != pl["H"]:
+                    raise NotImplementedError("rankops DIN training: target and history embeddings must share a width")
+                prob, logit, l2 = train.din_train_forward(self, pl, self.att_weights.get(dev))
+                return prob, logit, (l2 if pl["want_l2"] else 0.0)
+            bound = self._build(pl)
+        w = self.att_weights.get(dev)  # per-call mode: the reference's draws, once per forward
+        if bound is not None:
+            # the whole forward in one launch; a refusal (RK_ERR_UNSUPPORTED, e.g. past the kernel's
+            # LDS budget) marks the shape and takes the unfused launches, now and from then on
+            out = self._outputs(bound.batch, dev)
+            img = bound.patch(out, w)  # noqa: F841  (the attention image outlives the launch)
+            name, args = bound.launches[0]
+            args[-1] = ops._lib.raw_stream(dev)
             try:
-                self._launch_fused(pl, w, logit, prob, l2_reg)
-                return prob, logit, l2_reg
+                ops.din_forward(name, args)
+                return out
             except ops._lib.RankOpsError as e:
                 if getattr(e, "code", None) != ops._lib.RK_ERR_UNSUPPORTED:
                     raise
-                self._mark_unfusable(T, H)
-
+                self._mark_unfusable((pl["seq"] if pl is not None else sequence[SEQ_KEY]).shape[1],
+                                     self.embeddings["feedid"].embedding_dim)
+                common.EagerCalls.drop(self, bound)
+        pl = pl or self._plan(dense, category, sequence, target)
+        B, segs, H = pl["B"], pl["segs"], pl["H"]
+        cat_col0, q_col, att_col, width = pl["cat_col0"], pl["q_col"], pl["att_col"], pl["width"]
+        seq, seq_len = pl["seq"], pl["seq_len"]
+        prob, logit, l2_reg = self._outputs(B, dev)
         row = torch.empty(B, width, device=dev, dtype=torch.float32)
         ops.concat_gather(segs, B, row)
-        ops.din_attention(ops._lib.fptr(row, q_col), width, self.embeddings[SEQ_KEY].weight, seq, seq_len, T, H, w,
-                          self.use_softmax, ops._lib.fptr(row, att_col), width, B, dev)
+        ops.din_attention(ops._lib.fptr(row, q_col), width, self.embeddings[SEQ_KEY].weight, seq, seq_len, seq.shape[1], H,
+                          w, self.use_softmax, ops._lib.fptr(row, att_col), width, B, dev)
         run_tail(row, self._tail, self.output_layer, {}, logit, prob)
-
-        l2_reg = 0.0
-        if want_l2:
-            l2_reg = torch.empty((), device=dev, dtype=torch.float32)
+        if pl["want_l2"]:
             ops.row_l2norm_mean(row, cat_col0, width - cat_col0, float(self.l2_lambda), l2_reg)
         return prob, logit, l2_reg

@@ -41,38 +41,26 @@ class FwFM(EngineModule):
         self.field_weight = nn.Parameter(torch.randn(self.num_pairs), requires_grad=True)
         self.bias = nn.Parameter(torch.zeros(1))
 
-    def _eager_eval(self, x, return_logit):
-        """The eval forward through the EagerCalls cache (common.EagerCalls): one rk_fwfm_forward
-        call with fresh outputs patched in; None off that path."""
-        if not common.EAGER_CACHE:
-            return None
-        try:
-            idx = [x[n] for n in self.field_names]
-        except (KeyError, TypeError):
-            return None
-        if not all(isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 1 for t in idx) \
-                or idx[0].device.type != "cuda" or any(t.shape != idx[0].shape for t in idx):
-            return None
-        dev = idx[0].device
-        stream = ops._lib.raw_stream(dev)
-        calls = self.__dict__.setdefault("_eager", common.EagerCalls())
-        key = calls.key(self, idx, stream)
-        hit = calls.get(key)
-        if hit is None:
-            emb = [ops.table_segment(self.embedding[f].weight, t, 0) for f, t in enumerate(idx)]
-            lin = [ops.table_segment(self.linear[f].weight, t, 0) for f, t in enumerate(idx)]
-            ops._lib.ensure_device(dev)
-            ea, la = ops._seg_array(emb), ops._seg_array(lin)
-            args = [ea, la, len(emb), self.embed_dim, idx[0].shape[0], ops.as_f32(self.field_weight, "field_weight")
-                    .data_ptr(), ops.as_f32(self.bias, "bias").data_ptr(), None, None, None]
-            hit = calls.put(key, (args, idx[0].shape[0], (ea, la)))
-        args, B, _keep = hit
+    def _build(self, idx):
+        """The forward's one rk_fwfm_forward launch bound to the int64 [B] index tensors `idx` (field
+        order) as a common.Bound; the outputs are patched in per call.  The launch reads the
+        parameters in place."""
+        B, dev = idx[0].shape[0], idx[0].device
+        emb = [ops.table_segment(self.embedding[f].weight, t, 0) for f, t in enumerate(idx)]
+        lin = [ops.table_segment(self.linear[f].weight, t, 0) for f, t in enumerate(idx)]
+        fw, bias = ops.as_f32(self.field_weight, "field_weight"), ops.as_f32(self.bias, "bias")
+        args = ops.fwfm_forward_args(emb, lin, self.embed_dim, B, fw, bias, None, None)
+        return common.bound([("rk_fwfm_forward", args)], B, (fw, bias), self._patch)
+
+    @staticmethod
+    def _patch(_ep, args, out):
+        prob, logit = out
+        args[ops.FWFM_LOGIT_SLOT], args[ops.FWFM_PROB_SLOT] = ops.ptr(logit), prob.data_ptr()
+
+    @staticmethod
+    def _outputs(B, dev, return_logit=True):
         prob = torch.empty(B, device=dev, dtype=torch.float32)
-        logit = torch.empty(B, device=dev, dtype=torch.float32) if return_logit else None
-        args[7] = logit.data_ptr() if return_logit else None
-        args[8], args[9] = prob.data_ptr(), stream
-        ops.check(ops._lib.load().rk_fwfm_forward(*args), "rk_fwfm_forward")
-        return (prob, logit) if return_logit else prob
+        return prob, (torch.empty(B, device=dev, dtype=torch.float32) if return_logit else None)
 
     def prepare(self, x):
         """An eval forward bound to these index tensors (as DCNModel.prepare): returns `run()` that
@@ -82,22 +70,7 @@ class FwFM(EngineModule):
         if self.training:
             raise RuntimeError("FwFM.prepare: eval mode only (call .eval() first)")
         idxs = [ops.bound_index(x[name], f"x[{name!r}]") for name in self.field_names]
-        B, dev = idxs[0].shape[0], idxs[0].device
-        emb = ops._seg_array([ops.table_segment(self.embedding[f].weight, idx, 0) for f, idx in enumerate(idxs)])
-        lin = ops._seg_array([ops.table_segment(self.linear[f].weight, idx, 0) for f, idx in enumerate(idxs)])
-        prob = torch.empty(B, device=dev, dtype=torch.float32)
-        logit = torch.empty(B, device=dev, dtype=torch.float32)
-        fw, bias = ops.as_f32(self.field_weight, "field_weight"), ops.as_f32(self.bias, "bias")
-        ops._lib.ensure_device(dev)
-        args = (emb, lin, len(idxs), self.embed_dim, B, fw.data_ptr(), bias.data_ptr(), logit.data_ptr(),
-                prob.data_ptr(), ops._lib.stream_of(prob))
-        fn, out = ops._lib.load().rk_fwfm_forward, (prob, logit)
-
-        def run():
-            ops.check(fn(*args), "rk_fwfm_forward")
-            return out
-        run.keep = (args, idxs, fw, bias, x)
-        return run
+        return common.prepared(self, self._build(idxs), idxs[0].device, x)
 
     def forward(self, x, *, return_logit=False):
         """x: {field: int64 [B]} -> probabilities [B] (and the logits [B] with return_logit).
@@ -106,27 +79,32 @@ class FwFM(EngineModule):
         if not self.training and isinstance(first, torch.Tensor) and first.shape[0] == 0:
             prob, logit = common.empty_rows(ops.require_gpu(first, "x").device, 2, shape=(0,))
             return (prob, logit) if return_logit else prob
+        bound = None
         if not self.training:
-            out = self._eager_eval(x, return_logit)
-            if out is not None:
-                return out
+            try:
+                idxs = [x[n] for n in self.field_names]
+            except (KeyError, TypeError):
+                idxs = ()
+            # the caller's own int64 [B] tensors: the cached launch (anything else: the checks below)
+            if idxs and all(isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 1 for t in idxs) \
+                    and idxs[0].device.type == "cuda" and all(t.shape == idxs[0].shape for t in idxs):
+                bound = common.EagerCalls.lookup(self, idxs, ops._lib.raw_stream(idxs[0].device),
+                                                 lambda: self._build(idxs))
         if self.training and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             check_eval(self)  # a train-mode forward without autograd is not implemented
-        idx0 = ops.as_index(x[self.field_names[0]], f"x[{self.field_names[0]!r}]")
-        B = idx0.shape[0]
-        emb, lin, idxs = [], [], []
-        for f, name in enumerate(self.field_names):
-            idx = ops.as_index(x[name], f"x[{name!r}]")
-            if idx.shape != (B,):
-                raise ValueError(f"FwFM.forward: x[{name!r}] has shape {tuple(idx.shape)}, expected ({B},)")
-            idxs.append(idx)
-        if self.training:  # the train Function marshals its own segments
-            return train.fwfm_train_forward(self, idxs, return_logit)
-        for f, idx in enumerate(idxs):
-            emb.append(ops.table_segment(self.embedding[f].weight, idx, 0))
-            lin.append(ops.table_segment(self.linear[f].weight, idx, 0))
-        prob = torch.empty(B, device=idx0.device, dtype=torch.float32)
-        logit = torch.empty(B, device=idx0.device, dtype=torch.float32) if return_logit else None
-        ops.fwfm_forward(emb, lin, self.embed_dim, B, ops.as_f32(self.field_weight, "field_weight"),
-                         ops.as_f32(self.bias, "bias"), logit, prob)
-        return (prob, logit) if return_logit else prob
+        if bound is None:
+            B = ops.as_index(x[self.field_names[0]], f"x[{self.field_names[0]!r}]").shape[0]
+            idxs = []
+            for name in self.field_names:
+                idx = ops.as_index(x[name], f"x[{name!r}]")
+                if idx.shape != (B,):
+                    raise ValueError(f"FwFM.forward: x[{name!r}] has shape {tuple(idx.shape)}, expected ({B},)")
+                idxs.append(idx)
+            if self.training:  # the train Function marshals its own segments
+                return train.fwfm_train_forward(self, idxs, return_logit)
+            bound = self._build(idxs)
+        dev = idxs[0].device
+        out = self._outputs(bound.batch, dev, return_logit)
+        bound.patch(out)
+        common.run_launches(bound.launches, ops._lib.raw_stream(dev))
+        return out if return_logit else out[0]

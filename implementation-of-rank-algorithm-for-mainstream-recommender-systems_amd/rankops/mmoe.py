@@ -132,7 +132,8 @@ class MMoE(EngineModule):
         return [m for m in seq if isinstance(m, nn.Linear)]
 
     def _build(self, dense, names, idx, pin=False):
-        """The forward's launch over these inputs: (rk_mmoe_forward argument list, keep-alive objects)."""
+        """The forward's one rk_mmoe_forward launch over these inputs as a common.Bound (pin: prepare()'s
+        pinned weight images); the outputs are patched in per call."""
         if not self.fits():
             raise RuntimeError("MMoE: configuration outside rk_mmoe_forward's envelope (common.mmoe_fits)")
         B, dev = dense.shape[0], dense.device
@@ -155,18 +156,21 @@ class MMoE(EngineModule):
         heads = [(o.weight, o.bias) for o in self.tower_outputs]
         args, keep = ops.mmoe_forward_args(segs, self.input_dim, B, stacks, gate_image, gate_b, len(self.task_names),
                                            towers, heads, dev)
-        return args, (keep, stacks, towers, gate_w, gate_b, gate_image)
+        return common.bound([("rk_mmoe_forward", args)], B, (keep, stacks, towers, gate_w, gate_b, gate_image),
+                            self._patch)
 
     @staticmethod
-    def _run(built, out, stream):
-        args = built[0]
+    def _patch(_ep, args, out):
         prob, logit = out
-        args[ops.MMOE_LOGITS_SLOT], args[ops.MMOE_PROBS_SLOT], args[-1] = logit.data_ptr(), prob.data_ptr(), stream
-        ops.check(ops._lib.load().rk_mmoe_forward(*args), "rk_mmoe_forward")
+        args[ops.MMOE_LOGITS_SLOT], args[ops.MMOE_PROBS_SLOT] = logit.data_ptr(), prob.data_ptr()
+
+    @staticmethod
+    def _run(bound, out, stream):
+        bound.patch(out)
+        common.run_launches(bound.launches, stream)
 
     def _outputs(self, B, dev):
-        K = len(self.task_names)
-        return (torch.empty(B, K, device=dev, dtype=torch.float32), torch.empty(B, K, device=dev, dtype=torch.float32))
+        return common.empty_rows(dev, 2, (B, len(self.task_names)))
 
     def prepare(self, dense, category):
         """An eval forward bound to these input tensors (as DCNModel.prepare): returns `run()` that
@@ -178,18 +182,9 @@ class MMoE(EngineModule):
         dense = ops.as_f32(dense, "dense")
         names = list(self.embeddings)
         idx = [ops.bound_index(category[n], f"category[{n!r}]") for n in names]
-        B, dev = dense.shape[0], dense.device
-        if B == 0:
+        if dense.shape[0] == 0:
             raise ValueError("MMoE.prepare: empty batch")
-        built = self._build(dense, names, idx, pin=True)
-        out = self._outputs(B, dev)
-        stream = ops._lib.raw_stream(dev)
-
-        def run():
-            self._run(built, out, stream)
-            return out
-        run.keep = (built, dense, category)
-        return run
+        return common.prepared(self, self._build(dense, names, idx, pin=True), dense.device, (dense, category))
 
     def forward(self, dense, category):
         if not self.trainable:
@@ -209,17 +204,12 @@ class MMoE(EngineModule):
             grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             return train.mmoe_train_forward(self, dense, names, idx, grad)
         stream = ops._lib.raw_stream(dev)
-        own = all(t is category[n] for t, n in zip(idx, names))  # no converted copies: addresses are the caller's
-        if common.EAGER_CACHE and own:
-            calls = self.__dict__.setdefault("_eager", common.EagerCalls())
-            key = calls.key(self, [dense] + idx, stream)
-            built = calls.get(key)
-            if built is None:
-                built = calls.put(key, self._build(dense, names, idx))
+        if all(t is category[n] for t, n in zip(idx, names)):  # no converted copies: addresses are the caller's
+            bound = common.EagerCalls.lookup(self, [dense] + idx, stream, lambda: self._build(dense, names, idx))
         else:
-            built = self._build(dense, names, idx)
+            bound = self._build(dense, names, idx)
         out = self._outputs(B, dev)
-        self._run(built, out, stream)
+        self._run(bound, out, stream)
         return out
 
 

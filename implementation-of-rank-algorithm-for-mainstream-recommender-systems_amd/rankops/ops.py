@@ -156,23 +156,18 @@ def dcn_cross(segs, batch, width, cross_w, cross_b, num_layers, head_w_ptr, x0, 
                            ptr(partial), _lib.raw_stream(device)), "rk_dcn_cross")
 
 
+DCN_CROSS_W_SLOT, DCN_CROSS_B_SLOT = 4, 5
+
+
 def dcn_forward_args(segs, batch, width, cross_w, cross_b, num_layers, cross_head_w, layers, head: Epilogue,
                      device):
-    """The rk_dcn_forward argument list (the stream last, None) — cross_w / cross_b at [4] / [5] and
-    the stream at [-1] are the per-call slots of a cached eager forward (DCNModel)."""
+    """The rk_dcn_forward argument list (gather + cross stack + MLP tail + head in one launch; the
+    stream last, None) — cross_w / cross_b at DCN_CROSS_W_SLOT / DCN_CROSS_B_SLOT are per-call slots."""
     _lib.ensure_device(device)
     arr = _seg_array(segs)
     mls = (_lib.MlpLayer * max(1, len(layers)))(*layers)
     return [arr, len(segs), batch, width, ptr(cross_w), ptr(cross_b), num_layers, cross_head_w.data_ptr(), mls,
             len(layers), ctypes.byref(head), None]
-
-
-def dcn_forward(segs, batch, width, cross_w, cross_b, num_layers, cross_head_w, layers, head: Epilogue,
-                device):
-    """rk_dcn_forward: gather + cross stack + MLP tail + head in one launch (DCNModel eval forward)."""
-    args = dcn_forward_args(segs, batch, width, cross_w, cross_b, num_layers, cross_head_w, layers, head, device)
-    args[-1] = _lib.raw_stream(device)
-    check(_lib.load().rk_dcn_forward(*args), "rk_dcn_forward")
 
 
 def fm_gather(second, first, dim, batch, deep_in, fm1, fm2):
@@ -213,6 +208,10 @@ def fm_linear_packed(fields, dim, batch, layer: "_lib.MlpLayer", y, fm1, fm2):
     arr = _seg_array(fields)
     check(lib.rk_fm_linear_packed(arr, len(fields), dim, batch, ctypes.byref(layer), ptr(y), y.stride(0), ptr(fm1),
                                   ptr(fm2), _lib.stream_of(y)), "rk_fm_linear_packed")
+
+
+# (fm1, fm2) argument slots of the launch that opens a DeepFM eval forward, by entry point
+FM_OUT_SLOTS = {"rk_fm_gather_packed": (6, 7), "rk_fm_linear_packed": (7, 8), "rk_deepfm_forward": (7, 8)}
 
 
 def deepfm_whole_plan(k0: int, widths) -> bool:
@@ -796,14 +795,18 @@ def row_l2norm_mean(x: torch.Tensor, col0: int, ncols: int, scale: float, out: t
     return out
 
 
+AFM_LOGIT_SLOT, AFM_PROB_SLOT = 16, 17
+
+
 def afm_forward_args(fields, dim, batch, dense, dense_w, dense_b, att_w, att_b, att_h, att_hb, p_w, p_b, logit, prob):
-    """The argument tuple of one rk_afm_forward call (the segment array is part of it)."""
-    _lib.ensure_device(logit.device)
+    """The argument list of one rk_afm_forward call (the segment array is part of it; the stream
+    last); logit / prob (AFM_LOGIT_SLOT / AFM_PROB_SLOT) may be None and patched later."""
+    _lib.ensure_device(att_w.device)
     arr = _seg_array(fields)
     nd = dense.shape[1] if dense is not None else 0
-    return (arr, len(fields), dim, batch, ptr(dense), dense.stride(0) if dense is not None else 0, nd, ptr(dense_w),
+    return [arr, len(fields), dim, batch, ptr(dense), dense.stride(0) if dense is not None else 0, nd, ptr(dense_w),
             ptr(dense_b), ptr(att_w), ptr(att_b), att_w.shape[0], ptr(att_h), ptr(att_hb), ptr(p_w), ptr(p_b),
-            ptr(logit), ptr(prob), _lib.stream_of(logit))
+            ptr(logit), ptr(prob), _lib.stream_of(att_w)]
 
 
 def afm_forward(fields, dim, batch, dense, dense_w, dense_b, att_w, att_b, att_h, att_hb, p_w, p_b, logit, prob):
@@ -815,12 +818,21 @@ def _as_seg_array(segs):
     return segs if isinstance(segs, ctypes.Array) else _seg_array(segs)
 
 
+FWFM_LOGIT_SLOT, FWFM_PROB_SLOT = 7, 8
+
+
+def fwfm_forward_args(emb, lin, dim, batch, field_weight, bias, logit, prob):
+    """The argument list of one rk_fwfm_forward call (the stream last); emb / lin: lists of Segments or
+    ready rk_segment arrays (table_seg_array); logit / prob (FWFM_LOGIT_SLOT / FWFM_PROB_SLOT) may be
+    None and patched later."""
+    _lib.ensure_device(bias.device)
+    return [_as_seg_array(emb), _as_seg_array(lin), len(emb), dim, batch, ptr(field_weight), ptr(bias), ptr(logit),
+            ptr(prob), _lib.stream_of(bias)]
+
+
 def fwfm_forward(emb, lin, dim, batch, field_weight, bias, logit, prob):
-    """emb / lin: lists of Segments or ready rk_segment arrays (table_seg_array)."""
-    lib = _lib.load()
-    _lib.ensure_device(prob.device)
-    check(lib.rk_fwfm_forward(_as_seg_array(emb), _as_seg_array(lin), len(emb), dim, batch, ptr(field_weight),
-                              ptr(bias), ptr(logit), ptr(prob), _lib.stream_of(prob)), "rk_fwfm_forward")
+    check(_lib.load().rk_fwfm_forward(*fwfm_forward_args(emb, lin, dim, batch, field_weight, bias, logit, prob)),
+          "rk_fwfm_forward")
 
 
 def bst_attention(qkv, batch, T, d_model, heads, seq_len, ctx):
@@ -876,8 +888,8 @@ def pack_bst_weight(weight: torch.Tensor, out: torch.Tensor = None) -> torch.Ten
 
 
 def bst_small_forward_args(segs, width, table, seq, seq_len, heads, blocks, pool_mean, layers, head: Epilogue):
-    """The argument tuple of one rk_bst_small_forward call (every array it points into is part of
-    the tuple, so holding the tuple keeps them alive; the tensors stay the caller's)."""
+    """The argument list of one rk_bst_small_forward call, the stream last (every array it points
+    into is part of the list, so holding it keeps them alive; the tensors stay the caller's)."""
     B, T = seq.shape
     params = (ctypes.c_void_p * (BST_BLOCK_PARAMS * len(blocks)))()
     scalars = (ctypes.c_float * (3 * len(blocks)))()
@@ -888,16 +900,16 @@ def bst_small_forward_args(segs, width, table, seq, seq_len, heads, blocks, pool
             scalars[3 * i + k] = float(sc[k])
     arr = _seg_array(segs)
     larr = (_lib.MlpLayer * max(1, len(layers)))(*layers)
-    return (arr, len(segs), width, ptr(table), table.shape[0], table.stride(0), ptr(seq), seq.stride(0), T,
+    return [arr, len(segs), width, ptr(table), table.shape[0], table.stride(0), ptr(seq), seq.stride(0), T,
             ptr(seq_len), B, heads, len(blocks), params, scalars, 1 if pool_mean else 0, larr, len(layers),
-            ctypes.byref(head), _lib.stream_of(table))
+            ctypes.byref(head), _lib.stream_of(table)]
 
 
-def bst_small_forward(segs, width, table, seq, seq_len, heads, blocks, pool_mean, layers, head: Epilogue) -> bool:
-    """rk_bst_small_forward: the whole BST eval forward at d_model 16 in one launch.  False (nothing
-    launched) outside its envelope (RK_ERR_UNSUPPORTED), for the three-launch path."""
-    rc = _lib.load().rk_bst_small_forward(*bst_small_forward_args(segs, width, table, seq, seq_len, heads, blocks,
-                                                                  pool_mean, layers, head))
+def bst_small_forward(args) -> bool:
+    """rk_bst_small_forward over bst_small_forward_args' list: the whole BST eval forward at d_model
+    16 in one launch.  False (nothing launched) outside its envelope (RK_ERR_UNSUPPORTED), for the
+    three-launch path."""
+    rc = _lib.load().rk_bst_small_forward(*args)
     if rc == _lib.RK_ERR_UNSUPPORTED:
         return False
     check(rc, "rk_bst_small_forward")
@@ -972,6 +984,14 @@ def mlp_forward(x: torch.Tensor, layers, head: Epilogue = None, out: torch.Tenso
     return out
 
 
+def mlp_forward_gather_args(segs, width, batch, layers, head: Epilogue, device):
+    """The rk_mlp_forward_gather argument list (the row gather inside the fused MLP's launch; the
+    stream last, None)."""
+    _lib.ensure_device(device)
+    return [_seg_array(segs), len(segs), width, batch, (_lib.MlpLayer * len(layers))(*layers), len(layers),
+            ctypes.byref(head), None]
+
+
 def linear_tiled(x: torch.Tensor, layer: "_lib.MlpLayer", out: torch.Tensor, K: int = None):
     """One packed MLP layer as a 2D-tiled GEMM (rk_linear_tiled) into `out` [M, n]."""
     lib = _lib.load()
@@ -1013,36 +1033,41 @@ def din_pack_attention(att_weights, H: int) -> torch.Tensor:
     return img
 
 
-def _din_forward_args(segs, width, q_col, att_col, key_table, seq, seq_len, H, att_weights, use_softmax, layers,
-                      head: Epilogue, batch, device, l2_col0, l2_scale, l2_out, att_image, private_ws=False):
+# rk_din_forward argument slots: the row width, the layer array and its length (pack_epilogue_image),
+# and what a cached eager forward patches per call: the six H2 attention weights, l2_out, the image
+DIN_WIDTH_SLOT, DIN_LAYERS_SLOT, DIN_NUM_LAYERS_SLOT = 2, 21, 22
+DIN_H2_SLOTS, DIN_L2_OUT_SLOT, DIN_ATT_IMAGE_SLOT = slice(14, 20), 27, 28
+
+
+def _din_forward_args(segs, width, q_col, att_col, key_table, seq, seq_len, H, use_softmax, layers, head: Epilogue,
+                      batch, device, l2_col0, l2_scale, want_l2, private_ws=False):
     """The rk_din_forward argument list (without the stream) and the ctypes arrays it points into.
-    private_ws: an l2 workspace of its own (a prepared plan, which may run concurrently with other
-    plans on other streams) instead of the shared per-(device, batch) one."""
-    w1, b1, w2, b2, w3, b3 = att_weights
+    The H2 weights, l2_out (with want_l2) and the attention image are left empty: the caller patches
+    them (DIN_H2_SLOTS, DIN_L2_OUT_SLOT, DIN_ATT_IMAGE_SLOT).  private_ws: an l2 workspace of its own
+    (a prepared plan, which may run concurrently with other plans on other streams) instead of the
+    shared per-(device, batch) one."""
+    _lib.ensure_device(device)
     arr = _seg_array(segs)
     larr = (_lib.MlpLayer * max(1, len(layers)))(*layers)
     ws = None
-    if l2_out is not None:
+    if want_l2:
         if private_ws:
             ws = torch.zeros((batch + 15) // 16 + 1, device=device, dtype=torch.float32)
             torch.cuda.current_stream(ws.device).synchronize()  # zeroed before a launch on any stream
         else:
             ws = _din_l2_workspace(device, batch)
-    args = (arr, len(segs), width, q_col, att_col, ptr(key_table), key_table.shape[0], key_table.stride(0), ptr(seq),
-            seq.stride(0), seq.shape[1], ptr(seq_len), batch, H, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3),
-            ptr(b3), 1 if use_softmax else 0, larr, len(layers), ctypes.byref(head), l2_col0, float(l2_scale),
-            ptr(ws), ptr(l2_out), ptr(att_image))
+    args = [arr, len(segs), width, q_col, att_col, ptr(key_table), key_table.shape[0], key_table.stride(0), ptr(seq),
+            seq.stride(0), seq.shape[1], ptr(seq_len), batch, H, None, None, None, None, None, None,
+            1 if use_softmax else 0, larr, len(layers), ctypes.byref(head), l2_col0, float(l2_scale),
+            ptr(ws), None, None]
     return args, (arr, larr, head, ws)
 
 
-def din_forward(segs, width, q_col, att_col, key_table, seq, seq_len, H, att_weights, use_softmax, layers,
-                head: Epilogue, batch, device, l2_col0=0, l2_scale=0.0, l2_out=None, att_image=None):
-    """Whole DIN eval forward (row gather, attention, fcn tail, head, l2 partials) in one launch."""
-    lib = _lib.load()
-    _lib.ensure_device(device)
-    args, _keep = _din_forward_args(segs, width, q_col, att_col, key_table, seq, seq_len, H, att_weights,
-                                    use_softmax, layers, head, batch, device, l2_col0, l2_scale, l2_out, att_image)
-    check(lib.rk_din_forward(*args, _lib.raw_stream(device)), "rk_din_forward")
+def din_forward(name, args):
+    """Whole DIN eval forward (row gather, attention, fcn tail, head, l2 partials) in one launch:
+    `name` is rk_din_forward over _din_forward_args' list + [stream], or rk_din_forward_ex over that
+    list + [epilogue image, stream]."""
+    check(getattr(_lib.load(), name)(*args), "rk_din_forward")
 
 
 def pack_epilogue_image(larr, nlayers, K0, device):
@@ -1074,8 +1099,7 @@ class DinPlan:
         # phase B's epilogue parameters packed once (rk_mlp_pack_epilogue) and copied into LDS by
         # the kernel, for plans whose launches use them (balanced streamed plans); the image is a
         # snapshot of the current BatchNorm / Dice parameters, as the plan binds the weights
-        larr, nl, width = args[21], args[22], args[2]
-        img = pack_epilogue_image(larr, nl, width, device)
+        img = pack_epilogue_image(args[DIN_LAYERS_SLOT], args[DIN_NUM_LAYERS_SLOT], args[DIN_WIDTH_SLOT], device)
         if img is not None and self._lib.rk_din_plan_set_epilogue_image(self._handle, img.data_ptr()) == _lib.RK_OK:
             self._epi = img  # (RK_ERR_UNSUPPORTED: no streamed phase B)
 
@@ -1095,12 +1119,9 @@ class DinPlan:
             h.value = None
 
 
-def din_forward_plan(segs, width, q_col, att_col, key_table, seq, seq_len, H, att_weights, use_softmax, layers,
-                     head: Epilogue, batch, device, l2_col0=0, l2_scale=0.0, l2_out=None, att_image=None, keep=()):
-    _lib.ensure_device(device)
-    args, k = _din_forward_args(segs, width, q_col, att_col, key_table, seq, seq_len, H, att_weights, use_softmax,
-                                layers, head, batch, device, l2_col0, l2_scale, l2_out, att_image, private_ws=True)
-    return DinPlan(args, (k, tuple(keep)), device)
+def din_forward_plan(args, keep, device):
+    """A DinPlan over _din_forward_args' list (made with private_ws=True, every pointer patched in)."""
+    return DinPlan(args, keep, device)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor = None, *, M: int = None, K: int = None,

@@ -111,8 +111,9 @@ class XDeepFM(EngineModule):
         return names, idx
 
     def _build(self, names, idx):
-        """The forward's launches over these index tensors: (rk_cin_forward argument list, tail launch
-        list or None, head epilogue or None, deep_in, keep-alive objects)."""
+        """The forward's launches over these index tensors as a common.Bound: rk_cin_forward, then the
+        fused deep tail (ep None, and no tail launch, when the deep layers are outside it: _run).  The
+        outputs are patched in per call."""
         D, m = self.embedding_dim, self.num_categories
         B, dev = idx[0].shape[0], idx[0].device
         second = [ops.table_segment(self.second_order_embeddings[n].weight, i, f * D)
@@ -127,25 +128,33 @@ class XDeepFM(EngineModule):
                                           self.cin_output_layer.bias, deep_in, None, None, None, dev)
         head_kwargs = dict(final_w=self.final_layer.weight, final_b=self.final_layer.bias)
         tail = common.tail_launches(deep_in, self._tail, self.deep_output_layer, head_kwargs)
-        tl, ep, tkeep = tail if tail is not None else (None, None, None)
-        folded = [l.epilogue_kwargs() for l in self._tail]  # the folded BatchNorm affines the tail points into
-        # keep-alive: what the argument blocks point into (not the caller's index tensors: the cache
-        # key's address / shape / stride check makes those pointers valid on a hit)
-        return args, tl, ep, deep_in, (keep, images, tkeep, folded)
+        tl, ep, tkeep = tail if tail is not None else ([], None, None)
+        # keep-alive: the deep input (_run reads it), and what the argument blocks point into (not the
+        # caller's index tensors: the cache key's address / shape / stride check makes those pointers
+        # valid on a hit)
+        return common.bound([("rk_cin_forward", args)] + tl, B, dict(deep_in=deep_in, blocks=(keep, images, tkeep)),
+                            self._patch, ep)
 
-    def _run(self, built, out, stream):
-        args, tl, ep, deep_in, _keep = built
+    @staticmethod
+    def _patch(ep, args, out):
         prob, total, linear, cin, deep = out
-        args[_FM1_SLOT], args[_CIN_SLOT], args[-1] = linear.data_ptr(), cin.data_ptr(), stream
-        ops.check(ops._lib.load().rk_cin_forward(*args), "rk_cin_forward")
-        if tl is not None:
+        args[_FM1_SLOT], args[_CIN_SLOT] = linear.data_ptr(), cin.data_ptr()
+        if ep is not None:
             ep.fm1, ep.fm2, ep.head_aux = linear.data_ptr(), cin.data_ptr(), deep.data_ptr()
             ep.head_logit, ep.head_prob = total.data_ptr(), prob.data_ptr()
-            common.run_launches(tl, stream)
-        else:
+
+    def _run(self, bound, out, stream):
+        bound.patch(out)
+        common.run_launches(bound.launches, stream)
+        if bound.ep is None:  # deep layers outside the fused tail: rk_linear per layer
+            prob, total, linear, cin, deep = out
             head_kwargs = dict(fm1=linear, fm2=cin, final_w=self.final_layer.weight, final_b=self.final_layer.bias,
                                head_aux=deep)
-            run_tail(deep_in, self._tail, self.deep_output_layer, head_kwargs, total, prob)
+            run_tail(bound.keep["deep_in"], self._tail, self.deep_output_layer, head_kwargs, total, prob)
+
+    @staticmethod
+    def _outputs(B, dev):
+        return common.empty_rows(dev, 5, (B, 1))
 
     def prepare(self, category):
         """An eval forward bound to these input tensors (as DeepFM.prepare): returns `run()` that
@@ -159,24 +168,15 @@ class XDeepFM(EngineModule):
         idx = [ops.bound_index(category[n], f"category[{n!r}]") for n in names]
         if any(t.dim() != 1 or t.shape[0] != idx[0].shape[0] for t in idx):
             raise ValueError("XDeepFM.prepare: every category feature must be a 1-D tensor of one length")
-        B, dev = idx[0].shape[0], idx[0].device
-        if B == 0:
+        if idx[0].shape[0] == 0:
             raise ValueError("XDeepFM.prepare: empty batch")
-        built = self._build(names, idx)
-        if built[1] is None:
+        bound = self._build(names, idx)
+        if bound.ep is None:
             raise RuntimeError("XDeepFM.prepare: deep layers outside the fused tail (common.fused_mlp_fits)")
-        for l in self._tail:  # the images the plan binds are never rewritten in place under it
-            common.PACKED.pin(l.linear.weight)
+        common.pin_tail(self._tail)  # the images the plan binds are never rewritten in place under it
         for c in self.cin_layers:
             common.CIN_PACKED.pin(c.weight)
-        out = tuple(torch.empty(B, 1, device=dev, dtype=torch.float32) for _ in range(5))
-        stream = ops._lib.raw_stream(dev)
-
-        def run():
-            self._run(built, out, stream)
-            return out
-        run.keep = (built, category)
-        return run
+        return common.prepared(self, bound, idx[0].device, category)
 
     def forward(self, category):
         if not self.trainable:
@@ -189,16 +189,10 @@ class XDeepFM(EngineModule):
             grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             return train.xdeepfm_train_forward(self, names, idx, grad)
         stream = ops._lib.raw_stream(dev)
-        built = None
-        own = all(t is category[n] for t, n in zip(idx, names))  # no converted copies: addresses are the caller's
-        if common.EAGER_CACHE and own:
-            calls = self.__dict__.setdefault("_eager", common.EagerCalls())
-            key = calls.key(self, idx, stream)
-            built = calls.get(key)
-            if built is None:
-                built = calls.put(key, self._build(names, idx))
+        if all(t is category[n] for t, n in zip(idx, names)):  # no converted copies: addresses are the caller's
+            bound = common.EagerCalls.lookup(self, idx, stream, lambda: self._build(names, idx))
         else:
-            built = self._build(names, idx)
-        out = tuple(torch.empty(B, 1, device=dev, dtype=torch.float32) for _ in range(5))
-        self._run(built, out, stream)
+            bound = self._build(names, idx)
+        out = self._outputs(B, dev)
+        self._run(bound, out, stream)
         return out

@@ -233,7 +233,7 @@ def test_plan_epilogue_image_by_lds_dma_bit_identical(monkeypatch, dim, batch, b
         model.__dict__.pop("_eager", None)
         eager_dma = H.as_tuple(H.call_model(model, "din", d))  # the cached eager entry packs its image
         entry = next(iter(model._eager._d.values()))
-        assert entry[-1][-1] is not None
+        assert entry.keep[-1] is not None  # phase B's epilogue image
     torch.cuda.synchronize()
     for a, b, c, e in zip(dma, res, eager, eager_dma):
         assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(a, e)

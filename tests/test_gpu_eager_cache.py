@@ -57,7 +57,7 @@ def test_cached_eager_equals_uncached_and_follows_inputs(name):
     _equal(b, ref)
     assert a_live[0].data_ptr() != b_live[0].data_ptr() or a_live[0] is not b_live[0]
     assert torch.equal(a_live[0], a[0])  # the earlier output was not overwritten by the hit
-    assert len(model.__dict__["_eager"]._d) >= 1
+    assert len(model.__dict__["_eager"]) >= 1
     # new contents in the same buffers: the cached launch reads them
     new = H.to_device(H.make_inputs(name, cfg, 1000, seed=6), "cuda")
     _copy_into(inp, new)
@@ -95,6 +95,76 @@ def test_cached_eager_rebuilds_after_parameter_updates(name):
     x, _ = _run(model, name, inp, cached=True)
     y, _ = _run(model, name, inp, cached=False)
     _equal(x, y)
+
+
+BOUND_MODELS = dict(MODELS, afm={}, bst={"T": 20, "dim": 16}, deepcrossing={"interaction_weights": "frozen"})
+# the C entry points one forward issues: (cached eager hit, prepared run()), recorded once on the
+# commit before the eval forwards moved onto common.Bound, and equal to the model docstrings' launches
+BOUND_LAUNCHES = {
+    "afm": (["rk_afm_forward"], ["rk_afm_forward"]),
+    "bst": (["rk_bst_small_forward"], ["rk_bst_small_forward"]),
+    "dcn": (["rk_dcn_forward"], ["rk_dcn_forward"]),
+    "deepcrossing": (["rk_mlp_forward_gather"], ["rk_mlp_forward_gather"]),
+    "deepfm": (["rk_deepfm_forward"], ["rk_deepfm_forward"]),
+    "din": (["rk_din_forward_ex"], ["rk_din_plan_launch"]),
+    "fwfm": (["rk_fwfm_forward"], ["rk_fwfm_forward"]),
+}
+
+
+class _Recorder:
+    """The library handle with every call's entry-point name noted."""
+
+    def __init__(self, lib):
+        self._lib, self.names = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            self.names.append(name)
+            return fn(*args)
+        return call
+
+
+def _prepare(model, name, inp):
+    if name in ("dcn", "deepcrossing"):
+        return model.prepare(inp["dense"], inp["category"])
+    if name == "din":
+        return model.prepare(inp["dense"], inp["category"], inp["sequence"], inp["target"])
+    if name == "afm":
+        return model.prepare(inp["dense_input"], inp["category_input"])
+    if name == "bst":
+        return model.prepare(inp["dense"], inp["category"], inp["seq_feedid"], inp["seq_length"])
+    return model.prepare(inp["category"] if name == "deepfm" else inp["x"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(BOUND_MODELS))
+def test_hit_uncached_and_prepared_agree_and_issue_the_same_launches(name, monkeypatch):
+    """One bound eval forward per model: the cached eager hit, the forward with EAGER_CACHE off and
+    prepare()'s run() return bit-identical outputs, and the hit and run() issue exactly the C entry
+    points of BOUND_LAUNCHES.  Batch 37: two full 16-row tiles and a 5-row remainder."""
+    from rankops import ops
+    cfg = BOUND_MODELS[name]
+    model = H.build(name, cfg).cuda().eval()
+    inp = H.to_device(H.make_inputs(name, cfg, 37, seed=12), "cuda")
+    rec = _Recorder(ops._lib.load())
+    monkeypatch.setattr(ops._lib, "load", lambda: rec)
+    _run(model, name, inp, cached=True)  # builds the entry (and draws the frozen H2 weights)
+    rec.names.clear()
+    hit, _ = _run(model, name, inp, cached=True)
+    hit_names = list(rec.names)
+    uncached, _ = _run(model, name, inp, cached=False)
+    with torch.no_grad():
+        run = _prepare(model, name, inp)
+        rec.names.clear()
+        prepared = H.as_tuple(run())
+        run_names = list(rec.names)
+    torch.cuda.synchronize()
+    assert len(prepared) >= len(hit) == len(uncached) >= 1
+    _equal(hit, uncached)
+    _equal(hit, prepared[:len(hit)])  # FwFM: forward() returns prob alone, run() (prob, logit)
+    assert (hit_names, run_names) == BOUND_LAUNCHES[name]
 
 
 @pytest.mark.gpu

@@ -188,9 +188,9 @@ def test_model_matches_restatement(name):
         out = model(inp["dense"], inp["category"])
         assert out[0].shape == out[1].shape == (B, K)
         check_model(out, ref, name)
-        entries = len(model._eager._d)
+        entries = len(model._eager)
         cached = model(inp["dense"], inp["category"])  # the EagerCalls hit
-        assert len(model._eager._d) == entries
+        assert len(model._eager) == entries
         common.EAGER_CACHE = False
         try:
             uncached = model(inp["dense"], inp["category"])
