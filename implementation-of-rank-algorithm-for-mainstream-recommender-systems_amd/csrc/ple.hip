@@ -1,0 +1,503 @@
+// PLE (Progressive Layered Extraction, Tang et al., RecSys 2020) eval forward in one launch, on the
+// fused-MLP machinery of mlp_core.h as mmoe.hip uses it: 16 rows per workgroup of 16 waves, FP32
+// MFMA (v_mfma_f32_16x16x4_f32), fragment-major packed weights streamed through the 8-slot ring.
+//
+// L extraction levels.  With x_k^{-1} = x_s^{-1} = the gathered row, level j computes
+//   g_k   = softmax(gate_{j,k}(x_k^{j-1}))       ms + mc columns: task k's own experts, then the shared
+//   g_s   = softmax(gate_{j,s}(x_s^{j-1}))       K ms + mc columns: every expert of the level (not at
+//                                                the last level)
+//   f_s   = expert_{j,s}(its owner's input)      stack s = k ms + i reads x_k, s = K ms + i reads x_s
+//   x_k^j = sum_c g_k[c] f,  x_s^j = sum_c g_s[c] f     c ascending
+// and logit_k = head_k(tower_k(x_k^{L-1})), prob_k = sigmoid(logit_k).
+//
+// Phases of a workgroup (a barrier after each layer; the next layer's weight ring is issued before
+// that barrier, LayerPipe::prepare):
+//   1. wave w gathers row m0 + w into input slot 0 (level 0: every expert and gate reads it)
+//   2. per level, the gates: K (+ 1) small GEMMs, each on its own input, into the two gate-logit
+//      buffers in turn; the softmax of gate q (maximum subtracted) is one wave's work while the
+//      others run gate q + 1, its weights left transposed in gt
+//   3. the level's experts s = 0 .. K ms + mc - 1, layers ping-pong ha / hb; the last layer's tiles
+//      stay in registers (TileSink) and each lane adds g * z into its own elements of every mixture
+//      the expert belongs to (a task's expert: that task's and the shared one; a shared expert: all
+//      K + 1).  s ascends, which is the gates' column order, so two runs give the same bits.
+//   4. the K + 1 mixtures (accumulator layout in mt) become the next level's row-major inputs; after
+//      the last level each task's mixture goes to ha, through its tower, and the head (one wave per
+//      row), as in mmoe.hip.
+// Nothing between the gather and the logits reaches HBM unless reps / gates ask for it.
+//
+// The layer descriptors of L (K ms + mc) De + L (K + 1) + K Dt + K layers do not fit in the 4 KiB of
+// kernel arguments: they are a device table of rk_mmoe_layer (pointers only are read from it; every
+// width comes from the arguments the host checked).
+//
+// LDS (floats): xin [nx][16][ldr] (nx = K + 1 inputs, 1 when L == 1), ha and hb [16][ldh],
+// gs [2][16][64 + 8], gt [GC][16] (gt[(column offset + c) 16 + row]), mt [K + 1][pad64(H)][16]
+// (mt[(i pad64(H) + n) 16 + row]: every element belongs to one lane, no barrier guards it).
+#include "mlp_core.h"
+
+namespace rk {
+
+constexpr int kPlSegs = 16;
+constexpr int kPlCols = 256;
+constexpr int kPlMaxLevels = 4;
+constexpr int kPlMaxTasks = 8;
+constexpr int kPlMaxStacks = 64;  // K ms + mc: the shared gate's columns (4 tiles)
+constexpr int kPlMaxDepth = 3;
+constexpr int kPlLdG = kPlMaxStacks + kMlpLdPad;
+
+struct PleArgs {
+  rk_segment segs[kPlSegs];
+  uint8_t col_seg[kPlCols], col_off[kPlCols];  // 255: no segment
+  const rk_mmoe_layer* table;  // device: experts [(j NE + s) De + l], gates, towers [k Dt + l], heads
+  int64_t M;
+  int width, L, K, ms, mc, De, Dt, H;
+  int eu[kPlMaxDepth], tu[kPlMaxDepth];
+  int has_head;
+  int ldr, ldh, nx;
+  float* logits;
+  float* probs;
+  float* reps[kPlMaxLevels];
+  float* gates[kPlMaxLevels];
+  uint32_t* flags;
+};
+static_assert(sizeof(PleArgs) <= 4096, "kernel arguments beyond 4 KiB");
+
+// mlp_layer's sink of an expert's last layer: the wave's finished tiles stay in registers (one type
+// per tile count, as in mmoe.hip).
+template <int TPW>
+struct PlTileSink {
+  f32x4_t z[TPW];
+  __device__ __forceinline__ void take(int j, int r, int row, float v) { z[j][r] = v; }
+};
+
+// Wave w owns column tiles w and w + 16; a wave without a tile takes part in the active waves'
+// lockstep barriers.
+__device__ __forceinline__ void pl_prepare(LayerPipe& pipe, const rk_mlp_layer& L, int K, int wave, int lane) {
+  const int nt = pad64(L.n) / 16, kch = pad64(K) / 16;
+  if (wave + kMlpWaves < nt)
+    pipe.prepare<2, 4>(L, kch, wave, lane);
+  else if (wave < nt)
+    pipe.prepare<1, 8>(L, kch, wave, lane);
+}
+
+__device__ __forceinline__ void pl_layer(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin, float* out,
+                                         int ldout, int Kp, int wave, int lane) {
+  const int ntiles = pad64(L.n) / 16;
+  if (wave + kMlpWaves < ntiles) {
+    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
+  } else if (wave < ntiles) {
+    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
+  } else {
+    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
+  }
+}
+
+// The same with the output tiles left in z (zero for a tile the wave does not own), nothing in LDS.
+__device__ __forceinline__ void pl_layer_tiles(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin,
+                                               int Kp, int wave, int lane, f32x4_t (&z)[2]) {
+  const int ntiles = pad64(L.n) / 16;
+  z[0] = z[1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  if (wave + kMlpWaves < ntiles) {
+    PlTileSink<2> f;
+    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
+    z[0] = f.z[0];
+    z[1] = f.z[1];
+  } else if (wave < ntiles) {
+    PlTileSink<1> f;
+    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
+    z[0] = f.z[0];
+  } else {
+    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
+  }
+}
+
+__global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+  const int64_t m0 = (int64_t)blockIdx.x * kMlpRows;
+  const int rows = (int)min<int64_t>(kMlpRows, a.M - m0);
+  const int width = a.width, NL = a.L, K = a.K, ms = a.ms, mc = a.mc, De = a.De, Dt = a.Dt, H = a.H;
+  const int NE = K * ms + mc;             // the stacks of a level: task k's at k ms + i, the shared at K ms + i
+  const int GT = ms + mc;                 // a task gate's columns
+  const int GC = K * GT + NE;             // gt's columns: task gate k at k GT, the shared gate at K GT
+  const int Hp = pad64(H), ntH = Hp / 16;
+  float* const xin = sm;
+  float* const ha = xin + a.nx * kMlpRows * a.ldr;
+  float* const hb = ha + kMlpRows * a.ldh;
+  float* const gs = hb + kMlpRows * a.ldh;
+  float* const gt = gs + 2 * kMlpRows * kPlLdG;
+  float* const mt = gt + GC * kMlpRows;
+  const int K0p = pad64(width);
+  const bool live = wave < rows;
+  const int64_t b = m0 + wave;
+  const rk_mmoe_layer* __restrict__ const table = a.table;
+  const int gate0 = NL * NE * De, tower0 = gate0 + NL * (K + 1), head0 = tower0 + K * Dt;
+
+  // 1. the row gather (mlp_gather_kernel's stage): indices first, the values after
+  float v[kPlCols / 64];
+  int64_t r[kPlCols / 64];
+  int sg[kPlCols / 64];
+#pragma unroll
+  for (int i = 0; i < kPlCols / 64; ++i) {
+    const int c = lane + 64 * i;
+    sg[i] = live && c < width ? a.col_seg[c] : 255;
+    r[i] = b;
+    if (sg[i] != 255) {
+      const rk_segment& g = a.segs[sg[i]];
+      if (g.idx) {
+        r[i] = g.idx[b * g.idx_stride];
+        if (r[i] < 0 || r[i] >= g.rows) {
+          flag_oob(a.flags);
+          r[i] = -1;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kPlCols / 64; ++i) {
+    v[i] = 0.f;
+    if (sg[i] != 255 && r[i] >= 0) {
+      const rk_segment& g = a.segs[sg[i]];
+      v[i] = g.src[r[i] * g.src_ld + a.col_off[lane + 64 * i]];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);  // the gather's loads stay ahead of the weight ring
+
+  LayerPipe pipe;
+  // (selects, not a[l]: an index the compiler cannot resolve into the by-value arguments' int arrays
+  // moved the whole argument block into scratch)
+  auto eun = [&](int l) { return l == 0 ? a.eu[0] : l == 1 ? a.eu[1] : a.eu[2]; };
+  auto tun = [&](int l) { return l == 0 ? a.tu[0] : l == 1 ? a.tu[1] : a.tu[2]; };
+  auto view = [&](int idx, int n, int act) {
+    rk_mlp_layer L = {};
+    L.w = table[idx].w;
+    L.bias = table[idx].bias;
+    L.n = n;
+    L.act = act;
+    return L;
+  };
+  // level j's input width, its expert s layer l, its gate q (q == K: the shared one), tower k layer l
+  auto in_width = [&](int j) { return j ? H : width; };
+  auto expert = [&](int j, int s, int l) {
+    rk_mlp_layer L = view((j * NE + s) * De + l, eun(l), RK_ACT_RELU);
+    L.ldw = pad64(l ? eun(l - 1) : in_width(j));
+    return L;
+  };
+  auto gate = [&](int j, int q) {
+    rk_mlp_layer L = view(gate0 + j * (K + 1) + q, q < K ? GT : NE, RK_ACT_NONE);
+    L.ldw = pad64(in_width(j));
+    return L;
+  };
+  auto tower = [&](int k, int l) {
+    rk_mlp_layer L = view(tower0 + k * Dt + l, tun(l), RK_ACT_RELU);
+    L.ldw = pad64(l ? tun(l - 1) : H);
+    return L;
+  };
+  // input slot of owner q (a task, or K: the shared representation) at level j
+  auto input = [&](int j, int q) -> const float* { return j ? xin + q * kMlpRows * a.ldr : xin; };
+  // The lane index behind an empty asm, taken once per layer (mmoe.hip: derived from `lane` itself the
+  // compiler hoists every layer's addresses out of the loops and spills them around every layer).
+  auto lane_now = [&]() {
+    int x = lane;
+    asm volatile("" : "+v"(x));
+    return x;
+  };
+  auto close_layer = [&]() {
+    mlp_lds_barrier();
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  {
+    const rk_mlp_layer LG = gate(0, 0);
+    pl_prepare(pipe, LG, width, wave, lane);
+  }
+#pragma unroll
+  for (int i = 0; i < kPlCols / 64; ++i) {
+    const int c = lane + 64 * i;
+    if (c < K0p) xin[wave * a.ldr + c] = v[i];  // dead rows and pad columns stage zeros
+  }
+  mlp_lds_barrier();
+
+  for (int j = 0; j < NL; ++j) {
+    const bool last_level = j + 1 == NL;
+    const int nq = last_level ? K : K + 1;  // the last level has no shared gate and no shared mixture
+    const int Kin = in_width(j), Kinp = pad64(Kin);
+    const int gcols = K * GT + (last_level ? 0 : NE);  // columns of this level's gate output
+
+    // 2. the gates
+    for (int q = 0; q < nq; ++q) {
+      const int ln = lane_now();
+      const rk_mlp_layer LG = gate(j, q);
+      float* const gq = gs + (q & 1) * kMlpRows * kPlLdG;
+      pl_layer(pipe, LG, input(j, q), a.ldr, gq, kPlLdG, Kinp, wave, ln);
+      {  // the next gate, or the level's first expert (one prepare for both: the descriptor is chosen, not the call)
+        const bool more = q + 1 < nq;
+        rk_mlp_layer N = view(more ? gate0 + j * (K + 1) + q + 1 : j * NE * De, more ? (q + 1 < K ? GT : NE) : eun(0),
+                              more ? RK_ACT_NONE : RK_ACT_RELU);
+        N.ldw = Kinp;
+        pl_prepare(pipe, N, Kin, wave, ln);
+      }
+      close_layer();
+      // softmax of gate q: one wave outside the four that own the next gate's tiles; lane = row + 16 part,
+      // part p takes the columns c = p, p + 4, ...
+      if (wave == 4 + (q & 7)) {
+        const int row = ln & 15, part = ln >> 4, n = LG.n, off = q * GT;
+        const float* const p = gq + row * kPlLdG;
+        float mx = -INFINITY;
+        for (int c = part; c < n; c += 4) mx = fmaxf(mx, p[c]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        float s = 0.f;
+        for (int c = part; c < n; c += 4) s += expf(p[c] - mx);
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        float* const go = a.gates[j];
+        for (int c = part; c < n; c += 4) {
+          const float w = expf(p[c] - mx) / s;
+          gt[(off + c) * kMlpRows + row] = w;
+          if (go && row < rows) go[(m0 + row) * gcols + off + c] = w;
+        }
+      }
+    }
+    mlp_lds_barrier();  // the last gate's weights are in gt
+
+    // 3. the experts; the mix after the last layer's epilogue
+    for (int s = 0; s < NE; ++s) {
+      const int owner = s < K * ms ? s / ms : K;
+      const float* const x0 = input(j, owner);
+      for (int l = 0; l < De; ++l) {
+        const int ln = lane_now();
+        const rk_mlp_layer L = expert(j, s, l);
+        const int Kp = pad64(l ? eun(l - 1) : Kin);
+        const float* in = l == 0 ? x0 : (l & 1) ? ha : hb;
+        float* out = (l & 1) ? hb : ha;
+        // what runs next (one prepare for every case: the descriptor is chosen, not the call): this expert's
+        // next layer, the next expert, the next level's first gate, or the first tower
+        int nidx = (j * NE + s) * De + l + 1, nn = eun(l + 1 < De ? l + 1 : 0), nk = L.n, nact = RK_ACT_RELU;
+        bool has_next = true;
+        if (l + 1 == De) {
+          nk = Kin;
+          if (s + 1 == NE) {
+            nk = H;
+            if (!last_level) {
+              nidx = gate0 + (j + 1) * (K + 1);
+              nn = GT;
+              nact = RK_ACT_NONE;
+            } else {
+              nidx = tower0;
+              nn = tun(0);
+              has_next = a.has_head && Dt > 0;
+            }
+          }
+        }
+        rk_mlp_layer N = view(has_next ? nidx : 0, nn, nact);
+        N.ldw = pad64(nk);
+        if (l + 1 < De) {
+          pl_layer(pipe, L, in, l == 0 ? a.ldr : a.ldh, out, a.ldh, Kp, wave, ln);
+          pl_prepare(pipe, N, nk, wave, ln);
+        } else {
+          f32x4_t z[2];
+          pl_layer_tiles(pipe, L, in, l == 0 ? a.ldr : a.ldh, Kp, wave, ln, z);
+          if (has_next) pl_prepare(pipe, N, nk, wave, ln);
+          const int q4 = (ln >> 4) * 4;  // the lane's first row
+          // mixtures i0 .. i1 - 1 take this expert (a task's expert: its task, then the shared one below)
+          const int i0 = owner < K ? owner : 0, i1 = owner < K ? owner + 1 : K;
+          const int col = owner < K ? s - owner * ms : ms + (s - K * ms);  // its column of a task gate
+          for (int i = i0; i <= i1; ++i) {
+            int slot = i, gcol = i * GT + col;
+            bool first = ms > 0 ? s == i * ms : s == 0;
+            if (i == i1) {  // the shared mixture, column s of the shared gate
+              if (last_level) break;
+              slot = K;
+              gcol = K * GT + s;
+              first = s == 0;
+            }
+            const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(gt + gcol * kMlpRows + q4);
+#pragma unroll
+            for (int t2 = 0; t2 < 2; ++t2) {
+              const int t = wave + kMlpWaves * t2;
+              if (t < ntH) {
+                f32x4_t* const mp = reinterpret_cast<f32x4_t*>(mt + (slot * Hp + 16 * t + (ln & 15)) * kMlpRows + q4);
+                f32x4_t m = {0.f, 0.f, 0.f, 0.f};
+                if (!first) m = *mp;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) m[q] = __builtin_fmaf(gv[q], z[t2][q], m[q]);
+                *mp = m;
+              }
+            }
+          }
+        }
+        close_layer();
+      }
+    }
+
+    if (!last_level) {
+      // 4a. the K + 1 mixtures -> the next level's row-major inputs (pad columns hold zeros) and reps[j]
+      const int lm = lane_now();
+      float* const ro = a.reps[j];
+      for (int i = 0; i <= K; ++i) {
+        float* const xi = xin + i * kMlpRows * a.ldr;
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+          const int t = wave + kMlpWaves * t2;
+          if (t < ntH) {
+            const int n = 16 * t + (lm & 15);
+            const f32x4_t mv = *reinterpret_cast<const f32x4_t*>(mt + (i * Hp + n) * kMlpRows + (lm >> 4) * 4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int row = (lm >> 4) * 4 + q;
+              xi[row * a.ldr + n] = mv[q];
+              if (ro && n < H && row < rows) ro[((m0 + row) * (K + 1) + i) * H + n] = mv[q];
+            }
+          }
+        }
+      }
+      mlp_lds_barrier();
+    }
+  }
+
+  // 4b. per task: the last level's mixture to LDS row-major (and reps[L - 1]), the tower, the head
+  {
+    float* const ro = a.reps[NL - 1];
+    for (int k = 0; k < K; ++k) {
+      const int lm = lane_now();
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2) {
+        const int t = wave + kMlpWaves * t2;
+        if (t < ntH) {
+          const int n = 16 * t + (lm & 15);
+          const f32x4_t mv = *reinterpret_cast<const f32x4_t*>(mt + (k * Hp + n) * kMlpRows + (lm >> 4) * 4);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int row = (lm >> 4) * 4 + q;
+            if (a.has_head) ha[row * a.ldh + n] = mv[q];  // pad columns hold zeros: the tower's zero K pad
+            if (ro && n < H && row < rows) ro[((m0 + row) * K + k) * H + n] = mv[q];
+          }
+        }
+      }
+      if (!a.has_head) continue;
+      mlp_lds_barrier();
+      for (int l = 0; l < Dt; ++l) {
+        const int ln = lane_now();
+        const rk_mlp_layer L = tower(k, l);
+        const int Kp = pad64(l ? tun(l - 1) : H);
+        const float* in = (l & 1) ? hb : ha;
+        float* out = (l & 1) ? ha : hb;
+        pl_layer(pipe, L, in, a.ldh, out, a.ldh, Kp, wave, ln);
+        if (l + 1 < Dt) {
+          const rk_mlp_layer N = tower(k, l + 1);
+          pl_prepare(pipe, N, L.n, wave, ln);
+        } else if (k + 1 < K) {
+          const rk_mlp_layer N = tower(k + 1, 0);
+          pl_prepare(pipe, N, H, wave, ln);
+        }
+        close_layer();
+      }
+      const float* fin = (Dt & 1) ? hb : ha;
+      const int Kh = Dt ? tun(Dt - 1) : H;
+      if (live) {  // one wave per row
+        const float* hw = table[head0 + k].w;
+        float p = 0.f;
+        for (int n = lm; n < Kh; n += 64) p = __builtin_fmaf(fin[wave * a.ldh + n], hw[n], p);
+        p = wave_sum(p);
+        if (lm == 0) {
+          const float logit = p + table[head0 + k].bias[0];
+          if (a.logits) a.logits[b * K + k] = logit;
+          if (a.probs) a.probs[b * K + k] = sigmoid_fast(logit);
+        }
+      }
+      mlp_lds_barrier();  // the next task's mixture overwrites ha
+    }
+  }
+}
+
+}  // namespace rk
+
+using namespace rk;
+
+RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
+                          int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
+                          int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
+                          const rk_mmoe_layer* table, int64_t table_len, float* logits, float* probs,
+                          float* const* level_reps, float* const* level_gates, void* stream) {
+  const char* const name = "rk_ple_forward";
+  if (!segs || !table || !expert_units || batch < 0 || nseg <= 0 || width <= 0 || num_levels <= 0 || num_tasks <= 0 ||
+      num_specific < 0 || num_shared <= 0 || expert_depth <= 0 || tower_depth < 0 || (tower_depth > 0 && !tower_units) ||
+      (tower_depth > 0 && !has_heads))
+    return fail(RK_ERR_INVALID, "%s: null pointer or negative size (batch %lld)", name, (long long)batch);
+  if (!has_heads && (logits || probs)) return fail(RK_ERR_INVALID, "%s: logits / probs need the heads", name);
+  const int L = num_levels, K = num_tasks, ms = num_specific, mc = num_shared, De = expert_depth, Dt = tower_depth;
+  const int64_t NE = (int64_t)K * ms + mc;
+  if (nseg > kPlSegs || width > kPlCols || L > kPlMaxLevels || K > kPlMaxTasks || ms > kPlMaxStacks ||
+      mc > kPlMaxStacks || NE > kPlMaxStacks || De > kPlMaxDepth || Dt > kPlMaxDepth)
+    return fail(RK_ERR_UNSUPPORTED, "%s: %d segments (<= %d) over %d columns (<= %d), %d levels (<= %d), %d tasks (<= %d), "
+                "%d specific and %d shared experts (tasks x specific + shared <= %d) of depth %d (1..%d), tower depth %d "
+                "(<= %d)", name, nseg, kPlSegs, width, kPlCols, L, kPlMaxLevels, K, kPlMaxTasks, ms, mc, kPlMaxStacks,
+                De, kPlMaxDepth, Dt, kPlMaxDepth);
+  bool any_out = logits || probs;
+  for (int j = 0; j < L; ++j) any_out = any_out || (level_reps && level_reps[j]) || (level_gates && level_gates[j]);
+  if (!any_out) return fail(RK_ERR_INVALID, "%s: no output", name);
+  PleArgs a = {};
+  int wide = kMlpPad;  // the widest hidden activation, padded
+  for (int l = 0; l < De + Dt; ++l) {
+    const int n = l < De ? expert_units[l] : tower_units[l - De];
+    if (n <= 0) return fail(RK_ERR_INVALID, "%s: %s layer %d: n = %d", name, l < De ? "expert" : "tower", l < De ? l : l - De, n);
+    if (n > kMlpMaxN)
+      return fail(RK_ERR_UNSUPPORTED, "%s: %s layer %d: n = %d (<= %d)", name, l < De ? "expert" : "tower",
+                  l < De ? l : l - De, n, kMlpMaxN);
+    (l < De ? a.eu[l] : a.tu[l - De]) = n;
+    wide = std::max(wide, pad64(n));
+  }
+  const int H = expert_units[De - 1];
+  const int64_t want = (int64_t)L * NE * De + (int64_t)L * (K + 1) + (has_heads ? (int64_t)K * Dt + K : 0);
+  if (table_len != want || !aligned16(table) || ((uintptr_t)table & 7u))
+    return fail(RK_ERR_INVALID, "%s: the layer table holds %lld descriptors, this shape needs %lld", name,
+                (long long)table_len, (long long)want);
+  for (int c = 0; c < kPlCols; ++c) {
+    a.col_seg[c] = 255;
+    a.col_off[c] = 0;
+  }
+  for (int i = 0; i < nseg; ++i) {
+    const rk_segment& sg = segs[i];
+    if (!sg.src || sg.dim <= 0 || sg.out_col < 0 || sg.out_col + sg.dim > width || (sg.idx && sg.rows <= 0) ||
+        sg.dim > 255)
+      return fail(RK_ERR_INVALID, "%s: segment %d invalid", name, i);
+    a.segs[i] = sg;
+    for (int c = sg.out_col; c < sg.out_col + sg.dim; ++c) {  // the last covering segment wins
+      a.col_seg[c] = (uint8_t)i;
+      a.col_off[c] = (uint8_t)(c - sg.out_col);
+    }
+  }
+  a.table = table;
+  a.M = batch;
+  a.width = width;
+  a.L = L;
+  a.K = K;
+  a.ms = ms;
+  a.mc = mc;
+  a.De = De;
+  a.Dt = Dt;
+  a.H = H;
+  a.has_head = has_heads != 0;
+  a.nx = L > 1 ? K + 1 : 1;
+  a.ldr = pad64(L > 1 ? std::max(width, H) : width) + kMlpLdPad;
+  a.ldh = wide + kMlpLdPad;
+  a.logits = logits;
+  a.probs = probs;
+  for (int j = 0; j < L; ++j) {
+    a.reps[j] = level_reps ? level_reps[j] : nullptr;
+    a.gates[j] = level_gates ? level_gates[j] : nullptr;
+  }
+  // LDS: the level inputs, the activation buffers, the gate logits and weights, the K + 1 mixtures
+  const int64_t GC = (int64_t)K * (ms + mc) + NE;
+  const size_t shm = (size_t)kMlpRows * ((size_t)a.nx * a.ldr + 2 * a.ldh + 2 * kPlLdG + GC + (size_t)(K + 1) * pad64(H)) *
+                     sizeof(float);
+  if (shm > 160 * 1024) return fail(RK_ERR_UNSUPPORTED, "%s: this shape needs %zu B of LDS (<= %d)", name, shm, 160 * 1024);
+  a.flags = device_flags();
+  if (!a.flags) return fail(RK_ERR_RUNTIME, "%s: device not initialised (rk_init)", name);
+  if (batch == 0) return RK_OK;
+  const int64_t blocks = (batch + kMlpRows - 1) / kMlpRows;
+  if (blocks > INT32_MAX) return fail(RK_ERR_UNSUPPORTED, "%s: batch too large", name);
+  raise_lds_limit((const void*)ple_kernel, 160 * 1024);
+  ple_kernel<<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(a);
+  return check_launch(name);
+}

@@ -22,6 +22,10 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
                                            snapshot): one probability per task, the whole eval forward in
                                            one launch (rk_mmoe_forward); rankops.mmoe is the module and,
                                            called, the same kernel on plain tensors
+    PLE, ple                               PLE, progressive layered extraction (the multi-task list's third
+                                           model, no script in the reference): L levels of task and shared
+                                           experts and gates, the whole eval forward in one launch
+                                           (rk_ple_forward); rankops.ple is the module and, called, the op
 
 `rankops.sharded.ShardedDeepFM` adds the table-sharded multi-GPU DeepFM lookup (RCCL
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the
@@ -49,6 +53,8 @@ from .fwfm import FwFM  # noqa: F401
 from .loader import BatchAssembler, Vocabulary, label_encode, wechat_vocabularies  # noqa: F401
 from . import mmoe  # noqa: F401  (callable: rankops.mmoe(x, experts, gates, towers=None))
 from .mmoe import MMoE  # noqa: F401
+from . import ple  # noqa: F401  (callable: rankops.ple(x, levels, towers=None, return_levels=False))
+from .ple import PLE  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
 from .ranking import GroupedAUC, GroupTable, RequestTopK, grouped_auc, topk_per_request, topk_segments  # noqa: F401
 from .ops import cin  # noqa: F401
@@ -61,5 +67,5 @@ __all__ = [
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
     "dien_aux_loss", "dien_aux_loss_gather", "dien_extract", "dien_extract_gather", "dien_evolve", "DIENInterests",
-    "SparseAdam", "XDeepFM", "cin", "MMoE", "mmoe", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
+    "SparseAdam", "XDeepFM", "cin", "MMoE", "mmoe", "PLE", "ple", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
 ]

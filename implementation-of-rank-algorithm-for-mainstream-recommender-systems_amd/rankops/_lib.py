@@ -445,6 +445,9 @@ SIGNATURES = {
     "rk_mmoe_forward": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
                                        c_void_p, c_void_p, c_int32, POINTER(MmoeLayer), c_int32, POINTER(c_void_p),
                                        POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rk_ple_forward": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                      POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, c_int32, c_void_p, c_int64,
+                                      c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "rk_mlp_pack_weights": (ctypes.c_int, [POINTER(PackItem), c_int32, c_void_p]),
     "rk_mmoe_forward_train": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
                                              c_void_p, c_void_p, c_int32, POINTER(MmoeLayer), c_int32, POINTER(c_void_p),

@@ -500,6 +500,28 @@ def mmoe_fits(width: int, num_segments: int, num_experts: int, num_tasks: int, e
     return base + 16 * _pad64(expert_units[-1]) * 4 <= 160 * 1024
 
 
+def ple_fits(width: int, num_segments: int, num_levels: int, num_tasks: int, num_specific: int, num_shared: int,
+             expert_units, tower_units) -> bool:
+    """Whether rk_ple_forward takes this shape (the mirror of its envelope and LDS check, csrc/ple.hip):
+    width <= 256 in at most 16 segments, 1..4 levels, K <= 8, ms >= 0, mc >= 1, K ms + mc <= 64, 1..3 expert
+    layers, 0..3 tower layers, every hidden width <= 512, and the K + 1 level inputs (one when L == 1), the two
+    activation buffers, the gate logits and weights and the K + 1 mixtures within 160 KiB."""
+    expert_units, tower_units = list(expert_units), list(tower_units)
+    L, K, ms, mc = num_levels, num_tasks, num_specific, num_shared
+    if not (0 < width <= 256 and 0 < num_segments <= 16 and 1 <= L <= 4 and 0 < K <= 8 and ms >= 0 and mc >= 1
+            and K * ms + mc <= 64 and 1 <= len(expert_units) <= 3 and len(tower_units) <= 3):
+        return False
+    units = expert_units + tower_units
+    if min(units) <= 0 or max(units) > 512:
+        return False
+    H = expert_units[-1]
+    nx = K + 1 if L > 1 else 1
+    ldr = _pad64(max(width, H) if L > 1 else width) + 8  # rows padded by kMlpLdPad
+    ldh = max(64, max(_pad64(n) for n in units)) + 8
+    gate_cols = K * (ms + mc) + K * ms + mc
+    return 16 * (nx * ldr + 2 * ldh + 2 * (64 + 8) + gate_cols + (K + 1) * _pad64(H)) * 4 <= 160 * 1024
+
+
 class PackedWeights:
     """Packed weight images (rk_mlp_pack_weight, or the `pack` given), held weakly per weight
     tensor object and rebuilt when its storage or version changes (load_state_dict, .to(),

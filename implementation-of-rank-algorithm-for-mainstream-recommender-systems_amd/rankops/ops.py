@@ -2094,3 +2094,168 @@ def mmoe(x: torch.Tensor, experts, gates, towers=None):
         args[-1] = _lib.raw_stream(dev)
         check(_lib.load().rk_mmoe_forward(*args), "rk_mmoe_forward")
     return (mixed, gate_probs) if towers is None else (mixed, gate_probs, logits, probs)
+
+
+# ---------------------------------------------------------------- PLE (rk_ple_forward)
+
+# argument slots of rk_ple_forward patched per call (ple_forward_args)
+PLE_LOGITS_SLOT, PLE_PROBS_SLOT = 15, 16
+
+_PLE_TABLES = {}
+
+
+def ple_table(entries, device):
+    """The device table of rk_ple_forward: [(weight image or head weight, bias or None)…] in the order of
+    include/rankops.h, as a uint8 tensor holding rk_mmoe_layer structs.  Memoized on its bytes (the
+    addresses): a forward rebuilt over the same images reuses the table, so that building one inside a
+    hipGraph capture copies nothing."""
+    arr = (_lib.MmoeLayer * len(entries))()
+    for d, (w, b) in zip(arr, entries):
+        d.w, d.bias = w.data_ptr(), ptr(b)
+    raw = bytes(arr)
+    key = (str(device), raw)
+    hit = _PLE_TABLES.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("rankops.ple: the layer table of these weights is not on the device yet and cannot be "
+                               "uploaded inside a hipGraph capture; run the forward once before capturing")
+        hit = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+        if len(_PLE_TABLES) >= 64:
+            _PLE_TABLES.pop(next(iter(_PLE_TABLES)))
+        _PLE_TABLES[key] = hit
+    return hit
+
+
+def ple_forward_args(segs, width, batch, num_levels, num_tasks, num_specific, num_shared, expert_units, tower_units,
+                     entries, has_heads, device, *, logits=None, probs=None, reps=None, gates=None):
+    """The rk_ple_forward argument list (the stream last, None) and what it points into.  entries: the
+    layer table's (image, bias) pairs in the header's order (experts level-major, gates, towers, heads);
+    reps / gates: lists of L tensors (or None) for the per-level outputs.  logits [15], probs [16] and
+    the stream [-1] are the per-call slots of a cached forward."""
+    _lib.ensure_device(device)
+    arr = _as_seg_array(segs)
+    eu = (ctypes.c_int32 * max(1, len(expert_units)))(*expert_units)
+    tu = (ctypes.c_int32 * max(1, len(tower_units)))(*tower_units)
+    table = ple_table(entries, device)
+
+    def ptrs(ts):
+        return None if ts is None else (ctypes.c_void_p * num_levels)(*[ptr(t) for t in ts])
+    rp, gp = ptrs(reps), ptrs(gates)
+    args = [arr, len(arr), width, batch, num_levels, num_tasks, num_specific, num_shared, eu, len(expert_units),
+            tu if tower_units else None, len(tower_units), int(bool(has_heads)), table.data_ptr(), len(entries),
+            ptr(logits), ptr(probs), rp, gp, None]
+    return args, (arr, eu, tu, table, rp, gp, entries)
+
+
+def _ple_pair(wb, n, k, what):
+    w, b = wb
+    as_f32(w, f"{what} weight")
+    if w.dim() != 2 or w.stride(1) != 1 or (n is not None and w.shape[0] != n) or w.shape[1] != k:
+        raise ValueError(f"rankops.ple: {what} weight must be [{'n' if n is None else n}, {k}] with unit column "
+                         f"stride, got {tuple(w.shape)}")
+    if b is not None and (as_f32(b, f"{what} bias").dim() != 1 or b.shape[0] != w.shape[0] or not b.is_contiguous()):
+        raise ValueError(f"rankops.ple: {what} bias must be a contiguous [{w.shape[0]}] tensor")
+    return w.detach(), (b.detach() if b is not None else None)
+
+
+def ple(x: torch.Tensor, levels, towers=None, return_levels=False):
+    """Progressive layered extraction on rows x [B, width] (float32, unit column stride, any row stride
+    >= width), in one launch (rk_ple_forward).  levels[j] = (specific, shared, gates, shared_gate):
+
+        specific: K lists (one per task) of ms experts, shared: mc experts; an expert is a list of (W, b),
+                  Linear + ReLU each, b may be None; level 0 reads x, later levels the H-wide representations
+        gates: K (W [ms + mc, in], b or None); shared_gate: (W [K ms + mc, in], b or None), None at the last level
+
+    (the definition: rankops.PLE).  towers: K (hidden [(W, b)…], (w_out [1, ·], b_out)) or None.
+    Returns (logits [B, K], probs [B, K]) with towers, else the last level's (representations [B, K, H],
+    gates [B, K, ms + mc]).  return_levels=True appends (with towers) or returns instead (without) the list
+    over the levels of (representations [B, K + 1, H] — the tasks', then the shared one; [B, K, H] at the
+    last level —, task gates [B, K, ms + mc], shared gate [B, K ms + mc] or None)."""
+    as_f32(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"rankops.ple: x must be [B, width] with unit column stride, got {tuple(x.shape)}")
+    B, width = x.shape
+    dev = x.device
+    L = len(levels)
+    if L == 0:
+        raise ValueError("rankops.ple: at least one level")
+    K = len(levels[0][2])
+    ms = len(levels[0][0][0]) if K and len(levels[0][0]) else 0
+    mc = len(levels[0][1])
+    if K == 0 or mc == 0:
+        raise ValueError("rankops.ple: at least one task gate and one shared expert per level")
+    eu = [w.shape[0] for w, _ in levels[0][1][0]]
+    if len(eu) == 0:
+        raise ValueError("rankops.ple: an expert has no layer")
+    H, NE = eu[-1], K * ms + mc
+    experts, gate_entries = [], []
+    for j, (specific, shared, gates, shared_gate) in enumerate(levels):
+        k_in = width if j == 0 else H
+        if len(specific) != K or any(len(s) != ms for s in specific) or len(shared) != mc or len(gates) != K:
+            raise ValueError(f"rankops.ple: level {j} must hold {K} x {ms} task experts, {mc} shared experts and {K} gates")
+        if (shared_gate is None) != (j == L - 1):
+            raise ValueError("rankops.ple: every level but the last has a shared gate, the last has none")
+        stacks = [e for s in specific for e in s] + list(shared)
+        for s, layers in enumerate(stacks):
+            if len(layers) != len(eu):
+                raise ValueError(f"rankops.ple: level {j} expert {s} must have {len(eu)} layers")
+            k = k_in
+            for l, wb in enumerate(layers):
+                experts.append(_ple_pair(wb, eu[l], k, f"level {j} expert {s} layer {l}"))
+                k = eu[l]
+        for q, wb in enumerate(gates):
+            gate_entries.append(_ple_pair(wb, ms + mc, k_in, f"level {j} gate {q}"))
+        gate_entries.append(_ple_pair(shared_gate, NE, k_in, f"level {j} shared gate") if shared_gate is not None
+                            else None)
+    tu, tower_entries, heads = [], [], []
+    if towers is not None:
+        if len(towers) != K:
+            raise ValueError(f"rankops.ple: {K} gates need {K} towers, got {len(towers)}")
+        tu = [w.shape[0] for w, _ in towers[0][0]]
+        for k, (hidden, (w_out, b_out)) in enumerate(towers):
+            if len(hidden) != len(tu):
+                raise ValueError("rankops.ple: every tower must have the same layers")
+            kin = H
+            for l, wb in enumerate(hidden):
+                tower_entries.append(_ple_pair(wb, tu[l], kin, f"tower {k} layer {l}"))
+                kin = tu[l]
+            as_f32(w_out, f"tower {k} output weight")
+            as_f32(b_out, f"tower {k} output bias")
+            if w_out.numel() != kin or b_out.numel() != 1:
+                raise ValueError(f"rankops.ple: tower {k} output must be (w [1, {kin}], b [1])")
+            heads.append((w_out.detach().reshape(-1).contiguous(), b_out.detach().reshape(1)))
+    from . import common
+    if not common.ple_fits(width, (width + 127) // 128, L, K, ms, mc, eu, tu):
+        raise RuntimeError("rankops.ple: configuration outside rk_ple_forward's envelope (common.ple_fits)")
+    want = return_levels or towers is None
+    GT = ms + mc
+    reps = [torch.empty(B, K + (j < L - 1), H, device=dev, dtype=torch.float32) if want and (return_levels or j == L - 1)
+            else None for j in range(L)]
+    gate_out = [torch.empty(B, K * GT + (NE if j < L - 1 else 0), device=dev, dtype=torch.float32)
+                if want and (return_levels or j == L - 1) else None for j in range(L)]
+    logits = probs = None
+    if towers is not None:
+        logits = torch.empty(B, K, device=dev, dtype=torch.float32)
+        probs = torch.empty(B, K, device=dev, dtype=torch.float32)
+    if B > 0:
+        stream = _lib.raw_stream(dev)
+        packed = [wb for wb in experts + gate_entries + tower_entries if wb is not None]
+        images = [mlp_image(w.shape[0], w.shape[1], dev) for w, _ in packed]
+        pack_mlp_weights([(w, img) for (w, _), img in zip(packed, images)], stream)  # every image in one launch
+        it = iter(images)
+        zero = images[0]
+        entries = [(next(it), wb[1]) if wb is not None else (zero, None) for wb in experts + gate_entries + tower_entries]
+        entries += heads
+        segs = [dense_segment(x, min(128, width - c), c, c) for c in range(0, width, 128)]
+        args, _keep = ple_forward_args(segs, width, B, L, K, ms, mc, eu, tu, entries, towers is not None, dev,
+                                       logits=logits, probs=probs, reps=reps if want else None,
+                                       gates=gate_out if want else None)
+        args[-1] = stream
+        check(_lib.load().rk_ple_forward(*args), "rk_ple_forward")
+
+    def split(j):
+        g = gate_out[j]
+        return (reps[j], g[:, :K * GT].view(B, K, GT), g[:, K * GT:] if j < L - 1 else None)
+    if towers is None:
+        return [split(j) for j in range(L)] if return_levels else split(L - 1)[:2]
+    return (logits, probs, [split(j) for j in range(L)]) if return_levels else (logits, probs)

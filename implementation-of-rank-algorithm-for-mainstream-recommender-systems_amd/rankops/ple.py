@@ -1,0 +1,253 @@
+"""PLE (Progressive Layered Extraction, Tang et al., RecSys 2020) on the rankops engine: the third model
+of the reference README's multi-task list (ESMM, MMOE, PLE), one probability per task and row.
+
+The reference's README lists the model; it has no script for it, so the definition is this one, in the
+conventions of rankops.MMoE and the reference's DCN (algorithm/DCN/dcn.py):
+
+`PLE(vocab_dir, num_levels=2, num_specific_experts=2, num_shared_experts=2, expert_hidden_units=(256, 128),
+     tower_hidden_units=(64,), task_names=("read_comment", "like", "click_avatar"), dropout_rate=0.1, *,
+     vocab_sizes=None)`
+`forward(dense [B, 16], category {6 x [B]}) -> (probabilities [B, K], logits [B, K])`, column k = task_names[k].
+
+With L = num_levels, ms = num_specific_experts, mc = num_shared_experts, K tasks, x = cat[dense, embeddings]
+(width 50) and x_k^{-1} = x_s^{-1} = x, level j = 0 .. L - 1 is, in eval mode (Dropout the identity):
+
+    f_{k,i} = specific_experts[k][i](x_k^{j-1})   i < ms        f_{s,i} = shared_experts[i](x_s^{j-1})   i < mc
+    g_k = softmax(gates[k](x_k^{j-1}))       over ms + mc columns: c < ms -> f_{k,c}, else f_{s,c-ms}
+    x_k^j = sum_c g_k[c] * (that expert's output)                  c ascending
+    g_s = softmax(shared_gate(x_s^{j-1}))    over K ms + mc columns: k ms + i -> f_{k,i}, K ms + i -> f_{s,i}
+    x_s^j = sum_c g_s[c] * (that expert's output)                  c ascending
+
+(the last level has no shared_gate and no x_s), then logit_k = tower_outputs[k](towers[k](x_k^{L-1})) and
+prob_k = sigmoid(logit_k).  Every expert is Linear + ReLU (+ Dropout(p) when p > 0) per entry of
+expert_hidden_units; level 0's experts read width 50, later levels the last width H.  With L = 1 and
+ms = 0 this is MMoE with mc experts.
+
+Modules are created in this order (it fixes the seeded values and the state_dict keys): embeddings
+(DCNModel's ModuleDict exactly: a DCN or MMoE checkpoint's `embeddings.*` load, the same seed gives the same
+tables), levels = ModuleList of L modules, each creating specific_experts (ModuleList[K] of ModuleList[ms] of
+Sequential), shared_experts (ModuleList[mc]), gates (ModuleList[K] of Linear) and, except at the last level,
+shared_gate (Linear); then towers and tower_outputs as in MMoE.
+
+One launch, rk_ple_forward (csrc/ple.hip): the row gather, every level's gates, experts and mixtures, the
+towers and the heads; nothing between the gather and the logits reaches HBM.  Train mode raises
+NotImplementedError (training is later work), CPU tensors raise the engine's "ROCm GPU" error, and a
+configuration outside the kernel's envelope (common.ple_fits) is an error, not a fallback.
+
+`rankops.ple(x, levels, towers=None, return_levels=False)` is the same kernel on plain tensors (ops.ple); this
+module is callable so that `rankops.ple` is both the module and that function.
+"""
+from __future__ import annotations
+
+import sys
+import types
+
+import torch
+import torch.nn as nn
+
+from . import common, ops
+from .common import EngineModule, check_eval, table_rows
+from .mmoe import DEFAULT_TASKS, _stack
+
+
+class _LevelGates:
+    """The packed images of one level's gate weights (each gate reads its own representation, so they
+    cannot be stacked into one GEMM), all written by a single rk_mlp_pack_weights launch and cached on the
+    weights' versions as common.PackedWeights caches one image: a version bump rewrites the images in
+    place on the stream, unless a prepared forward pinned them (then the new version gets fresh images)."""
+
+    def __init__(self):
+        self._key = None
+        self._images = None
+        self._pinned = False
+
+    def __call__(self, weights, pin=False):
+        key = common._key(weights)
+        if key != self._key:
+            dev = weights[0].device
+            same_place = (self._key is not None and key[0] == self._key[0]
+                          and [k[0] for k in key[1:]] == [k[0] for k in self._key[1:]])
+            if not (same_place and not self._pinned and not torch.cuda.is_current_stream_capturing()):
+                self._images = [ops.mlp_image(w.shape[0], w.shape[1], dev) for w in weights]
+                self._pinned = False
+            ops.pack_mlp_weights([(w.detach(), img) for w, img in zip(weights, self._images)], ops._lib.raw_stream(dev))
+            self._key = key
+        if pin:
+            self._pinned = True
+        return self._images
+
+
+class _Level(nn.Module):
+    def __init__(self, in_dim, num_tasks, ms, mc, units, dropout_rate, last):
+        super().__init__()
+        self.specific_experts = nn.ModuleList(
+            nn.ModuleList(_stack(in_dim, units, dropout_rate)[0] for _ in range(ms)) for _ in range(num_tasks))
+        self.shared_experts = nn.ModuleList(_stack(in_dim, units, dropout_rate)[0] for _ in range(mc))
+        self.gates = nn.ModuleList(nn.Linear(in_dim, ms + mc) for _ in range(num_tasks))
+        if not last:
+            self.shared_gate = nn.Linear(in_dim, num_tasks * ms + mc)
+
+    def all_gates(self):
+        return list(self.gates) + ([self.shared_gate] if hasattr(self, "shared_gate") else [])
+
+    def stacks(self):
+        """The level's experts in the kernel's order: task k's at k ms + i, then the shared ones."""
+        return [e for task in self.specific_experts for e in task] + list(self.shared_experts)
+
+
+class PLE(EngineModule):
+    def __init__(self, vocab_dir, num_levels=2, num_specific_experts=2, num_shared_experts=2,
+                 expert_hidden_units=(256, 128), tower_hidden_units=(64,), task_names=DEFAULT_TASKS, dropout_rate=0.1,
+                 *, vocab_sizes=None):
+        super().__init__()
+        self.dropout_rate = float(dropout_rate)
+        expert_hidden_units = tuple(int(h) for h in expert_hidden_units)
+        tower_hidden_units = tuple(int(h) for h in tower_hidden_units)
+        task_names = tuple(task_names)
+        if int(num_levels) <= 0:
+            raise ValueError(f"num_levels must be positive, got {num_levels!r}")
+        if int(num_specific_experts) < 0 or int(num_shared_experts) <= 0:
+            raise ValueError(f"num_specific_experts must be >= 0 and num_shared_experts >= 1, got "
+                             f"{num_specific_experts!r}, {num_shared_experts!r}")
+        if len(expert_hidden_units) == 0 or any(h <= 0 for h in expert_hidden_units + tower_hidden_units):
+            raise ValueError(f"expert_hidden_units must be a non-empty list of positive widths and tower_hidden_units "
+                             f"a list of positive widths, got {expert_hidden_units!r}, {tower_hidden_units!r}")
+        if len(task_names) == 0 or len(set(task_names)) != len(task_names):
+            raise ValueError(f"task_names must be a non-empty list of distinct names, got {task_names!r}")
+        if not 0 <= dropout_rate < 1:
+            raise ValueError(f"dropout_rate must lie in [0, 1), got {dropout_rate!r}")
+        fields = ("userid", "feedid", "device", "authorid", "bgm_song_id", "bgm_singer_id", "manual_tag_list")
+        self.vocab_sizes = {f: table_rows(vocab_dir, f, vocab_sizes) for f in fields}
+        self.num_dense_features = 16
+        self.num_levels = int(num_levels)
+        self.num_specific_experts = int(num_specific_experts)
+        self.num_shared_experts = int(num_shared_experts)
+        self.task_names = task_names
+        self.expert_hidden_units = expert_hidden_units
+        self.tower_hidden_units = tower_hidden_units
+        self.embeddings = nn.ModuleDict({
+            "userid": nn.Embedding(self.vocab_sizes["userid"], 16),
+            "device": nn.Embedding(self.vocab_sizes["device"], 2),
+            "authorid": nn.Embedding(self.vocab_sizes["authorid"], 4),
+            "bgm_song_id": nn.Embedding(self.vocab_sizes["bgm_song_id"], 4),
+            "bgm_singer_id": nn.Embedding(self.vocab_sizes["bgm_singer_id"], 4),
+            "manual_tag_list": nn.Embedding(self.vocab_sizes["manual_tag_list"], 4),
+        })
+        self.input_dim = self.num_dense_features + 16 + 2 + 4 + 4 + 4 + 4
+        K, H = len(task_names), expert_hidden_units[-1]
+        self.levels = nn.ModuleList(
+            _Level(self.input_dim if j == 0 else H, K, self.num_specific_experts, self.num_shared_experts,
+                   expert_hidden_units, dropout_rate, j == self.num_levels - 1) for j in range(self.num_levels))
+        self.towers = nn.ModuleList()
+        last = H
+        for _ in range(K):
+            seq, last = _stack(H, tower_hidden_units, dropout_rate)
+            self.towers.append(seq)
+        self.tower_outputs = nn.ModuleList(nn.Linear(last, 1) for _ in range(K))
+        self._gate_images = [_LevelGates() for _ in range(self.num_levels)]
+
+    def fits(self) -> bool:
+        return common.ple_fits(self.input_dim, 1 + len(self.embeddings), self.num_levels, len(self.task_names),
+                               self.num_specific_experts, self.num_shared_experts, self.expert_hidden_units,
+                               self.tower_hidden_units)
+
+    def _indices(self, category):
+        names = list(self.embeddings)
+        if not isinstance(category, dict):
+            raise TypeError(f"PLE.forward: category must be a dict of index tensors, got {type(category).__name__}")
+        missing = [c for c in names if c not in category]
+        if missing:
+            raise KeyError(f"PLE.forward: category features missing: {missing}")
+        idx = [ops.as_index(category[n], f"category[{n!r}]") for n in names]
+        return names, idx
+
+    @staticmethod
+    def _linears(seq):
+        return [m for m in seq if isinstance(m, nn.Linear)]
+
+    def _build(self, dense, names, idx, pin=False):
+        """The forward's one rk_ple_forward launch over these inputs as a common.Bound (pin: prepare()'s
+        pinned weight images); the outputs are patched in per call."""
+        if not self.fits():
+            raise RuntimeError("PLE: configuration outside rk_ple_forward's envelope (common.ple_fits)")
+        B, dev = dense.shape[0], dense.device
+        if any(t.dim() != 1 or t.shape[0] != B for t in idx):
+            raise ValueError("PLE.forward: every category feature must be a 1-D tensor of the batch's length")
+        image = common.PACKED.pin if pin else common.PACKED
+        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
+        col = self.num_dense_features
+        for n, i in zip(names, idx):
+            emb = self.embeddings[n]
+            segs.append(ops.table_segment(emb.weight, i, col))
+            col += emb.embedding_dim
+        K = len(self.task_names)
+        experts, gates = [], []
+        for level, packer in zip(self.levels, self._gate_images):
+            experts += [(image(l.weight), l.bias) for seq in level.stacks() for l in self._linears(seq)]
+            lin = level.all_gates()
+            images = packer([g.weight for g in lin], pin)  # the level's K (+ 1) gate images, one pack launch
+            gates += [(img, g.bias) for img, g in zip(images, lin)]
+            if len(lin) == K:  # the last level: the shared gate's slot is never read
+                gates.append((images[0], None))
+        towers = [(image(l.weight), l.bias) for seq in self.towers for l in self._linears(seq)]
+        heads = [(o.weight, o.bias) for o in self.tower_outputs]
+        entries = experts + gates + towers + heads
+        args, keep = ops.ple_forward_args(segs, self.input_dim, B, self.num_levels, K, self.num_specific_experts,
+                                          self.num_shared_experts, self.expert_hidden_units, self.tower_hidden_units,
+                                          entries, True, dev)
+        return common.bound([("rk_ple_forward", args)], B, keep, self._patch)
+
+    @staticmethod
+    def _patch(_ep, args, out):
+        prob, logit = out
+        args[ops.PLE_LOGITS_SLOT], args[ops.PLE_PROBS_SLOT] = logit.data_ptr(), prob.data_ptr()
+
+    @staticmethod
+    def _run(bound, out, stream):
+        bound.patch(out)
+        common.run_launches(bound.launches, stream)
+
+    def _outputs(self, B, dev):
+        return common.empty_rows(dev, 2, (B, len(self.task_names)))
+
+    def prepare(self, dense, category):
+        """An eval forward bound to these input tensors (as MMoE.prepare): returns `run()` that recomputes
+        the whole forward from the current contents of the inputs with one rk_ple_forward launch and returns
+        the same (probabilities, logits) tensors each time.  Binds the current weights and pins their packed
+        images: prepare again after changing them."""
+        if self.training:
+            raise RuntimeError("PLE.prepare: eval mode only (call .eval() first)")
+        dense = ops.as_f32(dense, "dense")
+        names = list(self.embeddings)
+        idx = [ops.bound_index(category[n], f"category[{n!r}]") for n in names]
+        if dense.shape[0] == 0:
+            raise ValueError("PLE.prepare: empty batch")
+        return common.prepared(self, self._build(dense, names, idx, pin=True), dense.device, (dense, category))
+
+    def forward(self, dense, category):
+        check_eval(self)  # training is later work
+        dense = ops.as_f32(dense, "dense")
+        if dense.dim() != 2 or dense.shape[1] < self.num_dense_features:
+            raise ValueError(f"PLE.forward: dense must be [B, {self.num_dense_features}], got {tuple(dense.shape)}")
+        names, idx = self._indices(category)
+        B, dev = dense.shape[0], dense.device
+        if B == 0:
+            return common.empty_rows(dev, 2, (0, len(self.task_names)))
+        stream = ops._lib.raw_stream(dev)
+        if all(t is category[n] for t, n in zip(idx, names)):  # no converted copies: addresses are the caller's
+            bound = common.EagerCalls.lookup(self, [dense] + idx, stream, lambda: self._build(dense, names, idx))
+        else:
+            bound = self._build(dense, names, idx)
+        out = self._outputs(B, dev)
+        self._run(bound, out, stream)
+        return out
+
+
+class _CallableModule(types.ModuleType):
+    """`rankops.ple(x, levels, towers=None, return_levels=False)`: the op-level function under the module's name."""
+
+    def __call__(self, *args, **kwargs):
+        return ops.ple(*args, **kwargs)
+
+
+sys.modules[__name__].__class__ = _CallableModule

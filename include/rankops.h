@@ -55,6 +55,8 @@
  *   rk_mmoe_forward    MMoE (multi-gate mixture of experts) eval forward in one launch: row gather,
  *                      gates + softmax, experts with the mix in their last epilogue, towers, heads
  *                      (the reference lists the model, its script is not in the snapshot)
+ *   rk_ple_forward     PLE (progressive layered extraction) eval forward in one launch: row gather, L
+ *                      levels of task / shared experts and gates, towers, heads
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
  *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
  *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
@@ -837,6 +839,43 @@ int rk_mmoe_head_backward(int64_t batch, int32_t num_tasks, int32_t n, int32_t p
                           const float* dprobs, const float* probs, const float* const* head_w, const float* t,
                           float mask_scale, float* g_out, int32_t ld_g, float* dt, int32_t accumulate,
                           void* stream);
+
+/* ---- PLE: progressive layered extraction (Tang et al., RecSys 2020), eval forward ---- */
+/* The whole PLE eval forward in one launch.  L = num_levels, K = num_tasks, ms = num_specific, mc =
+ * num_shared, NE = K ms + mc stacks per level (task k's at k ms + i, the shared at K ms + i), De =
+ * expert_depth, Dt = tower_depth, H = expert_units[De - 1].  Per row b, with x = the `width` columns
+ * gathered from segs (as rk_mmoe_forward) and x_k^{-1} = x_s^{-1} = x, level j = 0 .. L - 1 computes
+ *   f_s   = expert_{j,s}(its owner's input)       Linear + ReLU per expert_units entry; stack k ms + i reads
+ *                                                 x_k^{j-1}, stack K ms + i reads x_s^{j-1}
+ *   g_k   = softmax(gate_{j,k}(x_k^{j-1}))        ms + mc columns: c < ms -> f_{k ms + c}, else f_{K ms + c - ms}
+ *   g_s   = softmax(gate_{j,K}(x_s^{j-1}))        NE columns: c -> f_c (not at the last level)
+ *   x_k^j = sum_c g_k[c] f,  x_s^j = sum_c g_s[c] f      c ascending, FP32, no atomics: two launches give
+ *                                                 the same bits
+ * then logit_k = towers[k](x_k^{L-1}) . head_w[k] + head_b[k][0] (Linear + ReLU per tower_units entry),
+ * prob_k = sigmoid(logit_k).
+ * table: a DEVICE array of table_len rk_mmoe_layer from which only w and bias are read (every width
+ * comes from expert_units / tower_units), w = the rk_mlp_pack_weight image, bias [n] or NULL:
+ *   [(j NE + s) De + l]              expert s of level j, layer l
+ *   [L NE De + j (K + 1) + q]        level j's gate q (q == K: the shared gate; unused at the last level)
+ *   [L NE De + L (K + 1) + k Dt + l] tower k, layer l
+ *   [.. + K Dt + k]                  head k: w = the plain weight [last width], bias [1], both required
+ * so table_len = L NE De + L (K + 1) + K Dt + K (without heads: L NE De + L (K + 1)).  The table and everything it points to is the caller's
+ * to keep valid and 16-B aligned; the host checks its length and address only.
+ * Outputs, each may be NULL: logits, probs [batch, K] (need has_heads != 0); level_reps[j]
+ * [batch, K + 1, H] (x_0 .. x_{K-1}, x_s; [batch, K, H] at the last level); level_gates[j]
+ * [batch, K (ms + mc) + NE] (g_0 .. g_{K-1}, g_s; [batch, K (ms + mc)] at the last level); level_reps /
+ * level_gates are host arrays of L pointers or NULL.  has_heads == 0 (then tower_depth = 0) stops after
+ * the last level.
+ * Envelope: nseg <= 16 segments of at most 255 columns each, width <= 256, L <= 4, K <= 8, ms >= 0,
+ * mc >= 1, NE <= 64, 1 <= De <= 3, 0 <= Dt <= 3, every n <= 512, and the level inputs, activation
+ * buffers, gates and K + 1 mixtures within 160 KiB of LDS (else RK_ERR_UNSUPPORTED); NULL or shape
+ * errors and batch < 0: RK_ERR_INVALID; both before any launch.  batch == 0: RK_OK, no launch.
+ * Out-of-range ids read zero rows and raise RK_FLAG_INDEX_OOB.                                     */
+int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
+                   int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
+                   int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
+                   const rk_mmoe_layer* table, int64_t table_len, float* logits, float* probs,
+                   float* const* level_reps, float* const* level_gates, void* stream);
 
 /* ---- xDeepFM training: the CIN's train forward, data backward and weight gradient ---- */
 /* rk_cin_forward that also writes every layer's feature maps for the backward:
