@@ -6,8 +6,8 @@
 // din.py:272-285,312-316; bst.py:203-214,245-247; deepcrossing.py:25-42,157-162.
 #include <cstdlib>
 
-#include "mlp_core.h"
 #include "mlp_stream.h"
+#include "mtl_core.h"
 
 namespace rk {
 
@@ -74,12 +74,9 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_kernel(MlpArgs a) {
 // uncovered columns and out-of-range rows are zero, the latter flagged) into the layer-0 buffer, so
 // the [M, width] row never goes through HBM.  DeepCrossing's forward (deepcrossing.py:146-163): the
 // residual units and output_layer run on mlp_rows as in mlp_kernel.
-constexpr int kMgSegs = 16;
-constexpr int kMgCols = 256;
 struct MlpGatherArgs {
   MlpArgs m;
-  rk_segment segs[kMgSegs];
-  uint8_t col_seg[kMgCols], col_off[kMgCols];  // 255: no segment
+  RowMap map;
   uint32_t* flags;
 };
 static_assert(sizeof(MlpGatherArgs) <= 4096, "kernel arguments beyond 4 KiB");
@@ -95,17 +92,17 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_gather_kernel(MlpGatherArgs a
   const bool live = wave < rows;
   const int64_t b = m0 + wave;
   // the row's index in every column's segment first (one dependent round trip), the values after
-  float v[kMgCols / 64];
-  int64_t r[kMgCols / 64];
-  int sg[kMgCols / 64];
+  float v[kRowCols / 64];
+  int64_t r[kRowCols / 64];
+  int sg[kRowCols / 64];
   auto stage_issue = [&]() {
 #pragma unroll
-    for (int i = 0; i < kMgCols / 64; ++i) {
+    for (int i = 0; i < kRowCols / 64; ++i) {
       const int c = lane + 64 * i;
-      sg[i] = live && c < a.m.K0 ? a.col_seg[c] : 255;
+      sg[i] = live && c < a.m.K0 ? a.map.col_seg[c] : 255;
       r[i] = b;
       if (sg[i] != 255) {
-        const rk_segment& g = a.segs[sg[i]];
+        const rk_segment& g = a.map.segs[sg[i]];
         if (g.idx) {
           r[i] = g.idx[b * g.idx_stride];
           if (r[i] < 0 || r[i] >= g.rows) {
@@ -116,17 +113,17 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_gather_kernel(MlpGatherArgs a
       }
     }
 #pragma unroll
-    for (int i = 0; i < kMgCols / 64; ++i) {
+    for (int i = 0; i < kRowCols / 64; ++i) {
       v[i] = 0.f;
       if (sg[i] != 255 && r[i] >= 0) {
-        const rk_segment& g = a.segs[sg[i]];
-        v[i] = g.src[r[i] * g.src_ld + a.col_off[lane + 64 * i]];
+        const rk_segment& g = a.map.segs[sg[i]];
+        v[i] = g.src[r[i] * g.src_ld + a.map.col_off[lane + 64 * i]];
       }
     }
   };
   auto stage_store = [&]() {
 #pragma unroll
-    for (int i = 0; i < kMgCols / 64; ++i) {
+    for (int i = 0; i < kRowCols / 64; ++i) {
       const int c = lane + 64 * i;
       if (c < K0p) buf0[wave * a.m.ld0 + c] = v[i];
     }
@@ -163,14 +160,14 @@ __global__ __launch_bounds__(kMlpThreads) void dc_forward_kernel(MlpGatherArgs a
   // by a cross-lane read and loads its value — index -> value, one dependent round trip after the
   // argument reads instead of map -> descriptor -> index -> value
   const int c = lane;  // K0 <= 64: one column per lane
-  const int64_t* ip = a.segs[0].idx;
-  int64_t ist = a.segs[0].idx_stride, irows = a.segs[0].rows;
+  const int64_t* ip = a.map.segs[0].idx;
+  int64_t ist = a.map.segs[0].idx_stride, irows = a.map.segs[0].rows;
 #pragma unroll
-  for (int t = 1; t < kMgSegs; ++t)
+  for (int t = 1; t < kRowSegs; ++t)
     if (lane == t) {
-      ip = a.segs[t].idx;
-      ist = a.segs[t].idx_stride;
-      irows = a.segs[t].rows;
+      ip = a.map.segs[t].idx;
+      ist = a.map.segs[t].idx_stride;
+      irows = a.map.segs[t].rows;
     }
   int64_t mine = b;
   if (live && ip) {  // lanes past the segment count read a zeroed slot (idx null): nothing
@@ -180,12 +177,12 @@ __global__ __launch_bounds__(kMlpThreads) void dc_forward_kernel(MlpGatherArgs a
       mine = -1;
     }
   }
-  const int sg = live && c < a.m.K0 ? a.col_seg[c] : 255;
+  const int sg = live && c < a.m.K0 ? a.map.col_seg[c] : 255;
   const float* csrc = nullptr;
   int64_t cld = 0;
   if (sg != 255) {
-    csrc = a.segs[sg].src + a.col_off[c];
-    cld = a.segs[sg].src_ld;
+    csrc = a.map.segs[sg].src + a.map.col_off[c];
+    cld = a.map.segs[sg].src_ld;
   }
   const int64_t r = __shfl(mine, sg != 255 ? sg : 0, kWave);
   // every weight fragment of this wave's tiles (fragment-major packed images, mlp_core.h wfrag)
@@ -596,6 +593,26 @@ __global__ void mlp_pack_kernel(const float* __restrict__ w, int64_t ldw, int n,
   out[i] = (r < n && col < k) ? w[(int64_t)r * ldw + col] : 0.f;
 }
 
+// The same image of many weights in one launch (rk_mlp_pack_weights): grid (256-element blocks of the
+// largest image, weight).
+constexpr int kPackMaxItems = 96;
+struct PackItems {
+  rk_pack_item item[kPackMaxItems];
+};
+static_assert(sizeof(PackItems) <= 4096, "kernel arguments beyond 4 KiB");
+
+__global__ __launch_bounds__(256) void mlp_pack_many_kernel(PackItems p) {
+  const rk_pack_item& it = p.item[blockIdx.y];
+  const int np = pad64(it.n), kp = pad64(it.k);
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)np * kp) return;
+  const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+  const int64_t blk = i >> 8;
+  const int kch = kp / 16;
+  const int t = (int)(blk / kch), c = (int)(blk % kch);
+  const int r = 16 * t + (lane & 15), col = 16 * c + 4 * (lane >> 4) + e;
+  it.out[i] = (r < it.n && col < it.k) ? it.w[(int64_t)r * it.ldw + col] : 0.f;
+}
 
 int stream_plan_for(const rk_mlp_layer* layers, int nlayers, int K0) {
   if (const char* e = getenv("RANKOPS_MLP_STREAM"))
@@ -685,6 +702,25 @@ RK_API int rk_mlp_pack_weight(const float* w, int64_t ldw, int32_t n, int32_t k,
   const int64_t total = (int64_t)np * kp;
   mlp_pack_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, ldw, n, k, np, kp, out);
   return check_launch("rk_mlp_pack_weight");
+}
+
+RK_API int rk_mlp_pack_weights(const rk_pack_item* items, int32_t count, void* stream) {
+  if (count < 0 || (count > 0 && !items)) return fail(RK_ERR_INVALID, "rk_mlp_pack_weights: bad arguments");
+  for (int i = 0; i < count; ++i)
+    if (!items[i].w || !items[i].out || items[i].n <= 0 || items[i].k <= 0 || items[i].ldw < items[i].k ||
+        !aligned16(items[i].out))
+      return fail(RK_ERR_INVALID, "rk_mlp_pack_weights: item %d: null / misaligned pointer or bad shape", i);
+  for (int i0 = 0; i0 < count; i0 += kPackMaxItems) {
+    PackItems p = {};
+    const int c = std::min(kPackMaxItems, count - i0);
+    int64_t most = 0;
+    for (int i = 0; i < c; ++i) {
+      p.item[i] = items[i0 + i];
+      most = std::max<int64_t>(most, (int64_t)pad64(p.item[i].n) * pad64(p.item[i].k));
+    }
+    mlp_pack_many_kernel<<<dim3((unsigned)((most + 255) / 256), (unsigned)c), 256, 0, (hipStream_t)stream>>>(p);
+  }
+  return check_launch("rk_mlp_pack_weights");
 }
 
 // The streamed tail's epilogue-parameter image ([column][8] resolved floats: mlp_stream.h
@@ -802,9 +838,9 @@ RK_API int rk_mlp_forward(const float* x, int64_t ldx, int64_t M, int32_t K0, co
 
 RK_API int rk_mlp_forward_gather(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
                                  const rk_mlp_layer* layers, int32_t nlayers, const rk_epilogue* head, void* stream) {
-  if (!segs || nseg <= 0 || nseg > kMgSegs || width <= 0 || width > kMgCols || batch < 0 || !head || !head->head_w)
+  if (!segs || nseg <= 0 || nseg > kRowSegs || width <= 0 || width > kRowCols || batch < 0 || !head || !head->head_w)
     return fail(RK_ERR_UNSUPPORTED, "rk_mlp_forward_gather: %d segments (<= %d) over %d columns (<= %d), with a head",
-                nseg, kMgSegs, width, kMgCols);
+                nseg, kRowSegs, width, kRowCols);
   MlpGatherArgs g = {};
   MlpArgs& a = g.m;
   a.head = *head;
@@ -822,21 +858,7 @@ RK_API int rk_mlp_forward_gather(const rk_segment* segs, int32_t nseg, int32_t w
   if (shm > 160 * 1024) return fail(RK_ERR_UNSUPPORTED, "rk_mlp_forward_gather: widths need %zu B of LDS", shm);
   a.M = batch;
   a.K0 = width;
-  for (int c = 0; c < kMgCols; ++c) {
-    g.col_seg[c] = 255;
-    g.col_off[c] = 0;
-  }
-  for (int i = 0; i < nseg; ++i) {
-    const rk_segment& sg = segs[i];
-    if (!sg.src || sg.dim <= 0 || sg.out_col < 0 || sg.out_col + sg.dim > width || (sg.idx && sg.rows <= 0) ||
-        sg.dim > 255)
-      return fail(RK_ERR_INVALID, "rk_mlp_forward_gather: segment %d invalid", i);
-    g.segs[i] = sg;
-    for (int c = sg.out_col; c < sg.out_col + sg.dim; ++c) {  // the last covering segment wins
-      g.col_seg[c] = (uint8_t)i;
-      g.col_off[c] = (uint8_t)(c - sg.out_col);
-    }
-  }
+  if (int e = row_map_fill(g.map, segs, nseg, width, "rk_mlp_forward_gather")) return e;
   g.flags = device_flags();
   if (!g.flags) return fail(RK_ERR_RUNTIME, "rk_mlp_forward_gather: device not initialised (rk_init)");
   if (batch == 0) return RK_OK;

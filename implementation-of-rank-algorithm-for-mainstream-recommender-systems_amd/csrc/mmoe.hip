@@ -30,13 +30,15 @@
 // LDS (floats): xs [16][pad64(width) + 8], ha and hb [16][max pad64(hidden) + 8], gs [16][64 + 8] (the
 // gate logits), gt [64][16] (the gate weights, gt[(e K + k) 16 + row]), mt [T][pad64(H)][16]
 // (mt[(i pad64(H) + n) 16 + row]).
-#include "mlp_core.h"
+//
+// The row's column map, the per-layer dispatch (mtl_prepare, mtl_layer, mtl_layer_tiles with its
+// TileSink), lane_now, close_layer and the mix into / walk over mt (mtl_mix, mtl_unmix) are
+// mtl_core.h's, shared with ple.hip.
+#include "mtl_core.h"
 #include "train_common.h"
 
 namespace rk {
 
-constexpr int kMmSegs = 16;
-constexpr int kMmCols = 256;
 constexpr int kMmMaxExperts = 16;
 constexpr int kMmMaxTasks = 8;
 constexpr int kMmMaxGates = 64;  // num_tasks * num_experts: the gate GEMM's columns (4 tiles)
@@ -45,8 +47,7 @@ constexpr int kMmLayers = (kMmMaxExperts + kMmMaxTasks) * kMmMaxDepth;
 constexpr int kMmLdG = kMmMaxGates + kMlpLdPad;
 
 struct MmoeArgs {
-  rk_segment segs[kMmSegs];
-  uint8_t col_seg[kMmCols], col_off[kMmCols];  // 255: no segment
+  RowMap map;
   rk_mmoe_layer layers[kMmLayers];             // expert e layer l at [e De + l], tower k layer l at [E De + k Dt + l]
   rk_mmoe_layer gate;                          // the stacked gates [K E, width]
   const float* head_w[kMmMaxTasks];
@@ -95,56 +96,6 @@ __device__ __forceinline__ rk_mlp_layer mm_view(const rk_mmoe_layer& d, int K) {
   return L;
 }
 
-// mlp_layer's sink of an expert's last layer: the wave's finished tiles stay in registers.
-// (One type per tile count: with one object for both, the compiler merged the two layer variants'
-// epilogue stores behind a runtime index and kept the tiles in scratch.)
-template <int TPW>
-struct TileSink {
-  f32x4_t z[TPW];
-  __device__ __forceinline__ void take(int j, int r, int row, float v) { z[j][r] = v; }
-};
-
-// mlp_rows' per-layer dispatch: wave w owns column tiles w and w + 16; a wave without a tile takes
-// part in the active waves' lockstep barriers.
-__device__ __forceinline__ void mm_prepare(LayerPipe& pipe, const rk_mlp_layer& L, int K, int wave, int lane) {
-  const int nt = pad64(L.n) / 16, kch = pad64(K) / 16;
-  if (wave + kMlpWaves < nt)
-    pipe.prepare<2, 4>(L, kch, wave, lane);
-  else if (wave < nt)
-    pipe.prepare<1, 8>(L, kch, wave, lane);
-}
-
-__device__ __forceinline__ void mm_layer(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin, float* out,
-                                         int ldout, int Kp, int wave, int lane) {
-  const int ntiles = pad64(L.n) / 16;
-  if (wave + kMlpWaves < ntiles) {
-    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
-  } else if (wave < ntiles) {
-    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
-  } else {
-    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
-  }
-}
-
-// The same with the output tiles left in z (zero for a tile the wave does not own), nothing in LDS.
-__device__ __forceinline__ void mm_layer_tiles(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin,
-                                               int Kp, int wave, int lane, f32x4_t (&z)[2]) {
-  const int ntiles = pad64(L.n) / 16;
-  z[0] = z[1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  if (wave + kMlpWaves < ntiles) {
-    TileSink<2> f;
-    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
-    z[0] = f.z[0];
-    z[1] = f.z[1];
-  } else if (wave < ntiles) {
-    TileSink<1> f;
-    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
-    z[0] = f.z[0];
-  } else {
-    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
-  }
-}
-
 // A finished hidden layer in LDS (16 rows of n columns, after the layer's barrier) for the train
 // forward: dropout applied in place (the next layer reads it), the result stored to its column block
 // of the layer's HBM buffer, zeros up to the pitch.  All threads; the caller's barrier follows.
@@ -182,17 +133,19 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
   const bool live = wave < rows;
   const int64_t b = m0 + wave;
 
-  // 1. the row gather (mlp_gather_kernel's stage): indices first, the values after
-  float v[kMmCols / 64];
-  int64_t r[kMmCols / 64];
-  int sg[kMmCols / 64];
+  // 1. the row gather (mlp_gather_kernel's stage): indices first, the values after.  (Written out in each
+  // of the three kernels: as one shared function it changed mlp_gather_kernel's instruction stream and
+  // made mmoe_kernel slower at large batches.)
+  float v[kRowCols / 64];
+  int64_t r[kRowCols / 64];
+  int sg[kRowCols / 64];
 #pragma unroll
-  for (int i = 0; i < kMmCols / 64; ++i) {
+  for (int i = 0; i < kRowCols / 64; ++i) {
     const int c = lane + 64 * i;
-    sg[i] = live && c < width ? a.col_seg[c] : 255;
+    sg[i] = live && c < width ? a.map.col_seg[c] : 255;
     r[i] = b;
     if (sg[i] != 255) {
-      const rk_segment& g = a.segs[sg[i]];
+      const rk_segment& g = a.map.segs[sg[i]];
       if (g.idx) {
         r[i] = g.idx[b * g.idx_stride];
         if (r[i] < 0 || r[i] >= g.rows) {
@@ -203,18 +156,18 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
     }
   }
 #pragma unroll
-  for (int i = 0; i < kMmCols / 64; ++i) {
+  for (int i = 0; i < kRowCols / 64; ++i) {
     v[i] = 0.f;
     if (sg[i] != 255 && r[i] >= 0) {
-      const rk_segment& g = a.segs[sg[i]];
-      v[i] = g.src[r[i] * g.src_ld + a.col_off[lane + 64 * i]];
+      const rk_segment& g = a.map.segs[sg[i]];
+      v[i] = g.src[r[i] * g.src_ld + a.map.col_off[lane + 64 * i]];
     }
   }
   uint64_t stream = 0;
   if constexpr (TRAIN) {
     if (a.threshold) stream = (uint64_t)*a.slot;
 #pragma unroll
-    for (int i = 0; i < kMmCols / 64; ++i) {
+    for (int i = 0; i < kRowCols / 64; ++i) {
       const int c = lane + 64 * i;
       if (live && c < a.ldx_out) a.x_out[b * a.ldx_out + c] = v[i];  // (zeros past the width)
     }
@@ -226,32 +179,20 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
   auto tower = [&](int k, int l) {
     return mm_view(a.layers[E * De + k * Dt + l], l ? a.layers[E * De + k * Dt + l - 1].n : H);
   };
-  // The lane index behind an empty asm, taken once per layer: what a layer derives from it (LDS and
-  // weight addresses, output offsets) is then computed where it is used.  Derived from `lane` itself
-  // the compiler hoists all of it out of the expert / task loops and spills it around every layer.
-  auto lane_now = [&]() {
-    int x = lane;
-    asm volatile("" : "+v"(x));
-    return x;
-  };
-  auto close_layer = [&]() {
-    mlp_lds_barrier();
-    __builtin_amdgcn_s_setprio(0);
-  };
 
   // 2. the gates: one GEMM over the K stacked gate weights, then softmax over e per (row, task)
   const rk_mlp_layer LG = mm_view(a.gate, width);
-  mm_prepare(pipe, LG, width, wave, lane);
+  mtl_prepare(pipe, LG, width, wave, lane);
 #pragma unroll
-  for (int i = 0; i < kMmCols / 64; ++i) {
+  for (int i = 0; i < kRowCols / 64; ++i) {
     const int c = lane + 64 * i;
     if (c < K0p) xs[wave * a.ldx + c] = v[i];  // dead rows and pad columns stage zeros
   }
   mlp_lds_barrier();
-  mm_layer(pipe, LG, xs, a.ldx, gs, kMmLdG, K0p, wave, lane);
+  mtl_layer(pipe, LG, xs, a.ldx, gs, kMmLdG, K0p, wave, lane);
   {
     const rk_mlp_layer L0 = expert(0, 0);
-    mm_prepare(pipe, L0, width, wave, lane);
+    mtl_prepare(pipe, L0, width, wave, lane);
   }
   close_layer();
   if (tid < kMlpRows * K) {
@@ -273,7 +214,7 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
   }
   mlp_lds_barrier();
 
-  const int Hp = pad64(H), ntH = Hp / 16;
+  const int Hp = pad64(H);
   for (int k0 = 0; k0 < K; k0 += a.T) {
     const int kg = min(a.T, K - k0);
     const bool more = k0 + a.T < K;  // another pass over the experts follows
@@ -281,15 +222,15 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
     // 3. the experts; the mix after the last layer's epilogue
     for (int e = 0; e < E; ++e) {
       for (int l = 0; l < De; ++l) {
-        const int ln = lane_now();
+        const int ln = lane_now(lane);
         const rk_mlp_layer L = expert(e, l);
         const int Kp = pad64(l ? a.layers[e * De + l - 1].n : width);
         const float* in = l == 0 ? xs : (l & 1) ? ha : hb;
         float* out = (l & 1) ? hb : ha;
         if (l + 1 < De) {
-          mm_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
+          mtl_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
           const rk_mlp_layer N = expert(e, l + 1);
-          mm_prepare(pipe, N, L.n, wave, ln);
+          mtl_prepare(pipe, N, L.n, wave, ln);
           if constexpr (TRAIN) {
             close_layer();
             mm_train_store(a, out, L.n, e * De + l, a.eact[l] + e * a.pitch_e[l], (int64_t)E * a.pitch_e[l],
@@ -300,15 +241,15 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
           // of f_e run after its barrier; the register epilogue with both went to scratch)
           f32x4_t z[2];
           if constexpr (TRAIN)
-            mm_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
+            mtl_layer(pipe, L, in, l == 0 ? a.ldx : a.ldh, out, a.ldh, Kp, wave, ln);
           else
-            mm_layer_tiles(pipe, L, in, l == 0 ? a.ldx : a.ldh, Kp, wave, ln, z);
+            mtl_layer_tiles(pipe, L, in, l == 0 ? a.ldx : a.ldh, Kp, wave, ln, z);
           if (e + 1 < E || (more && !(a.has_head && Dt > 0))) {
             const rk_mlp_layer N = expert(e + 1 < E ? e + 1 : 0, 0);
-            mm_prepare(pipe, N, width, wave, ln);
+            mtl_prepare(pipe, N, width, wave, ln);
           } else if (a.has_head && Dt > 0) {
             const rk_mlp_layer N = tower(k0, 0);
-            mm_prepare(pipe, N, H, wave, ln);
+            mtl_prepare(pipe, N, H, wave, ln);
           }
           const int q4 = (ln >> 4) * 4;  // the lane's first row
           if constexpr (TRAIN) {
@@ -323,21 +264,7 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
               for (int q = 0; q < 4; ++q) z[j][q] = n < Hp ? out[(q4 + q) * a.ldh + n] : 0.f;
             }
           }
-          for (int i = 0; i < kg; ++i) {
-            const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(gt + (e * K + k0 + i) * kMlpRows + q4);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const int t = wave + kMlpWaves * j;
-              if (t < ntH) {
-                f32x4_t* const mp = reinterpret_cast<f32x4_t*>(mt + (i * Hp + 16 * t + (ln & 15)) * kMlpRows + q4);
-                f32x4_t m = {0.f, 0.f, 0.f, 0.f};
-                if (e) m = *mp;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) m[q] = __builtin_fmaf(gv[q], z[j][q], m[q]);
-                *mp = m;
-              }
-            }
-          }
+          for (int i = 0; i < kg; ++i) mtl_mix(mt, gt, i, e * K + k0 + i, e == 0, z, Hp, wave, ln);
         }
         close_layer();
       }
@@ -346,44 +273,33 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
     // 4. per task: the mixture to LDS row-major (and `mixed`), the tower, the head
     for (int kk = 0; kk < kg; ++kk) {
       const int k = k0 + kk;
-      const int lm = lane_now();
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int t = wave + kMlpWaves * j;
-        if (t < ntH) {
-          const int n = 16 * t + (lm & 15);
-          const f32x4_t mv = *reinterpret_cast<const f32x4_t*>(mt + (kk * Hp + n) * kMlpRows + (lm >> 4) * 4);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int row = (lm >> 4) * 4 + q;
-            if (a.has_head) ha[row * a.ldh + n] = mv[q];  // pad columns hold zeros: the tower's zero K pad
-            if constexpr (TRAIN) {
-              if (a.mixed && n < a.pitch_m && row < rows)
-                a.mixed[((m0 + row) * K + k) * a.pitch_m + n] = n < H ? mv[q] : 0.f;
-            } else {
-              if (a.mixed && n < H && row < rows) a.mixed[((m0 + row) * K + k) * H + n] = mv[q];
-            }
-          }
+      const int lm = lane_now(lane);
+      mtl_unmix(mt, kk, Hp, wave, lm, [&](int row, int n, float m) {
+        if (a.has_head) ha[row * a.ldh + n] = m;  // pad columns hold zeros: the tower's zero K pad
+        if constexpr (TRAIN) {
+          if (a.mixed && n < a.pitch_m && row < rows) a.mixed[((m0 + row) * K + k) * a.pitch_m + n] = n < H ? m : 0.f;
+        } else {
+          if (a.mixed && n < H && row < rows) a.mixed[((m0 + row) * K + k) * H + n] = m;
         }
-      }
+      });
       if (!a.has_head) continue;
       mlp_lds_barrier();
       for (int l = 0; l < Dt; ++l) {
-        const int ln = lane_now();
+        const int ln = lane_now(lane);
         const rk_mlp_layer L = tower(k, l);
         const int Kp = pad64(l ? a.layers[E * De + k * Dt + l - 1].n : H);
         const float* in = (l & 1) ? hb : ha;
         float* out = (l & 1) ? ha : hb;
-        mm_layer(pipe, L, in, a.ldh, out, a.ldh, Kp, wave, ln);
+        mtl_layer(pipe, L, in, a.ldh, out, a.ldh, Kp, wave, ln);
         if (l + 1 < Dt) {
           const rk_mlp_layer N = tower(k, l + 1);
-          mm_prepare(pipe, N, L.n, wave, ln);
+          mtl_prepare(pipe, N, L.n, wave, ln);
         } else if (kk + 1 < kg) {
           const rk_mlp_layer N = tower(k + 1, 0);
-          mm_prepare(pipe, N, H, wave, ln);
+          mtl_prepare(pipe, N, H, wave, ln);
         } else if (more) {
           const rk_mlp_layer N = expert(0, 0);
-          mm_prepare(pipe, N, width, wave, ln);
+          mtl_prepare(pipe, N, width, wave, ln);
         }
         close_layer();
         if constexpr (TRAIN) {
@@ -394,6 +310,9 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
       }
       const float* fin = (Dt & 1) ? hb : ha;
       const int Kh = Dt ? a.layers[E * De + k * Dt + Dt - 1].n : H;
+      // (the head stays written out here and in ple.hip: as a function taking a.head_w[k] and a.head_b[k],
+      // by value or by reference, the runtime index into the by-value argument arrays moved the whole
+      // argument block into scratch, 3344 B per lane)
       if (live) {  // one wave per row
         const float* hw = a.head_w[k];
         float p = 0.f;
@@ -410,49 +329,9 @@ __global__ __launch_bounds__(kMlpThreads) void mmoe_kernel(std::conditional_t<TR
   }
 }
 
-// rk_mlp_pack_weight's image (mlp.hip, mlp_pack_kernel) of many weights in one launch: grid
-// (256-element blocks of the largest image, weight).
-constexpr int kPackMaxItems = 96;
-struct PackItems {
-  rk_pack_item item[kPackMaxItems];
-};
-static_assert(sizeof(PackItems) <= 4096, "kernel arguments beyond 4 KiB");
-
-__global__ __launch_bounds__(256) void mlp_pack_many_kernel(PackItems p) {
-  const rk_pack_item& it = p.item[blockIdx.y];
-  const int np = pad64(it.n), kp = pad64(it.k);
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)np * kp) return;
-  const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
-  const int64_t blk = i >> 8;
-  const int kch = kp / 16;
-  const int t = (int)(blk / kch), c = (int)(blk % kch);
-  const int r = 16 * t + (lane & 15), col = 16 * c + 4 * (lane >> 4) + e;
-  it.out[i] = (r < it.n && col < it.k) ? it.w[(int64_t)r * it.ldw + col] : 0.f;
-}
-
 }  // namespace rk
 
 using namespace rk;
-
-RK_API int rk_mlp_pack_weights(const rk_pack_item* items, int32_t count, void* stream) {
-  if (count < 0 || (count > 0 && !items)) return fail(RK_ERR_INVALID, "rk_mlp_pack_weights: bad arguments");
-  for (int i = 0; i < count; ++i)
-    if (!items[i].w || !items[i].out || items[i].n <= 0 || items[i].k <= 0 || items[i].ldw < items[i].k ||
-        !aligned16(items[i].out))
-      return fail(RK_ERR_INVALID, "rk_mlp_pack_weights: item %d: null / misaligned pointer or bad shape", i);
-  for (int i0 = 0; i0 < count; i0 += kPackMaxItems) {
-    PackItems p = {};
-    const int c = std::min(kPackMaxItems, count - i0);
-    int64_t most = 0;
-    for (int i = 0; i < c; ++i) {
-      p.item[i] = items[i0 + i];
-      most = std::max<int64_t>(most, (int64_t)pad64(p.item[i].n) * pad64(p.item[i].k));
-    }
-    mlp_pack_many_kernel<<<dim3((unsigned)((most + 255) / 256), (unsigned)c), 256, 0, (hipStream_t)stream>>>(p);
-  }
-  return check_launch("rk_mlp_pack_weights");
-}
 
 namespace {
 
@@ -480,11 +359,11 @@ int mmoe_launch(const char* name, const rk_segment* segs, int32_t nseg, int32_t 
   if (!head_w && (logits || probs)) return fail(RK_ERR_INVALID, "%s: logits / probs need the heads", name);
   if (!(head_w ? (logits || probs || mixed || gate_probs) : (mixed || gate_probs)))
     return fail(RK_ERR_INVALID, "%s: no output", name);
-  if (nseg > kMmSegs || width > kMmCols || num_experts > kMmMaxExperts || num_tasks > kMmMaxTasks ||
+  if (nseg > kRowSegs || width > kRowCols || num_experts > kMmMaxExperts || num_tasks > kMmMaxTasks ||
       num_tasks * num_experts > kMmMaxGates || expert_depth > kMmMaxDepth || tower_depth > kMmMaxDepth)
     return fail(RK_ERR_UNSUPPORTED, "%s: %d segments (<= %d) over %d columns (<= %d), %d experts (<= %d) of depth %d (1..%d), "
                 "%d tasks (<= %d, tasks x experts <= %d), tower depth %d (<= %d)", name,
-                nseg, kMmSegs, width, kMmCols, num_experts, kMmMaxExperts, expert_depth, kMmMaxDepth, num_tasks,
+                nseg, kRowSegs, width, kRowCols, num_experts, kMmMaxExperts, expert_depth, kMmMaxDepth, num_tasks,
                 kMmMaxTasks, kMmMaxGates, tower_depth, kMmMaxDepth);
   MmoeTrainArgs a = {};
   int wide = kMlpPad;  // the widest hidden activation, padded
@@ -519,21 +398,7 @@ int mmoe_launch(const char* name, const rk_segment* segs, int32_t nseg, int32_t 
   }
   if (!aligned16(gate_w)) return fail(RK_ERR_INVALID, "%s: gate image misaligned", name);
   a.gate = rk_mmoe_layer{gate_w, gate_b, num_tasks * num_experts, RK_ACT_NONE};
-  for (int c = 0; c < kMmCols; ++c) {
-    a.col_seg[c] = 255;
-    a.col_off[c] = 0;
-  }
-  for (int i = 0; i < nseg; ++i) {
-    const rk_segment& sg = segs[i];
-    if (!sg.src || sg.dim <= 0 || sg.out_col < 0 || sg.out_col + sg.dim > width || (sg.idx && sg.rows <= 0) ||
-        sg.dim > 255)
-      return fail(RK_ERR_INVALID, "%s: segment %d invalid", name, i);
-    a.segs[i] = sg;
-    for (int c = sg.out_col; c < sg.out_col + sg.dim; ++c) {  // the last covering segment wins
-      a.col_seg[c] = (uint8_t)i;
-      a.col_off[c] = (uint8_t)(c - sg.out_col);
-    }
-  }
+  if (int rc = row_map_fill(a.map, segs, nseg, width, name)) return rc;
   a.M = batch;
   a.width = width;
   a.E = num_experts;

@@ -32,12 +32,14 @@
 // LDS (floats): xin [nx][16][ldr] (nx = K + 1 inputs, 1 when L == 1), ha and hb [16][ldh],
 // gs [2][16][64 + 8], gt [GC][16] (gt[(column offset + c) 16 + row]), mt [K + 1][pad64(H)][16]
 // (mt[(i pad64(H) + n) 16 + row]: every element belongs to one lane, no barrier guards it).
-#include "mlp_core.h"
+//
+// The row's column map, the per-layer dispatch (mtl_prepare, mtl_layer, mtl_layer_tiles with its
+// TileSink), lane_now, close_layer and the mix into / walk over mt (mtl_mix, mtl_unmix) are
+// mtl_core.h's, shared with mmoe.hip.
+#include "mtl_core.h"
 
 namespace rk {
 
-constexpr int kPlSegs = 16;
-constexpr int kPlCols = 256;
 constexpr int kPlMaxLevels = 4;
 constexpr int kPlMaxTasks = 8;
 constexpr int kPlMaxStacks = 64;  // K ms + mc: the shared gate's columns (4 tiles)
@@ -45,8 +47,7 @@ constexpr int kPlMaxDepth = 3;
 constexpr int kPlLdG = kPlMaxStacks + kMlpLdPad;
 
 struct PleArgs {
-  rk_segment segs[kPlSegs];
-  uint8_t col_seg[kPlCols], col_off[kPlCols];  // 255: no segment
+  RowMap map;
   const rk_mmoe_layer* table;  // device: experts [(j NE + s) De + l], gates, towers [k Dt + l], heads
   int64_t M;
   int width, L, K, ms, mc, De, Dt, H;
@@ -61,55 +62,6 @@ struct PleArgs {
 };
 static_assert(sizeof(PleArgs) <= 4096, "kernel arguments beyond 4 KiB");
 
-// mlp_layer's sink of an expert's last layer: the wave's finished tiles stay in registers (one type
-// per tile count, as in mmoe.hip).
-template <int TPW>
-struct PlTileSink {
-  f32x4_t z[TPW];
-  __device__ __forceinline__ void take(int j, int r, int row, float v) { z[j][r] = v; }
-};
-
-// Wave w owns column tiles w and w + 16; a wave without a tile takes part in the active waves'
-// lockstep barriers.
-__device__ __forceinline__ void pl_prepare(LayerPipe& pipe, const rk_mlp_layer& L, int K, int wave, int lane) {
-  const int nt = pad64(L.n) / 16, kch = pad64(K) / 16;
-  if (wave + kMlpWaves < nt)
-    pipe.prepare<2, 4>(L, kch, wave, lane);
-  else if (wave < nt)
-    pipe.prepare<1, 8>(L, kch, wave, lane);
-}
-
-__device__ __forceinline__ void pl_layer(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin, float* out,
-                                         int ldout, int Kp, int wave, int lane) {
-  const int ntiles = pad64(L.n) / 16;
-  if (wave + kMlpWaves < ntiles) {
-    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
-  } else if (wave < ntiles) {
-    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, out, ldout, Kp, wave, lane, 0, kMlpRows);
-  } else {
-    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
-  }
-}
-
-// The same with the output tiles left in z (zero for a tile the wave does not own), nothing in LDS.
-__device__ __forceinline__ void pl_layer_tiles(LayerPipe& pipe, const rk_mlp_layer& L, const float* in, int ldin,
-                                               int Kp, int wave, int lane, f32x4_t (&z)[2]) {
-  const int ntiles = pad64(L.n) / 16;
-  z[0] = z[1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  if (wave + kMlpWaves < ntiles) {
-    PlTileSink<2> f;
-    mlp_layer<2, 1, 4, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
-    z[0] = f.z[0];
-    z[1] = f.z[1];
-  } else if (wave < ntiles) {
-    PlTileSink<1> f;
-    mlp_layer<1, 1, 8, false>(pipe, L, in, ldin, nullptr, 0, Kp, wave, lane, 0, kMlpRows, 0, 0, &f);
-    z[0] = f.z[0];
-  } else {
-    for (int i = 0; i < (Kp / 16 - 1) / kMlpSyncChunks; ++i) mlp_sync_barrier();
-  }
-}
-
 __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
@@ -119,7 +71,7 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
   const int NE = K * ms + mc;             // the stacks of a level: task k's at k ms + i, the shared at K ms + i
   const int GT = ms + mc;                 // a task gate's columns
   const int GC = K * GT + NE;             // gt's columns: task gate k at k GT, the shared gate at K GT
-  const int Hp = pad64(H), ntH = Hp / 16;
+  const int Hp = pad64(H);
   float* const xin = sm;
   float* const ha = xin + a.nx * kMlpRows * a.ldr;
   float* const hb = ha + kMlpRows * a.ldh;
@@ -132,17 +84,19 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
   const rk_mmoe_layer* __restrict__ const table = a.table;
   const int gate0 = NL * NE * De, tower0 = gate0 + NL * (K + 1), head0 = tower0 + K * Dt;
 
-  // 1. the row gather (mlp_gather_kernel's stage): indices first, the values after
-  float v[kPlCols / 64];
-  int64_t r[kPlCols / 64];
-  int sg[kPlCols / 64];
+  // 1. the row gather (mlp_gather_kernel's stage): indices first, the values after.  (Written out in each
+  // of the three kernels: as one shared function it changed mlp_gather_kernel's instruction stream and
+  // made mmoe_kernel slower at large batches.)
+  float v[kRowCols / 64];
+  int64_t r[kRowCols / 64];
+  int sg[kRowCols / 64];
 #pragma unroll
-  for (int i = 0; i < kPlCols / 64; ++i) {
+  for (int i = 0; i < kRowCols / 64; ++i) {
     const int c = lane + 64 * i;
-    sg[i] = live && c < width ? a.col_seg[c] : 255;
+    sg[i] = live && c < width ? a.map.col_seg[c] : 255;
     r[i] = b;
     if (sg[i] != 255) {
-      const rk_segment& g = a.segs[sg[i]];
+      const rk_segment& g = a.map.segs[sg[i]];
       if (g.idx) {
         r[i] = g.idx[b * g.idx_stride];
         if (r[i] < 0 || r[i] >= g.rows) {
@@ -153,11 +107,11 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
     }
   }
 #pragma unroll
-  for (int i = 0; i < kPlCols / 64; ++i) {
+  for (int i = 0; i < kRowCols / 64; ++i) {
     v[i] = 0.f;
     if (sg[i] != 255 && r[i] >= 0) {
-      const rk_segment& g = a.segs[sg[i]];
-      v[i] = g.src[r[i] * g.src_ld + a.col_off[lane + 64 * i]];
+      const rk_segment& g = a.map.segs[sg[i]];
+      v[i] = g.src[r[i] * g.src_ld + a.map.col_off[lane + 64 * i]];
     }
   }
   __builtin_amdgcn_sched_barrier(0);  // the gather's loads stay ahead of the weight ring
@@ -194,24 +148,12 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
   };
   // input slot of owner q (a task, or K: the shared representation) at level j
   auto input = [&](int j, int q) -> const float* { return j ? xin + q * kMlpRows * a.ldr : xin; };
-  // The lane index behind an empty asm, taken once per layer (mmoe.hip: derived from `lane` itself the
-  // compiler hoists every layer's addresses out of the loops and spills them around every layer).
-  auto lane_now = [&]() {
-    int x = lane;
-    asm volatile("" : "+v"(x));
-    return x;
-  };
-  auto close_layer = [&]() {
-    mlp_lds_barrier();
-    __builtin_amdgcn_s_setprio(0);
-  };
-
   {
     const rk_mlp_layer LG = gate(0, 0);
-    pl_prepare(pipe, LG, width, wave, lane);
+    mtl_prepare(pipe, LG, width, wave, lane);
   }
 #pragma unroll
-  for (int i = 0; i < kPlCols / 64; ++i) {
+  for (int i = 0; i < kRowCols / 64; ++i) {
     const int c = lane + 64 * i;
     if (c < K0p) xin[wave * a.ldr + c] = v[i];  // dead rows and pad columns stage zeros
   }
@@ -225,16 +167,16 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
 
     // 2. the gates
     for (int q = 0; q < nq; ++q) {
-      const int ln = lane_now();
+      const int ln = lane_now(lane);
       const rk_mlp_layer LG = gate(j, q);
       float* const gq = gs + (q & 1) * kMlpRows * kPlLdG;
-      pl_layer(pipe, LG, input(j, q), a.ldr, gq, kPlLdG, Kinp, wave, ln);
+      mtl_layer(pipe, LG, input(j, q), a.ldr, gq, kPlLdG, Kinp, wave, ln);
       {  // the next gate, or the level's first expert (one prepare for both: the descriptor is chosen, not the call)
         const bool more = q + 1 < nq;
         rk_mlp_layer N = view(more ? gate0 + j * (K + 1) + q + 1 : j * NE * De, more ? (q + 1 < K ? GT : NE) : eun(0),
                               more ? RK_ACT_NONE : RK_ACT_RELU);
         N.ldw = Kinp;
-        pl_prepare(pipe, N, Kin, wave, ln);
+        mtl_prepare(pipe, N, Kin, wave, ln);
       }
       close_layer();
       // softmax of gate q: one wave outside the four that own the next gate's tiles; lane = row + 16 part,
@@ -265,7 +207,7 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
       const int owner = s < K * ms ? s / ms : K;
       const float* const x0 = input(j, owner);
       for (int l = 0; l < De; ++l) {
-        const int ln = lane_now();
+        const int ln = lane_now(lane);
         const rk_mlp_layer L = expert(j, s, l);
         const int Kp = pad64(l ? eun(l - 1) : Kin);
         const float* in = l == 0 ? x0 : (l & 1) ? ha : hb;
@@ -292,13 +234,12 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
         rk_mlp_layer N = view(has_next ? nidx : 0, nn, nact);
         N.ldw = pad64(nk);
         if (l + 1 < De) {
-          pl_layer(pipe, L, in, l == 0 ? a.ldr : a.ldh, out, a.ldh, Kp, wave, ln);
-          pl_prepare(pipe, N, nk, wave, ln);
+          mtl_layer(pipe, L, in, l == 0 ? a.ldr : a.ldh, out, a.ldh, Kp, wave, ln);
+          mtl_prepare(pipe, N, nk, wave, ln);
         } else {
           f32x4_t z[2];
-          pl_layer_tiles(pipe, L, in, l == 0 ? a.ldr : a.ldh, Kp, wave, ln, z);
-          if (has_next) pl_prepare(pipe, N, nk, wave, ln);
-          const int q4 = (ln >> 4) * 4;  // the lane's first row
+          mtl_layer_tiles(pipe, L, in, l == 0 ? a.ldr : a.ldh, Kp, wave, ln, z);
+          if (has_next) mtl_prepare(pipe, N, nk, wave, ln);
           // mixtures i0 .. i1 - 1 take this expert (a task's expert: its task, then the shared one below)
           const int i0 = owner < K ? owner : 0, i1 = owner < K ? owner + 1 : K;
           const int col = owner < K ? s - owner * ms : ms + (s - K * ms);  // its column of a task gate
@@ -311,19 +252,7 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
               gcol = K * GT + s;
               first = s == 0;
             }
-            const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(gt + gcol * kMlpRows + q4);
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) {
-              const int t = wave + kMlpWaves * t2;
-              if (t < ntH) {
-                f32x4_t* const mp = reinterpret_cast<f32x4_t*>(mt + (slot * Hp + 16 * t + (ln & 15)) * kMlpRows + q4);
-                f32x4_t m = {0.f, 0.f, 0.f, 0.f};
-                if (!first) m = *mp;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) m[q] = __builtin_fmaf(gv[q], z[t2][q], m[q]);
-                *mp = m;
-              }
-            }
+            mtl_mix(mt, gt, slot, gcol, first, z, Hp, wave, ln);
           }
         }
         close_layer();
@@ -332,24 +261,14 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
 
     if (!last_level) {
       // 4a. the K + 1 mixtures -> the next level's row-major inputs (pad columns hold zeros) and reps[j]
-      const int lm = lane_now();
+      const int lm = lane_now(lane);
       float* const ro = a.reps[j];
       for (int i = 0; i <= K; ++i) {
         float* const xi = xin + i * kMlpRows * a.ldr;
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) {
-          const int t = wave + kMlpWaves * t2;
-          if (t < ntH) {
-            const int n = 16 * t + (lm & 15);
-            const f32x4_t mv = *reinterpret_cast<const f32x4_t*>(mt + (i * Hp + n) * kMlpRows + (lm >> 4) * 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int row = (lm >> 4) * 4 + q;
-              xi[row * a.ldr + n] = mv[q];
-              if (ro && n < H && row < rows) ro[((m0 + row) * (K + 1) + i) * H + n] = mv[q];
-            }
-          }
-        }
+        mtl_unmix(mt, i, Hp, wave, lm, [&](int row, int n, float m) {
+          xi[row * a.ldr + n] = m;
+          if (ro && n < H && row < rows) ro[((m0 + row) * (K + 1) + i) * H + n] = m;
+        });
       }
       mlp_lds_barrier();
     }
@@ -359,36 +278,26 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
   {
     float* const ro = a.reps[NL - 1];
     for (int k = 0; k < K; ++k) {
-      const int lm = lane_now();
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        const int t = wave + kMlpWaves * t2;
-        if (t < ntH) {
-          const int n = 16 * t + (lm & 15);
-          const f32x4_t mv = *reinterpret_cast<const f32x4_t*>(mt + (k * Hp + n) * kMlpRows + (lm >> 4) * 4);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int row = (lm >> 4) * 4 + q;
-            if (a.has_head) ha[row * a.ldh + n] = mv[q];  // pad columns hold zeros: the tower's zero K pad
-            if (ro && n < H && row < rows) ro[((m0 + row) * K + k) * H + n] = mv[q];
-          }
-        }
-      }
+      const int lm = lane_now(lane);
+      mtl_unmix(mt, k, Hp, wave, lm, [&](int row, int n, float m) {
+        if (a.has_head) ha[row * a.ldh + n] = m;  // pad columns hold zeros: the tower's zero K pad
+        if (ro && n < H && row < rows) ro[((m0 + row) * K + k) * H + n] = m;
+      });
       if (!a.has_head) continue;
       mlp_lds_barrier();
       for (int l = 0; l < Dt; ++l) {
-        const int ln = lane_now();
+        const int ln = lane_now(lane);
         const rk_mlp_layer L = tower(k, l);
         const int Kp = pad64(l ? tun(l - 1) : H);
         const float* in = (l & 1) ? hb : ha;
         float* out = (l & 1) ? ha : hb;
-        pl_layer(pipe, L, in, a.ldh, out, a.ldh, Kp, wave, ln);
+        mtl_layer(pipe, L, in, a.ldh, out, a.ldh, Kp, wave, ln);
         if (l + 1 < Dt) {
           const rk_mlp_layer N = tower(k, l + 1);
-          pl_prepare(pipe, N, L.n, wave, ln);
+          mtl_prepare(pipe, N, L.n, wave, ln);
         } else if (k + 1 < K) {
           const rk_mlp_layer N = tower(k + 1, 0);
-          pl_prepare(pipe, N, H, wave, ln);
+          mtl_prepare(pipe, N, H, wave, ln);
         }
         close_layer();
       }
@@ -427,11 +336,11 @@ RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, i
   if (!has_heads && (logits || probs)) return fail(RK_ERR_INVALID, "%s: logits / probs need the heads", name);
   const int L = num_levels, K = num_tasks, ms = num_specific, mc = num_shared, De = expert_depth, Dt = tower_depth;
   const int64_t NE = (int64_t)K * ms + mc;
-  if (nseg > kPlSegs || width > kPlCols || L > kPlMaxLevels || K > kPlMaxTasks || ms > kPlMaxStacks ||
+  if (nseg > kRowSegs || width > kRowCols || L > kPlMaxLevels || K > kPlMaxTasks || ms > kPlMaxStacks ||
       mc > kPlMaxStacks || NE > kPlMaxStacks || De > kPlMaxDepth || Dt > kPlMaxDepth)
     return fail(RK_ERR_UNSUPPORTED, "%s: %d segments (<= %d) over %d columns (<= %d), %d levels (<= %d), %d tasks (<= %d), "
                 "%d specific and %d shared experts (tasks x specific + shared <= %d) of depth %d (1..%d), tower depth %d "
-                "(<= %d)", name, nseg, kPlSegs, width, kPlCols, L, kPlMaxLevels, K, kPlMaxTasks, ms, mc, kPlMaxStacks,
+                "(<= %d)", name, nseg, kRowSegs, width, kRowCols, L, kPlMaxLevels, K, kPlMaxTasks, ms, mc, kPlMaxStacks,
                 De, kPlMaxDepth, Dt, kPlMaxDepth);
   bool any_out = logits || probs;
   for (int j = 0; j < L; ++j) any_out = any_out || (level_reps && level_reps[j]) || (level_gates && level_gates[j]);
@@ -452,21 +361,7 @@ RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, i
   if (table_len != want || !aligned16(table) || ((uintptr_t)table & 7u))
     return fail(RK_ERR_INVALID, "%s: the layer table holds %lld descriptors, this shape needs %lld", name,
                 (long long)table_len, (long long)want);
-  for (int c = 0; c < kPlCols; ++c) {
-    a.col_seg[c] = 255;
-    a.col_off[c] = 0;
-  }
-  for (int i = 0; i < nseg; ++i) {
-    const rk_segment& sg = segs[i];
-    if (!sg.src || sg.dim <= 0 || sg.out_col < 0 || sg.out_col + sg.dim > width || (sg.idx && sg.rows <= 0) ||
-        sg.dim > 255)
-      return fail(RK_ERR_INVALID, "%s: segment %d invalid", name, i);
-    a.segs[i] = sg;
-    for (int c = sg.out_col; c < sg.out_col + sg.dim; ++c) {  // the last covering segment wins
-      a.col_seg[c] = (uint8_t)i;
-      a.col_off[c] = (uint8_t)(c - sg.out_col);
-    }
-  }
+  if (int rc = row_map_fill(a.map, segs, nseg, width, name)) return rc;
   a.table = table;
   a.M = batch;
   a.width = width;

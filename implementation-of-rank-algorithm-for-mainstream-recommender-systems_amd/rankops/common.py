@@ -5,6 +5,8 @@ from __future__ import annotations
 import functools
 import math
 import os
+import sys
+import types
 import weakref
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
@@ -669,6 +671,16 @@ def check_eval(module: nn.Module):
             f"{type(module).__name__}: the rankops engine implements the eval-mode forward "
             f"(BatchNorm running stats, Dropout identity) on this path; call .eval() first, or "
             f"run the train-mode forward with autograd enabled (rankops.train).")
+
+
+def callable_module(name: str, fn):
+    """Makes the imported module `name` callable as `fn`: `rankops.mmoe` is the module and, called,
+    the op-level function ops.mmoe."""
+    class _CallableModule(types.ModuleType):
+        def __call__(self, *args, **kwargs):
+            return fn(*args, **kwargs)
+
+    sys.modules[name].__class__ = _CallableModule
 
 
 def sqrt_f32(x: float) -> float:

@@ -39,15 +39,11 @@ module is callable so that `rankops.ple` is both the module and that function.
 """
 from __future__ import annotations
 
-import sys
-import types
-
 import torch
 import torch.nn as nn
 
 from . import common, ops
-from .common import EngineModule, check_eval, table_rows
-from .mmoe import DEFAULT_TASKS, _stack
+from .multitask import DEFAULT_TASKS, MultiTask, _stack
 
 
 class _LevelGates:
@@ -95,55 +91,28 @@ class _Level(nn.Module):
         return [e for task in self.specific_experts for e in task] + list(self.shared_experts)
 
 
-class PLE(EngineModule):
+class PLE(MultiTask):
+    NAME, ENTRY = "PLE", "rk_ple_forward"
+    LOGITS_SLOT, PROBS_SLOT = ops.PLE_LOGITS_SLOT, ops.PLE_PROBS_SLOT
+
     def __init__(self, vocab_dir, num_levels=2, num_specific_experts=2, num_shared_experts=2,
                  expert_hidden_units=(256, 128), tower_hidden_units=(64,), task_names=DEFAULT_TASKS, dropout_rate=0.1,
                  *, vocab_sizes=None):
-        super().__init__()
-        self.dropout_rate = float(dropout_rate)
-        expert_hidden_units = tuple(int(h) for h in expert_hidden_units)
-        tower_hidden_units = tuple(int(h) for h in tower_hidden_units)
-        task_names = tuple(task_names)
         if int(num_levels) <= 0:
             raise ValueError(f"num_levels must be positive, got {num_levels!r}")
         if int(num_specific_experts) < 0 or int(num_shared_experts) <= 0:
             raise ValueError(f"num_specific_experts must be >= 0 and num_shared_experts >= 1, got "
                              f"{num_specific_experts!r}, {num_shared_experts!r}")
-        if len(expert_hidden_units) == 0 or any(h <= 0 for h in expert_hidden_units + tower_hidden_units):
-            raise ValueError(f"expert_hidden_units must be a non-empty list of positive widths and tower_hidden_units "
-                             f"a list of positive widths, got {expert_hidden_units!r}, {tower_hidden_units!r}")
-        if len(task_names) == 0 or len(set(task_names)) != len(task_names):
-            raise ValueError(f"task_names must be a non-empty list of distinct names, got {task_names!r}")
-        if not 0 <= dropout_rate < 1:
-            raise ValueError(f"dropout_rate must lie in [0, 1), got {dropout_rate!r}")
-        fields = ("userid", "feedid", "device", "authorid", "bgm_song_id", "bgm_singer_id", "manual_tag_list")
-        self.vocab_sizes = {f: table_rows(vocab_dir, f, vocab_sizes) for f in fields}
-        self.num_dense_features = 16
+        super().__init__(vocab_dir, expert_hidden_units, tower_hidden_units, task_names, dropout_rate, vocab_sizes)
         self.num_levels = int(num_levels)
         self.num_specific_experts = int(num_specific_experts)
         self.num_shared_experts = int(num_shared_experts)
-        self.task_names = task_names
-        self.expert_hidden_units = expert_hidden_units
-        self.tower_hidden_units = tower_hidden_units
-        self.embeddings = nn.ModuleDict({
-            "userid": nn.Embedding(self.vocab_sizes["userid"], 16),
-            "device": nn.Embedding(self.vocab_sizes["device"], 2),
-            "authorid": nn.Embedding(self.vocab_sizes["authorid"], 4),
-            "bgm_song_id": nn.Embedding(self.vocab_sizes["bgm_song_id"], 4),
-            "bgm_singer_id": nn.Embedding(self.vocab_sizes["bgm_singer_id"], 4),
-            "manual_tag_list": nn.Embedding(self.vocab_sizes["manual_tag_list"], 4),
-        })
-        self.input_dim = self.num_dense_features + 16 + 2 + 4 + 4 + 4 + 4
-        K, H = len(task_names), expert_hidden_units[-1]
+        K, H = len(self.task_names), self.expert_hidden_units[-1]
         self.levels = nn.ModuleList(
             _Level(self.input_dim if j == 0 else H, K, self.num_specific_experts, self.num_shared_experts,
-                   expert_hidden_units, dropout_rate, j == self.num_levels - 1) for j in range(self.num_levels))
-        self.towers = nn.ModuleList()
-        last = H
-        for _ in range(K):
-            seq, last = _stack(H, tower_hidden_units, dropout_rate)
-            self.towers.append(seq)
-        self.tower_outputs = nn.ModuleList(nn.Linear(last, 1) for _ in range(K))
+                   self.expert_hidden_units, self.dropout_rate, j == self.num_levels - 1)
+            for j in range(self.num_levels))
+        self._make_towers(H)
         self._gate_images = [_LevelGates() for _ in range(self.num_levels)]
 
     def fits(self) -> bool:
@@ -151,35 +120,7 @@ class PLE(EngineModule):
                                self.num_specific_experts, self.num_shared_experts, self.expert_hidden_units,
                                self.tower_hidden_units)
 
-    def _indices(self, category):
-        names = list(self.embeddings)
-        if not isinstance(category, dict):
-            raise TypeError(f"PLE.forward: category must be a dict of index tensors, got {type(category).__name__}")
-        missing = [c for c in names if c not in category]
-        if missing:
-            raise KeyError(f"PLE.forward: category features missing: {missing}")
-        idx = [ops.as_index(category[n], f"category[{n!r}]") for n in names]
-        return names, idx
-
-    @staticmethod
-    def _linears(seq):
-        return [m for m in seq if isinstance(m, nn.Linear)]
-
-    def _build(self, dense, names, idx, pin=False):
-        """The forward's one rk_ple_forward launch over these inputs as a common.Bound (pin: prepare()'s
-        pinned weight images); the outputs are patched in per call."""
-        if not self.fits():
-            raise RuntimeError("PLE: configuration outside rk_ple_forward's envelope (common.ple_fits)")
-        B, dev = dense.shape[0], dense.device
-        if any(t.dim() != 1 or t.shape[0] != B for t in idx):
-            raise ValueError("PLE.forward: every category feature must be a 1-D tensor of the batch's length")
-        image = common.PACKED.pin if pin else common.PACKED
-        segs = [ops.dense_segment(dense, self.num_dense_features, 0)]
-        col = self.num_dense_features
-        for n, i in zip(names, idx):
-            emb = self.embeddings[n]
-            segs.append(ops.table_segment(emb.weight, i, col))
-            col += emb.embedding_dim
+    def _launch_args(self, segs, B, dev, image, pin):
         K = len(self.task_names)
         experts, gates = [], []
         for level, packer in zip(self.levels, self._gate_images):
@@ -192,62 +133,9 @@ class PLE(EngineModule):
         towers = [(image(l.weight), l.bias) for seq in self.towers for l in self._linears(seq)]
         heads = [(o.weight, o.bias) for o in self.tower_outputs]
         entries = experts + gates + towers + heads
-        args, keep = ops.ple_forward_args(segs, self.input_dim, B, self.num_levels, K, self.num_specific_experts,
-                                          self.num_shared_experts, self.expert_hidden_units, self.tower_hidden_units,
-                                          entries, True, dev)
-        return common.bound([("rk_ple_forward", args)], B, keep, self._patch)
-
-    @staticmethod
-    def _patch(_ep, args, out):
-        prob, logit = out
-        args[ops.PLE_LOGITS_SLOT], args[ops.PLE_PROBS_SLOT] = logit.data_ptr(), prob.data_ptr()
-
-    @staticmethod
-    def _run(bound, out, stream):
-        bound.patch(out)
-        common.run_launches(bound.launches, stream)
-
-    def _outputs(self, B, dev):
-        return common.empty_rows(dev, 2, (B, len(self.task_names)))
-
-    def prepare(self, dense, category):
-        """An eval forward bound to these input tensors (as MMoE.prepare): returns `run()` that recomputes
-        the whole forward from the current contents of the inputs with one rk_ple_forward launch and returns
-        the same (probabilities, logits) tensors each time.  Binds the current weights and pins their packed
-        images: prepare again after changing them."""
-        if self.training:
-            raise RuntimeError("PLE.prepare: eval mode only (call .eval() first)")
-        dense = ops.as_f32(dense, "dense")
-        names = list(self.embeddings)
-        idx = [ops.bound_index(category[n], f"category[{n!r}]") for n in names]
-        if dense.shape[0] == 0:
-            raise ValueError("PLE.prepare: empty batch")
-        return common.prepared(self, self._build(dense, names, idx, pin=True), dense.device, (dense, category))
-
-    def forward(self, dense, category):
-        check_eval(self)  # training is later work
-        dense = ops.as_f32(dense, "dense")
-        if dense.dim() != 2 or dense.shape[1] < self.num_dense_features:
-            raise ValueError(f"PLE.forward: dense must be [B, {self.num_dense_features}], got {tuple(dense.shape)}")
-        names, idx = self._indices(category)
-        B, dev = dense.shape[0], dense.device
-        if B == 0:
-            return common.empty_rows(dev, 2, (0, len(self.task_names)))
-        stream = ops._lib.raw_stream(dev)
-        if all(t is category[n] for t, n in zip(idx, names)):  # no converted copies: addresses are the caller's
-            bound = common.EagerCalls.lookup(self, [dense] + idx, stream, lambda: self._build(dense, names, idx))
-        else:
-            bound = self._build(dense, names, idx)
-        out = self._outputs(B, dev)
-        self._run(bound, out, stream)
-        return out
+        return ops.ple_forward_args(segs, self.input_dim, B, self.num_levels, K, self.num_specific_experts,
+                                    self.num_shared_experts, self.expert_hidden_units, self.tower_hidden_units,
+                                    entries, True, dev)
 
 
-class _CallableModule(types.ModuleType):
-    """`rankops.ple(x, levels, towers=None, return_levels=False)`: the op-level function under the module's name."""
-
-    def __call__(self, *args, **kwargs):
-        return ops.ple(*args, **kwargs)
-
-
-sys.modules[__name__].__class__ = _CallableModule
+common.callable_module(__name__, ops.ple)  # rankops.ple(x, levels, towers=None, return_levels=False)

@@ -701,14 +701,9 @@ def _mmoe_front(model, dense, names, idx):
     seed, slot = 0, None
     if p > 0:
         seed, slot = model.__dict__.setdefault("_dropout", DropoutStreams()).next(dev)
-    segs = [ops.dense_segment(dense, model.num_dense_features, 0)]
-    col = model.num_dense_features
-    for n, i in zip(names, idx):
-        emb = model.embeddings[n]
-        segs.append(ops.table_segment(emb.weight, i, col))
-        col += emb.embedding_dim
     heads = [(w, b) for _, (w, b) in towers]
-    s = ops.mmoe_forward_train(segs, sh, B, stacks, gate_image, gate_b, tstacks, heads, dev, p, seed, slot)
+    s = ops.mmoe_forward_train(model._segments(dense, names, idx), sh, B, stacks, gate_image, gate_b, tstacks, heads,
+                               dev, p, seed, slot)
     s["weights"] = (experts, gates, towers, wst)
     s["dropout"] = (seed, slot)
     return sh, s

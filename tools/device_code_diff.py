@@ -5,7 +5,7 @@
 
 A tree is a git revision (materialised with `git archive` into a temporary directory) or `.`, the
 working tree (its tracked and its new, not ignored files, copied likewise).  Every named file (default: the translation units that include mlp_core.h /
-mlp_stream.h) is compiled in each tree with the flags that tree's csrc/Makefile gives its library
+mlp_stream.h / mtl_core.h) is compiled in each tree with the flags that tree's csrc/Makefile gives its library
 objects (read from `make -n`), plus --offload-device-only --no-gpu-bundle-output, at most 16
 compiles at once.  One line per file: `identical` when the two device ELFs have the same sha256,
 otherwise the __global__ kernels whose instruction stream (llvm-objdump -d, addresses and encodings
@@ -23,7 +23,8 @@ import subprocess
 import sys
 import tempfile
 
-DEFAULT_FILES = ["mlp.hip", "din_fused.hip", "deepfm_fused.hip", "bst_small.hip", "linear_tiled.hip", "afm.hip"]
+DEFAULT_FILES = ["mlp.hip", "din_fused.hip", "deepfm_fused.hip", "bst_small.hip", "dien_forward.hip",
+                 "linear_tiled.hip", "afm.hip", "mmoe.hip", "ple.hip"]
 DEVICE_ONLY = ["--offload-device-only", "--no-gpu-bundle-output"]
 # per-kernel metadata named in a report (any other difference in the kernel's note is "other")
 META_KEYS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size",
