@@ -36,7 +36,13 @@
 // The row's column map, the per-layer dispatch (mtl_prepare, mtl_layer, mtl_layer_tiles with its
 // TileSink), lane_now, close_layer and the mix into / walk over mt (mtl_mix, mtl_unmix) are
 // mtl_core.h's, shared with mmoe.hip.
+//
+// ple_kernel<true> is the train forward (rk_ple_forward_train), as mmoe_kernel<true>: dropout behind
+// every ReLU and every buffer the backward reads written on the way.  Every hidden layer, an expert's
+// last one included, goes through LDS; dropout and the HBM store run from there after the layer's
+// barrier, and the lanes read their mix operands back from LDS for the same fma chain, s ascending.
 #include "mtl_core.h"
+#include "train_common.h"
 
 namespace rk {
 
@@ -45,6 +51,8 @@ constexpr int kPlMaxTasks = 8;
 constexpr int kPlMaxStacks = 64;  // K ms + mc: the shared gate's columns (4 tiles)
 constexpr int kPlMaxDepth = 3;
 constexpr int kPlLdG = kPlMaxStacks + kMlpLdPad;
+
+__host__ __device__ constexpr int pad4(int v) { return (v + 3) / 4 * 4; }
 
 struct PleArgs {
   RowMap map;
@@ -62,7 +70,47 @@ struct PleArgs {
 };
 static_assert(sizeof(PleArgs) <= 4096, "kernel arguments beyond 4 KiB");
 
-__global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
+// The train forward's additions.  Every per-layer buffer holds the layer of all stacks (tasks) of a
+// level side by side: stack s of level j, layer l at columns s * p4(n_l) of eact[j * kPlMaxDepth + l]
+// [B, NE * p4(n_l)], tower k's layer l at columns k * p4(n_l) of tact[l]; the columns between a width and
+// its p4 hold zeros.  reps[j] is then [B, (K + 1) * p4(H)] ([B, K * p4(H)] at the last level), mixture i at
+// column i * p4(H); gates[j] keeps the eval layout.  Dropout site (j NE + s) De + l for expert s of level
+// j, layer l (its index in the table), L NE De + k Dt + l for tower k layer l; element (b, c) of a site's
+// [B, n] output is kept iff dropout_keep(seed + site, *slot, b n + c, threshold).
+struct PleTrainArgs : PleArgs {
+  float* x_out;
+  float* eact[kPlMaxLevels * kPlMaxDepth];
+  float* tact[kPlMaxDepth];
+  int ldx_out;
+  uint32_t threshold;
+  float scale;
+  uint64_t seed;
+  const int64_t* slot;
+};
+static_assert(sizeof(PleTrainArgs) <= 4096, "kernel arguments beyond 4 KiB");
+
+// A finished hidden layer in LDS (16 rows of n columns, stride ldh, after the layer's barrier) for the
+// train forward: dropout applied in place (the next layer reads it), the result stored to its column
+// block of the layer's HBM buffer, zeros up to the pitch.  All threads; the caller's barrier follows.
+__device__ __forceinline__ void pl_train_store(float* h, int ldh, int n, uint64_t key, uint64_t stream,
+                                               uint32_t threshold, float scale, float* dst, int64_t ld, int pitch,
+                                               int64_t m0, int rows, int tid) {
+  for (int i = tid; i < kMlpRows * pitch; i += kMlpThreads) {
+    const int row = i / pitch, c = i - row * pitch;
+    float y = 0.f;
+    if (c < n) {
+      y = h[row * ldh + c];
+      if (threshold) {
+        y = dropout_keep(key, stream, (uint64_t)(m0 + row) * n + c, threshold) ? y * scale : 0.f;
+        h[row * ldh + c] = y;
+      }
+    }
+    if (row < rows) dst[(m0 + row) * ld + c] = y;
+  }
+}
+
+template <bool TRAIN>
+__global__ __launch_bounds__(kMlpThreads) void ple_kernel(std::conditional_t<TRAIN, PleTrainArgs, PleArgs> a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
   const int64_t m0 = (int64_t)blockIdx.x * kMlpRows;
@@ -112,6 +160,15 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
     if (sg[i] != 255 && r[i] >= 0) {
       const rk_segment& g = a.map.segs[sg[i]];
       v[i] = g.src[r[i] * g.src_ld + a.map.col_off[lane + 64 * i]];
+    }
+  }
+  uint64_t stream = 0;
+  if constexpr (TRAIN) {
+    if (a.threshold) stream = (uint64_t)*a.slot;
+#pragma unroll
+    for (int i = 0; i < kRowCols / 64; ++i) {
+      const int c = lane + 64 * i;
+      if (live && c < a.ldx_out) a.x_out[b * a.ldx_out + c] = v[i];  // (zeros past the width)
     }
   }
   __builtin_amdgcn_sched_barrier(0);  // the gather's loads stay ahead of the weight ring
@@ -236,10 +293,35 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
         if (l + 1 < De) {
           mtl_layer(pipe, L, in, l == 0 ? a.ldr : a.ldh, out, a.ldh, Kp, wave, ln);
           mtl_prepare(pipe, N, nk, wave, ln);
+          if constexpr (TRAIN) {
+            close_layer();
+            const int pitch = pad4(L.n);
+            pl_train_store(out, a.ldh, L.n, a.seed + (uint64_t)((j * NE + s) * De + l), stream, a.threshold, a.scale,
+                           a.eact[j * kPlMaxDepth + l] + s * pitch, (int64_t)NE * pitch, pitch, m0, rows, tid);
+          }
         } else {
+          // (train: the last layer goes through LDS like the others, so that dropout and the store of f_s
+          // run after its barrier, as in mmoe_kernel<true>)
           f32x4_t z[2];
-          mtl_layer_tiles(pipe, L, in, l == 0 ? a.ldr : a.ldh, Kp, wave, ln, z);
+          if constexpr (TRAIN)
+            mtl_layer(pipe, L, in, l == 0 ? a.ldr : a.ldh, out, a.ldh, Kp, wave, ln);
+          else
+            mtl_layer_tiles(pipe, L, in, l == 0 ? a.ldr : a.ldh, Kp, wave, ln, z);
           if (has_next) mtl_prepare(pipe, N, nk, wave, ln);
+          if constexpr (TRAIN) {
+            close_layer();
+            const int pitch = pad4(H);
+            pl_train_store(out, a.ldh, H, a.seed + (uint64_t)((j * NE + s) * De + l), stream, a.threshold, a.scale,
+                           a.eact[j * kPlMaxDepth + l] + s * pitch, (int64_t)NE * pitch, pitch, m0, rows, tid);
+            mlp_lds_barrier();
+            const int q4 = (ln >> 4) * 4;  // the lane's first row
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              const int n = 16 * (wave + kMlpWaves * t) + (ln & 15);
+#pragma unroll
+              for (int q = 0; q < 4; ++q) z[t][q] = n < Hp ? out[(q4 + q) * a.ldh + n] : 0.f;
+            }
+          }
           // mixtures i0 .. i1 - 1 take this expert (a task's expert: its task, then the shared one below)
           const int i0 = owner < K ? owner : 0, i1 = owner < K ? owner + 1 : K;
           const int col = owner < K ? s - owner * ms : ms + (s - K * ms);  // its column of a task gate
@@ -255,6 +337,8 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
             mtl_mix(mt, gt, slot, gcol, first, z, Hp, wave, ln);
           }
         }
+        // (train: also the barrier pl_train_store relies on — its in-place dropout is complete before the
+        // next layer reads `out`, and the mix's LDS readback before the next expert overwrites it)
         close_layer();
       }
     }
@@ -267,7 +351,12 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
         float* const xi = xin + i * kMlpRows * a.ldr;
         mtl_unmix(mt, i, Hp, wave, lm, [&](int row, int n, float m) {
           xi[row * a.ldr + n] = m;
-          if (ro && n < H && row < rows) ro[((m0 + row) * (K + 1) + i) * H + n] = m;
+          if constexpr (TRAIN) {
+            const int pm = pad4(H);
+            if (n < pm && row < rows) ro[((m0 + row) * (K + 1) + i) * pm + n] = n < H ? m : 0.f;
+          } else {
+            if (ro && n < H && row < rows) ro[((m0 + row) * (K + 1) + i) * H + n] = m;
+          }
         });
       }
       mlp_lds_barrier();
@@ -281,7 +370,12 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
       const int lm = lane_now(lane);
       mtl_unmix(mt, k, Hp, wave, lm, [&](int row, int n, float m) {
         if (a.has_head) ha[row * a.ldh + n] = m;  // pad columns hold zeros: the tower's zero K pad
-        if (ro && n < H && row < rows) ro[((m0 + row) * K + k) * H + n] = m;
+        if constexpr (TRAIN) {
+          const int pm = pad4(H);
+          if (n < pm && row < rows) ro[((m0 + row) * K + k) * pm + n] = n < H ? m : 0.f;
+        } else {
+          if (ro && n < H && row < rows) ro[((m0 + row) * K + k) * H + n] = m;
+        }
       });
       if (!a.has_head) continue;
       mlp_lds_barrier();
@@ -300,6 +394,12 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
           mtl_prepare(pipe, N, H, wave, ln);
         }
         close_layer();
+        if constexpr (TRAIN) {
+          const int pitch = pad4(L.n);
+          pl_train_store(out, a.ldh, L.n, a.seed + (uint64_t)(gate0 + k * Dt + l), stream, a.threshold, a.scale,
+                         a.tact[l] + k * pitch, (int64_t)K * pitch, pitch, m0, rows, tid);
+          mlp_lds_barrier();
+        }
       }
       const float* fin = (Dt & 1) ? hb : ha;
       const int Kh = Dt ? tun(Dt - 1) : H;
@@ -323,12 +423,23 @@ __global__ __launch_bounds__(kMlpThreads) void ple_kernel(PleArgs a) {
 
 using namespace rk;
 
-RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
-                          int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
-                          int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
-                          const rk_mmoe_layer* table, int64_t table_len, float* logits, float* probs,
-                          float* const* level_reps, float* const* level_gates, void* stream) {
-  const char* const name = "rk_ple_forward";
+namespace {
+
+// The train entry's own arguments (null for the eval entry).
+struct TrainOut {
+  double p;
+  uint64_t seed;
+  const int64_t* slot;
+  float* x_out;
+  float* const* expert_acts;  // [j * expert_depth + l]
+  float* const* tower_acts;
+};
+
+int ple_launch(const char* name, const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
+               int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
+               int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
+               const rk_mmoe_layer* table, int64_t table_len, float* logits, float* probs, float* const* level_reps,
+               float* const* level_gates, const TrainOut* train, void* stream) {
   if (!segs || !table || !expert_units || batch < 0 || nseg <= 0 || width <= 0 || num_levels <= 0 || num_tasks <= 0 ||
       num_specific < 0 || num_shared <= 0 || expert_depth <= 0 || tower_depth < 0 || (tower_depth > 0 && !tower_units) ||
       (tower_depth > 0 && !has_heads))
@@ -345,7 +456,7 @@ RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, i
   bool any_out = logits || probs;
   for (int j = 0; j < L; ++j) any_out = any_out || (level_reps && level_reps[j]) || (level_gates && level_gates[j]);
   if (!any_out) return fail(RK_ERR_INVALID, "%s: no output", name);
-  PleArgs a = {};
+  PleTrainArgs a = {};
   int wide = kMlpPad;  // the widest hidden activation, padded
   for (int l = 0; l < De + Dt; ++l) {
     const int n = l < De ? expert_units[l] : tower_units[l - De];
@@ -389,10 +500,67 @@ RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, i
   if (shm > 160 * 1024) return fail(RK_ERR_UNSUPPORTED, "%s: this shape needs %zu B of LDS (<= %d)", name, shm, 160 * 1024);
   a.flags = device_flags();
   if (!a.flags) return fail(RK_ERR_RUNTIME, "%s: device not initialised (rk_init)", name);
+  if (train) {
+    if (!(train->p >= 0.0 && train->p < 1.0) || (train->p > 0.0 && !train->slot) || !train->x_out || !train->expert_acts ||
+        (Dt > 0 && !train->tower_acts) || !level_reps || !level_gates || (has_heads && (!logits || !probs)))
+      return fail(RK_ERR_INVALID, "%s: dropout_p outside [0, 1), or a null stream slot / saved buffer", name);
+    if (!aligned16(train->x_out) || !aligned16(logits) || !aligned16(probs))
+      return fail(RK_ERR_INVALID, "%s: x_out / logits / probs misaligned", name);
+    for (int j = 0; j < L; ++j) {
+      if (!level_reps[j] || !level_gates[j] || !aligned16(level_reps[j]) || !aligned16(level_gates[j]))
+        return fail(RK_ERR_INVALID, "%s: level_reps[%d] / level_gates[%d] null or misaligned", name, j, j);
+      for (int l = 0; l < De; ++l) {
+        float* const p = train->expert_acts[j * De + l];
+        if (!p || !aligned16(p)) return fail(RK_ERR_INVALID, "%s: expert_acts[%d] null or misaligned", name, j * De + l);
+        a.eact[j * kPlMaxDepth + l] = p;
+      }
+    }
+    for (int l = 0; l < Dt; ++l) {
+      if (!train->tower_acts[l] || !aligned16(train->tower_acts[l]))
+        return fail(RK_ERR_INVALID, "%s: tower_acts[%d] null or misaligned", name, l);
+      a.tact[l] = train->tower_acts[l];
+    }
+    a.x_out = train->x_out;
+    a.ldx_out = pad4(width);
+    a.threshold = dropout_threshold(train->p);
+    a.scale = (float)(1.0 / (1.0 - train->p));
+    a.seed = train->seed;
+    a.slot = train->slot;
+  }
   if (batch == 0) return RK_OK;
   const int64_t blocks = (batch + kMlpRows - 1) / kMlpRows;
   if (blocks > INT32_MAX) return fail(RK_ERR_UNSUPPORTED, "%s: batch too large", name);
-  raise_lds_limit((const void*)ple_kernel, 160 * 1024);
-  ple_kernel<<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(a);
+  if (train) {
+    raise_lds_limit((const void*)ple_kernel<true>, 160 * 1024);
+    ple_kernel<true><<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(a);
+  } else {
+    raise_lds_limit((const void*)ple_kernel<false>, 160 * 1024);
+    ple_kernel<false><<<(unsigned)blocks, kMlpThreads, shm, (hipStream_t)stream>>>(static_cast<const PleArgs&>(a));
+  }
   return check_launch(name);
+}
+
+}  // namespace
+
+RK_API int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
+                          int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
+                          int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
+                          const rk_mmoe_layer* table, int64_t table_len, float* logits, float* probs,
+                          float* const* level_reps, float* const* level_gates, void* stream) {
+  return ple_launch("rk_ple_forward", segs, nseg, width, batch, num_levels, num_tasks, num_specific, num_shared,
+                    expert_units, expert_depth, tower_units, tower_depth, has_heads, table, table_len, logits, probs,
+                    level_reps, level_gates, nullptr, stream);
+}
+
+RK_API int rk_ple_forward_train(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
+                                int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
+                                int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
+                                const rk_mmoe_layer* table, int64_t table_len, double dropout_p, uint64_t seed,
+                                const int64_t* stream_slot, float* x_out, float* const* expert_acts,
+                                float* const* tower_acts, float* logits, float* probs, float* const* level_reps,
+                                float* const* level_gates, void* stream) {
+  const TrainOut t = {dropout_p, seed, stream_slot, x_out, expert_acts, tower_acts};
+  return ple_launch("rk_ple_forward_train", segs, nseg, width, batch, num_levels, num_tasks, num_specific, num_shared,
+                    expert_units, expert_depth, tower_units, tower_depth, has_heads, table, table_len, logits, probs,
+                    level_reps, level_gates, &t, stream);
 }

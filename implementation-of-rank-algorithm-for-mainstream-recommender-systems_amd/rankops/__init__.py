@@ -25,7 +25,9 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
     PLE, ple                               PLE, progressive layered extraction (the multi-task list's third
                                            model, no script in the reference): L levels of task and shared
                                            experts and gates, the whole eval forward in one launch
-                                           (rk_ple_forward); rankops.ple is the module and, called, the op
+                                           (rk_ple_forward); rankops.ple is the module and, called, the op;
+                                           trainable=True trains (rk_ple_forward_train, rk_ple_mix_backward
+                                           and the grouped Linear backwards), ple is differentiable
 
 `rankops.sharded.ShardedDeepFM` adds the table-sharded multi-GPU DeepFM lookup (RCCL
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the

@@ -22,7 +22,7 @@ RK_ERR_UNSUPPORTED = 4  # include/rankops.h
 RK_FLAG_INDEX_OOB = 1
 RK_ACT_NONE, RK_ACT_RELU, RK_ACT_LEAKY, RK_ACT_DICE, RK_ACT_PRELU = 0, 1, 2, 3, 4
 RK_MAX_SEGMENTS = 64
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class Segment(ctypes.Structure):
@@ -448,6 +448,15 @@ SIGNATURES = {
     "rk_ple_forward": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
                                       POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, c_int32, c_void_p, c_int64,
                                       c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    "rk_ple_forward_train": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                            POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, c_int32, c_void_p,
+                                            c_int64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p,
+                                            POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, POINTER(c_void_p),
+                                            POINTER(c_void_p), c_void_p]),
+    "rk_ple_mix_backward": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                           c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_float, c_void_p,
+                                           c_int64, POINTER(c_int32), c_void_p, c_int64, POINTER(c_int32), c_int32,
+                                           c_void_p]),
     "rk_mlp_pack_weights": (ctypes.c_int, [POINTER(PackItem), c_int32, c_void_p]),
     "rk_mmoe_forward_train": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
                                              c_void_p, c_void_p, c_int32, POINTER(MmoeLayer), c_int32, POINTER(c_void_p),

@@ -42,11 +42,9 @@ module and that function.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
-from . import common, ops, train
-from .common import check_eval
+from . import common, ops
 from .multitask import DEFAULT_TASKS, MultiTask, _stack
 
 
@@ -86,16 +84,6 @@ class MMoE(MultiTask):
         args, keep = ops.mmoe_forward_args(segs, self.input_dim, B, stacks, gate_image, gate_b, len(self.task_names),
                                            towers, heads, dev)
         return args, (keep, stacks, towers, gate_w, gate_b, gate_image)
-
-    def forward(self, dense, category):
-        if not self.trainable:
-            check_eval(self)  # train mode is opt-in (trainable=True)
-        dense, names, idx = self._inputs(dense, category)
-        if self.training:  # Dropout live, HIP backward (rankops.train); an empty batch: zero gradients
-            self._check(dense.shape[0], idx)
-            grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-            return train.mmoe_train_forward(self, dense, names, idx, grad)
-        return self._eval_forward(dense, names, idx, category)
 
 
 common.callable_module(__name__, ops.mmoe)  # rankops.mmoe(x, experts, gates, towers=None)

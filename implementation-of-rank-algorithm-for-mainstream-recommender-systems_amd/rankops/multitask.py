@@ -5,14 +5,17 @@ that is one launch returning (probabilities [B, K], logits [B, K]).
 A model supplies NAME (its name in messages), ENTRY (the C entry point of that launch) and
 LOGITS_SLOT / PROBS_SLOT (the two outputs' positions in its argument list), `fits()`, and
 `_launch_args(segs, B, dev, image, pin)`, the launch's argument list over the row segments `segs` with
-what it must keep alive.  Its __init__ calls this one first (embeddings are the first modules created),
+what it must keep alive.  Training is opt-in per instance (`trainable`, `sparse_grad`, set by the model's
+constructor): train mode then runs rankops.train.multitask_train_forward, which finds the model's train
+forward, autograd function and parameter list by NAME.  Its __init__ calls this one first (embeddings are the first modules created),
 then creates its experts and gates, then calls `_make_towers`.
 """
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 
-from . import common, ops
+from . import common, ops, train
 from .common import EngineModule, check_eval, table_rows
 
 DEFAULT_TASKS = ("read_comment", "like", "click_avatar")
@@ -30,6 +33,7 @@ def _stack(width, units, dropout_rate):
 
 class MultiTask(EngineModule):
     NAME = ENTRY = LOGITS_SLOT = PROBS_SLOT = None
+    trainable = sparse_grad = False
 
     def __init__(self, vocab_dir, expert_hidden_units, tower_hidden_units, task_names, dropout_rate, vocab_sizes):
         super().__init__()
@@ -157,5 +161,11 @@ class MultiTask(EngineModule):
         return out
 
     def forward(self, dense, category):
-        check_eval(self)
-        return self._eval_forward(*self._inputs(dense, category), category)
+        if not self.trainable:
+            check_eval(self)  # train mode is opt-in (trainable=True)
+        dense, names, idx = self._inputs(dense, category)
+        if self.training:  # Dropout live, HIP backward (rankops.train); an empty batch: zero gradients
+            self._check(dense.shape[0], idx)
+            grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+            return train.multitask_train_forward(self, dense, names, idx, grad)
+        return self._eval_forward(dense, names, idx, category)

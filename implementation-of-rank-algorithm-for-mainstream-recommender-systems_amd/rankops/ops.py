@@ -1826,35 +1826,34 @@ def mmoe_forward_train(segs, sh: MmoeShape, B, stacks, gate_image, gate_bias, ts
     return s
 
 
-def mmoe_backward(sh: MmoeShape, B, s, wst, experts, gates, towers, p, d_mixed, d_logits, d_probs, need_dx, device):
-    """The MMoE backward from the buffers of mmoe_forward_train (s), the stacked layer-0 / gate weight
-    (wst) and the plain weights (experts: E lists of (W, b); gates: K (W, b); towers: K (hidden, (w, b)) or
-    None).  d_mixed [B, K, H], d_logits, d_probs [B, K]: the incoming gradients, each may be None.
-    Returns (dx [B, width] or None, expert grads [[(dW, db)…]…], gate grads [(dW, db)…], tower grads
-    [([(dW, db)…], (dw, db))…] or None); a db is returned for every layer (callers drop those of bias-free
-    layers).  The launches do not depend on E or K: per layer one rk_gemm_wgrad_grouped and one
-    rk_gemm_grouped over the experts (tasks); layer 0 of all experts and the gates as one rk_gemm_wgrad and
-    one rk_gemm; no float atomics, fixed-order sums."""
-    E, K, H, width = sh.E, sh.K, sh.H, sh.width
-    De, Dt = len(sh.eu), len(sh.tu)
-    pe, pt, pm, w4 = [p4(n) for n in sh.eu], [p4(n) for n in sh.tu], p4(H), p4(width)
-    f32 = dict(device=device, dtype=torch.float32)
-    # Pad columns: the head and mix kernels write zeros into theirs; rk_gemm_grouped leaves those of its
-    # outputs unwritten, which only reach rows of padded weight gradients that are cut away (the next
-    # grouped GEMM reduces over the exact width).  dZ0's own pad columns are read by the stacked data
-    # gradient, so dZ0 is zero-filled when it has any.
-    new = torch.empty
-    st = _lib.raw_stream(device)
-    scale = 1.0 / (1.0 - p)
+def _wgrad(B, N, Kd, A, lda, Bm, ldb, device, st):
+    """One rk_gemm_wgrad over the B rows: (dW [N, Kd] = A^T Bm, db [N] = A's column sums); A and Bm may be
+    column blocks of wider buffers (views: their addresses, lda / ldb the row strides)."""
     lib = _lib.load()
+    f32 = dict(device=device, dtype=torch.float32)
+    dW, db = torch.empty(N, Kd, **f32), torch.empty(N, **f32)
+    nws = _wgrad_ws_floats(lib, N, Kd, B)
+    ws = _wgrad_workspace(nws, device, st)
+    check(lib.rk_gemm_wgrad(N, Kd, B, A.data_ptr(), lda, None, Bm.data_ptr(), ldb, dW.data_ptr(), Kd, db.data_ptr(), 0,
+                            ws.data_ptr(), ws.numel(), st), "rk_gemm_wgrad")
+    return dW, db
+
+
+def mtl_tower_backward(K, H, tu, B, tacts, mixed, probs, towers, scale, d_mixed, d_logits, d_probs, device, st):
+    """The heads and towers of a multi-task model (MMoE, PLE), backward: rk_mmoe_head_backward, one
+    rk_gemm_wgrad for the heads and per tower layer the grouped pair over the K tasks.  tacts, mixed
+    [B, K p4(H)], probs: the train forward's buffers; towers: K (hidden [(W, b)…], (w, b)) or None;
+    d_mixed [B, K, H], d_logits, d_probs [B, K]: the incoming gradients, each may be None.  Returns (the
+    gradient of the mixtures [B, K p4(H)] — a private buffer —, tower grads [([(dW, db)…], (dw, db))…] or
+    None)."""
+    tu = tuple(tu)
+    Dt = len(tu)
+    pt, pm = [p4(n) for n in tu], p4(H)
+    f32 = dict(device=device, dtype=torch.float32)
+    new = torch.empty
 
     def wgrad(N, Kd, A, lda, Bm, ldb):
-        dW, db = torch.empty(N, Kd, **f32), torch.empty(N, **f32)
-        nws = _wgrad_ws_floats(lib, N, Kd, B)
-        ws = _wgrad_workspace(nws, device, st)
-        check(lib.rk_gemm_wgrad(N, Kd, B, A.data_ptr(), lda, None, Bm.data_ptr(), ldb, dW.data_ptr(), Kd, db.data_ptr(), 0,
-                                ws.data_ptr(), ws.numel(), st), "rk_gemm_wgrad")
-        return dW, db
+        return _wgrad(B, N, Kd, A, lda, Bm, ldb, device, st)
 
     def incoming():  # d_mixed [B, K, H] in the saved layout [B, K pm], a private copy (it is added to)
         if pm == H:
@@ -1866,20 +1865,20 @@ def mmoe_backward(sh: MmoeShape, B, s, wst, experts, gates, towers, p, d_mixed, 
     tower_grads = None
     dmix = None
     if towers is not None and (d_logits is not None or d_probs is not None):
-        last, plast = (sh.tu[-1], pt[-1]) if Dt else (H, pm)
-        feed = s["tacts"][-1] if Dt else s["mixed"]            # the heads' input, [B, K plast]
+        last, plast = (tu[-1], pt[-1]) if Dt else (H, pm)
+        feed = tacts[-1] if Dt else mixed            # the heads' input, [B, K plast]
         pk = p4(K)
         g = torch.empty(B, pk, **f32)
         own = Dt == 0 and d_mixed is not None
         dz = incoming() if own else new(B, K * plast, **f32)
-        mmoe_head_backward(B, K, last, plast, d_logits, d_probs, s["probs"], [w for _, (w, _) in towers],
-                           s["tacts"][-1] if Dt else None, scale, g, dz, own, st)
+        mmoe_head_backward(B, K, last, plast, d_logits, d_probs, probs, [w for _, (w, _) in towers],
+                           tacts[-1] if Dt else None, scale, g, dz, own, st)
         hd, hb = wgrad(pk, K * plast, g, pk, feed, K * plast)  # the heads' dw are its diagonal blocks
         head_grads = [(hd[k, k * plast:k * plast + last].view(1, last), hb[k:k + 1]) for k in range(K)]
         hidden_grads = [[None] * Dt for _ in range(K)]
         for l in range(Dt - 1, -1, -1):
-            n, n_in, p_in = sh.tu[l], (sh.tu[l - 1] if l else H), (pt[l - 1] if l else pm)
-            inp = s["tacts"][l - 1] if l else s["mixed"]
+            n, n_in, p_in = tu[l], (tu[l - 1] if l else H), (pt[l - 1] if l else pm)
+            inp = tacts[l - 1] if l else mixed
             dW, db = torch.empty(K, pt[l], p4(n_in), **f32), torch.empty(K, pt[l], **f32)
             gemm_wgrad_grouped(pt[l], p4(n_in), B, [fptr(dz, k * pt[l]) for k in range(K)], K * pt[l],
                                [fptr(inp, k * p_in) for k in range(K)], K * p_in, [dW[k].data_ptr() for k in range(K)],
@@ -1904,6 +1903,36 @@ def mmoe_backward(sh: MmoeShape, B, s, wst, experts, gates, towers, p, d_mixed, 
                         (torch.zeros_like(w), torch.zeros(1, **f32))) for hidden, (w, _) in towers]
     if dmix is None:
         dmix = torch.zeros(B, K * pm, **f32)
+    return dmix, tower_grads
+
+
+def mmoe_backward(sh: MmoeShape, B, s, wst, experts, gates, towers, p, d_mixed, d_logits, d_probs, need_dx, device):
+    """The MMoE backward from the buffers of mmoe_forward_train (s), the stacked layer-0 / gate weight
+    (wst) and the plain weights (experts: E lists of (W, b); gates: K (W, b); towers: K (hidden, (w, b)) or
+    None).  d_mixed [B, K, H], d_logits, d_probs [B, K]: the incoming gradients, each may be None.
+    Returns (dx [B, width] or None, expert grads [[(dW, db)…]…], gate grads [(dW, db)…], tower grads
+    [([(dW, db)…], (dw, db))…] or None); a db is returned for every layer (callers drop those of bias-free
+    layers).  The launches do not depend on E or K: per layer one rk_gemm_wgrad_grouped and one
+    rk_gemm_grouped over the experts (tasks); layer 0 of all experts and the gates as one rk_gemm_wgrad and
+    one rk_gemm; no float atomics, fixed-order sums."""
+    E, K, H, width = sh.E, sh.K, sh.H, sh.width
+    De, Dt = len(sh.eu), len(sh.tu)
+    pe, pm, w4 = [p4(n) for n in sh.eu], p4(H), p4(width)
+    f32 = dict(device=device, dtype=torch.float32)
+    # Pad columns: the head and mix kernels write zeros into theirs; rk_gemm_grouped leaves those of its
+    # outputs unwritten, which only reach rows of padded weight gradients that are cut away (the next
+    # grouped GEMM reduces over the exact width).  dZ0's own pad columns are read by the stacked data
+    # gradient, so dZ0 is zero-filled when it has any.
+    new = torch.empty
+    st = _lib.raw_stream(device)
+    scale = 1.0 / (1.0 - p)
+
+    def wgrad(N, Kd, A, lda, Bm, ldb):
+        return _wgrad(B, N, Kd, A, lda, Bm, ldb, device, st)
+
+    # heads and towers (shared with ple_backward)
+    dmix, tower_grads = mtl_tower_backward(K, H, sh.tu, B, s["tacts"], s["mixed"], s["probs"], towers, scale, d_mixed,
+                                           d_logits, d_probs, device, st)
 
     # the mix and the gates' softmax; with one expert layer its dz goes straight into dZ0
     dZ0 = (torch.zeros if sh.zw_padded else torch.empty)(B, sh.zw, **f32)
@@ -2170,7 +2199,12 @@ def ple(x: torch.Tensor, levels, towers=None, return_levels=False):
     Returns (logits [B, K], probs [B, K]) with towers, else the last level's (representations [B, K, H],
     gates [B, K, ms + mc]).  return_levels=True appends (with towers) or returns instead (without) the list
     over the levels of (representations [B, K + 1, H] — the tasks', then the shared one; [B, K, H] at the
-    last level —, task gates [B, K, ms + mc], shared gate [B, K ms + mc] or None)."""
+    last level —, task gates [B, K, ms + mc], shared gate [B, K ms + mc] or None).
+    Differentiable whenever grad is enabled and x or any weight or bias requires grad (rk_ple_forward_train
+    without dropout and ple_backward, DESIGN.md §4e "Training"): gradients for x and every (W, b) from the
+    incoming gradients of logits, probs and the last level's representations.  A gradient flowing into a
+    gate output or into a lower level's representations raises NotImplementedError.  With nothing requiring
+    grad the call is the eval launch, bit for bit."""
     as_f32(x, "x")
     if x.dim() != 2 or x.stride(1) != 1:
         raise ValueError(f"rankops.ple: x must be [B, width] with unit column stride, got {tuple(x.shape)}")
@@ -2227,6 +2261,10 @@ def ple(x: torch.Tensor, levels, towers=None, return_levels=False):
     from . import common
     if not common.ple_fits(width, (width + 127) // 128, L, K, ms, mc, eu, tu):
         raise RuntimeError("rankops.ple: configuration outside rk_ple_forward's envelope (common.ple_fits)")
+    flat = _ple_flat(levels, towers)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x] + flat):
+        return _ple_autograd(x, flat, PleShape(width, L, K, ms, mc, eu, tu, towers is not None), experts, gate_entries,
+                             tower_entries, heads, return_levels)
     want = return_levels or towers is None
     GT = ms + mc
     reps = [torch.empty(B, K + (j < L - 1), H, device=dev, dtype=torch.float32) if want and (return_levels or j == L - 1)
@@ -2258,4 +2296,326 @@ def ple(x: torch.Tensor, levels, towers=None, return_levels=False):
         return (reps[j], g[:, :K * GT].view(B, K, GT), g[:, K * GT:] if j < L - 1 else None)
     if towers is None:
         return [split(j) for j in range(L)] if return_levels else split(L - 1)[:2]
+    return (logits, probs, [split(j) for j in range(L)]) if return_levels else (logits, probs)
+
+
+# ---------------------------------------------------------------- PLE training ("Training")
+
+class PleShape:
+    """Widths of one PLE (L levels of K x ms task stacks and mc shared ones, units eu; K towers of units tu)
+    and the column layout of every level's dZ0, the buffer that holds the gradients of all the level's
+    first-layer pre-activations and gate logits side by side (every block on the 4 grid, zeros between):
+
+        level 0     [dz_{0,0} … dz_{NE-1,0} | dgl_0 … dgl_{K-1} | dgl_K]      every stack and gate reads x
+        level j>=1  K task blocks [dz_{s,0} of the task's ms stacks | dgl_q], then the shared block
+                    [dz_{s,0} of the mc shared stacks | dgl_K]                 owner q reads x_q^{j-1}
+
+    (dgl_K, the shared gate's, is absent at the last level)."""
+
+    def __init__(self, width, L, K, ms, mc, eu, tu, heads: bool):
+        self.width, self.L, self.K, self.ms, self.mc = width, L, K, ms, mc
+        self.eu, self.tu, self.heads = tuple(eu), tuple(tu), heads
+        self.H, self.NE, self.GT = self.eu[-1], K * ms + mc, ms + mc
+
+    def nq(self, j):
+        return self.K + (j < self.L - 1)
+
+    def gcols(self, j):
+        return self.K * self.GT + (self.NE if j < self.L - 1 else 0)
+
+    def layout(self, j):
+        """(columns of dZ0^j, stack offsets [NE], gate offsets [nq], task block width, shared block width)."""
+        K, ms, mc, NE, pe0, pg = self.K, self.ms, self.mc, self.NE, p4(self.eu[0]), p4(self.GT)
+        ps = p4(NE) if j < self.L - 1 else 0
+        if j == 0:
+            soff = [s * pe0 for s in range(NE)]
+            goff = [NE * pe0 + q * pg for q in range(self.nq(0))]
+            return NE * pe0 + K * pg + ps, soff, goff, 0, 0
+        bw_t, bw_s = ms * pe0 + pg, mc * pe0 + ps
+        soff = [q * bw_t + i * pe0 for q in range(K) for i in range(ms)] + [K * bw_t + i * pe0 for i in range(mc)]
+        goff = [q * bw_t + ms * pe0 for q in range(K)] + ([K * bw_t + mc * pe0] if ps else [])
+        return K * bw_t + bw_s, soff, goff, bw_t, bw_s
+
+    def padded(self):
+        """dZ0 has pad columns that no kernel writes: those behind a first layer off the 4 grid that
+        rk_gemm_grouped fills (rk_ple_mix_backward writes zeros into the pad columns of everything it
+        stores, the gates' included).  It is then zero-filled: the stacked data gradient reads them."""
+        return bool(self.eu[0] % 4 and len(self.eu) > 1)
+
+
+def _ple_flat(levels, towers):
+    """Every weight and bias of rankops.ple's arguments in a fixed order (None for an absent bias): per
+    level the stacks' layers (stack-major), the K gates, the shared gate; then the towers."""
+    flat = []
+    for specific, shared, gates, shared_gate in levels:
+        flat += [t for task in specific for layers in task for wb in layers for t in wb]
+        flat += [t for layers in shared for wb in layers for t in wb]
+        flat += [t for wb in gates for t in wb]
+        if shared_gate is not None:
+            flat += list(shared_gate)
+    if towers is not None:
+        flat += [t for hidden, out in towers for wb in list(hidden) + [out] for t in wb]
+    return flat
+
+
+def ple_level_lists(sh: PleShape, experts, gate_entries):
+    """[(stacks [NE][De] of (W, b), gates [nq] of (W, b))…] from the layer table's flat order."""
+    De, NE, K = len(sh.eu), sh.NE, sh.K
+    return [([[experts[(j * NE + s) * De + l] for l in range(De)] for s in range(NE)],
+             [gate_entries[j * (K + 1) + q] for q in range(sh.nq(j))]) for j in range(sh.L)]
+
+
+def ple_stacked_weights(sh: PleShape, levels):
+    """The stacked first-layer / gate weights behind dZ0 (PleShape), rows and columns on the 4 grid with
+    zeros between: level 0 one [zw, p4(width)] matrix; level j >= 1 (task owners [K, bw_t, p4(H)], shared owner
+    [bw_s, p4(H)]).  A fixed number of launches per level whatever K, ms and mc."""
+    K, ms, mc, pe0, n0 = sh.K, sh.ms, sh.mc, p4(sh.eu[0]), sh.eu[0]
+    pad = torch.nn.functional.pad
+
+    def block(ws, n, k_in):  # count weights [n, k_in] -> [count, p4(n), p4(k_in)]
+        # (padded even when on the grid: whether ms + mc or K ms + mc is must not change the launch list)
+        return pad(torch.stack(ws, 0), (0, p4(k_in) - k_in, 0, p4(n) - n))
+    out = []
+    for j, (stacks, gates) in enumerate(levels):
+        k_in = sh.width if j == 0 else sh.H
+        kp = p4(k_in)
+        first = [layers[0][0] for layers in stacks]
+        tg = block([w for w, _ in gates[:K]], sh.GT, k_in)
+        shared = [block(first[K * ms:], n0, k_in).view(mc * pe0, kp)]
+        if len(gates) > K:
+            shared.append(block([gates[K][0]], sh.NE, k_in)[0])
+        task = block(first[:K * ms], n0, k_in) if ms else None
+        if j == 0:
+            parts = ([task.view(K * ms * pe0, kp)] if ms else []) + [shared[0], tg.view(K * p4(sh.GT), kp)] + shared[1:]
+            out.append(torch.cat(parts, 0))
+        else:
+            wt = torch.cat([task.view(K, ms * pe0, kp), tg], 1) if ms else tg.contiguous()
+            out.append((wt, torch.cat(shared, 0) if len(shared) > 1 else shared[0]))
+    return out
+
+
+def ple_forward_train(segs, sh: PleShape, B, entries, device, p, seed, slot):
+    """rk_ple_forward_train: one launch; returns the saved buffers (include/rankops.h) as a dict."""
+    new = torch.empty  # (the kernel writes the pad columns)
+    f32 = dict(device=device, dtype=torch.float32)
+    L, K, NE, pm = sh.L, sh.K, sh.NE, p4(sh.H)
+    s = dict(x=new(B, p4(sh.width), **f32), eacts=[[new(B, NE * p4(n), **f32) for n in sh.eu] for _ in range(L)],
+             tacts=[new(B, K * p4(n), **f32) for n in sh.tu], reps=[new(B, sh.nq(j) * pm, **f32) for j in range(L)],
+             gates=[new(B, sh.gcols(j), **f32) for j in range(L)], logits=None, probs=None)
+    if sh.heads:
+        s["logits"], s["probs"] = new(B, K, **f32), new(B, K, **f32)
+    if B == 0:
+        return s
+    args, keep = ple_forward_args(segs, sh.width, B, L, K, sh.ms, sh.mc, sh.eu, sh.tu, entries, sh.heads, device)
+    ea = _ptrs([t.data_ptr() for lv in s["eacts"] for t in lv])
+    ta = _ptrs([t.data_ptr() for t in s["tacts"]]) if sh.tu else None
+    call = args[:15] + [float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(slot), s["x"].data_ptr(), ea, ta, ptr(s["logits"]),
+                        ptr(s["probs"]), _ptrs([t.data_ptr() for t in s["reps"]]),
+                        _ptrs([t.data_ptr() for t in s["gates"]]), _lib.raw_stream(device)]
+    check(_lib.load().rk_ple_forward_train(*call), "rk_ple_forward_train")
+    return s
+
+
+def ple_mix_backward(B, K, ms, mc, has_shared_mix, H, dm, ld_dm, pitch_dm, f, ld_f, pitch_f, gates, ld_gates, mask_scale,
+                     dgl, ld_dgl, gate_offsets, dz, ld_dz, stack_offsets, pitch_dz, stream):
+    """rk_ple_mix_backward; dm, f, gates, dgl, dz are device addresses or tensors, the offsets lists of ints."""
+    a = [t.data_ptr() if isinstance(t, torch.Tensor) else t for t in (dm, f, gates, dgl, dz)]
+    go = (ctypes.c_int32 * max(1, len(gate_offsets)))(*gate_offsets)
+    so = (ctypes.c_int32 * max(1, len(stack_offsets)))(*stack_offsets)
+    check(_lib.load().rk_ple_mix_backward(B, K, ms, mc, int(bool(has_shared_mix)), H, a[0], ld_dm, pitch_dm, a[1], ld_f,
+                                          pitch_f, a[2], ld_gates, mask_scale, a[3], ld_dgl, go, a[4], ld_dz, so,
+                                          pitch_dz, stream), "rk_ple_mix_backward")
+
+
+def ple_backward(sh: PleShape, B, s, wst, levels, towers, p, d_reps, d_logits, d_probs, need_dx, device):
+    """The PLE backward from the buffers of ple_forward_train (s), the stacked first-layer / gate weights
+    (wst, ple_stacked_weights) and the plain weights (levels: ple_level_lists' form; towers: K (hidden,
+    (w, b)) or None).  d_reps [B, K, H] (into the last level's representations), d_logits, d_probs [B, K]:
+    the incoming gradients, each may be None.  Returns (dx [B, width] or None, per level (stack grads
+    [[(dW, db)…]…], gate grads [(dW, db)…]), tower grads or None); a db is returned for every layer.
+    Heads and towers as MMoE's (mtl_tower_backward); then per level, going down: rk_ple_mix_backward,
+    per expert layer above the first the grouped pair over the level's stacks in chunks of 16, and
+    layer 0 with the gates through dZ0 (PleShape) — level 0 as one rk_gemm_wgrad and one rk_gemm against
+    x, a later level as one rk_gemm_wgrad_grouped + rk_gemm_grouped over the K task owners and one
+    rk_gemm_wgrad + rk_gemm for the shared owner, which write the gradient of the level below's
+    representations.  The launches depend on L, De, Dt and ceil(NE / 16) only; no float atomics,
+    fixed-order sums."""
+    L, K, ms, mc, NE, GT, H, width = sh.L, sh.K, sh.ms, sh.mc, sh.NE, sh.GT, sh.H, sh.width
+    De = len(sh.eu)
+    pe, pm, w4, n0 = [p4(n) for n in sh.eu], p4(H), p4(width), sh.eu[0]
+    pe0, pg = pe[0], p4(GT)
+    f32 = dict(device=device, dtype=torch.float32)
+    # Pad columns: as in mmoe_backward (the mix kernel writes zeros into its own, rk_gemm_grouped leaves those
+    # of its outputs unwritten, which only reach cut-away rows of padded weight gradients; dZ0's are read by
+    # the stacked data gradient, so a dZ0 that has any is zero-filled).
+    new = torch.empty
+    st = _lib.raw_stream(device)
+    scale = 1.0 / (1.0 - p)
+    dR, tower_grads = mtl_tower_backward(K, H, sh.tu, B, s["tacts"], s["reps"][L - 1], s["probs"], towers, scale, d_reps,
+                                         d_logits, d_probs, device, st)
+    level_grads = [None] * L
+    dx = None
+    for j in range(L - 1, -1, -1):
+        stacks, gates = levels[j]
+        nq = sh.nq(j)
+        zw, soff, goff, bw_t, bw_s = sh.layout(j)
+        dZ0 = (torch.zeros if sh.padded() else new)(B, zw, **f32)
+        if De == 1:
+            dz, ld_dz, zoff = dZ0, zw, soff
+        else:
+            dz, ld_dz, zoff = new(B, NE * pe[-1], **f32), NE * pe[-1], [i * pe[-1] for i in range(NE)]
+        ple_mix_backward(B, K, ms, mc, nq > K, H, dR, nq * pm, pm, s["eacts"][j][-1], NE * pe[-1], pe[-1], s["gates"][j],
+                         sh.gcols(j), scale, dZ0, zw, goff, dz, ld_dz, zoff, pe[-1], st)
+        sg = [[None] * De for _ in range(NE)]
+        for l in range(De - 1, 0, -1):
+            n, n_in = sh.eu[l], sh.eu[l - 1]
+            inp, ld_inp = s["eacts"][j][l - 1], NE * pe[l - 1]
+            dW, db = new(NE, pe[l], pe[l - 1], **f32), new(NE, pe[l], **f32)
+            if l == 1:
+                d_in, ld_in, ioff = dZ0, zw, soff
+            else:
+                d_in, ld_in, ioff = new(B, ld_inp, **f32), ld_inp, [i * pe[l - 1] for i in range(NE)]
+            for c0 in range(0, NE, 16):  # (rk_gemm_grouped takes 16 groups)
+                ss = range(c0, min(NE, c0 + 16))
+                A = [fptr(dz, zoff[i]) for i in ss]
+                X = [fptr(inp, i * pe[l - 1]) for i in ss]
+                gemm_wgrad_grouped(pe[l], pe[l - 1], B, A, ld_dz, X, ld_inp, [dW[i].data_ptr() for i in ss], pe[l - 1],
+                                   [db[i].data_ptr() for i in ss], device, st)
+                ws_ = [stacks[i][l][0] for i in ss]
+                gemm_grouped(False, True, B, n_in, n, A, ld_dz, [w.data_ptr() for w in ws_], ws_[0].stride(0),
+                             [fptr(d_in, ioff[i]) for i in ss], ld_in, st, C_mask=X, ldmask=ld_inp, mask_scale=scale)
+            dW, db = dW[:, :n, :n_in].contiguous(), db[:, :n].contiguous()  # (no launch unless padded)
+            for i in range(NE):
+                sg[i][l] = (dW[i], db[i])
+            dz, ld_dz, zoff = d_in, ld_in, ioff
+        if j == 0:
+            # every stack and gate reads x: one weight-gradient product, one data-gradient GEMM
+            dWs, dbs = _wgrad(B, zw, w4, dZ0, zw, s["x"], w4, device, st)
+            r0 = NE * pe0
+            dW0 = dWs[:r0].view(NE, pe0, w4)[:, :n0, :width].contiguous()
+            db0 = dbs[:r0].view(NE, pe0)[:, :n0].contiguous()
+            # (the gates' cuts are clones: a copy whether or not ms + mc is on the grid, as above)
+            dWg = dWs[r0:r0 + K * pg].view(K, pg, w4)[:, :GT, :width].clone()
+            dbg = dbs[r0:r0 + K * pg].view(K, pg)[:, :GT].clone()
+            gg = [(dWg[q], dbg[q]) for q in range(K)]
+            if nq > K:
+                gg.append((dWs[goff[K]:goff[K] + NE, :width].contiguous(), dbs[goff[K]:goff[K] + NE]))
+            if need_dx:
+                dx = new(B, width, **f32)
+                gemm(False, True, B, width, zw, dZ0, zw, wst[0], wst[0].stride(0), dx, split=1)
+        else:
+            # owner q reads x_q^{j-1}: the K task owners grouped, the shared owner on its own
+            wt, wsh = wst[j]
+            prev, ld_prev = s["reps"][j - 1], (K + 1) * pm
+            dWt, dbt = new(K, bw_t, pm, **f32), new(K, bw_t, **f32)
+            A = [fptr(dZ0, q * bw_t) for q in range(K)]
+            gemm_wgrad_grouped(bw_t, pm, B, A, zw, [fptr(prev, q * pm) for q in range(K)], ld_prev,
+                               [dWt[q].data_ptr() for q in range(K)], pm, [dbt[q].data_ptr() for q in range(K)], device, st)
+            dZs, prev_s = dZ0[:, K * bw_t:], prev[:, K * pm:]
+            dWs, dbs = _wgrad(B, bw_s, pm, dZs, zw, prev_s, ld_prev, device, st)
+            dR = new(B, ld_prev, **f32)  # (its pad columns come out zero: the stacked weights' are)
+            gemm_grouped(False, True, B, pm, bw_t, A, zw, [wt[q].data_ptr() for q in range(K)], pm,
+                         [fptr(dR, q * pm) for q in range(K)], ld_prev, st)
+            gemm(False, True, B, pm, bw_s, dZs, zw, wsh, pm, dR[:, K * pm:], ld_prev, split=1)
+            r0 = ms * pe0
+            dW0t = dWt[:, :r0, :H].clone().view(K * ms, pe0, H)[:, :n0].contiguous()
+            db0t = dbt[:, :r0].clone().view(K * ms, pe0)[:, :n0].contiguous()
+            dW0s = dWs[:mc * pe0].view(mc, pe0, pm)[:, :n0, :H].contiguous()
+            db0s = dbs[:mc * pe0].view(mc, pe0)[:, :n0].contiguous()
+            dW0, db0 = list(dW0t) + list(dW0s), list(db0t) + list(db0s)
+            dWg, dbg = dWt[:, r0:r0 + GT, :H].clone(), dbt[:, r0:r0 + GT].clone()
+            gg = [(dWg[q], dbg[q]) for q in range(K)]
+            if nq > K:
+                gg.append((dWs[mc * pe0:mc * pe0 + NE, :H].contiguous(), dbs[mc * pe0:mc * pe0 + NE]))
+        for i in range(NE):
+            sg[i][0] = (dW0[i], db0[i])
+        level_grads[j] = (sg, gg)
+    return dx, level_grads, tower_grads
+
+
+def ple_flat_grads(sh: PleShape, level_grads, tower_grads):
+    """ple_backward's gradients in _ple_flat's order (a (dW, db) per layer, bias-free ones included)."""
+    out = []
+    for sg, gg in level_grads:
+        out += [t for layers in sg for wb in layers for t in wb]
+        out += [t for wb in gg for t in wb]
+    if tower_grads is not None:
+        for hidden, head in tower_grads:
+            out += [t for wb in hidden for t in wb] + list(head)
+    return out
+
+
+class _PleFn(torch.autograd.Function):
+    """rankops.ple with autograd: rk_ple_forward_train without dropout, ple_backward.  Inputs after the
+    fixed arguments: x, then every weight and bias in _ple_flat's order (None for an absent bias).
+    Outputs: per level (representations, gates), then logits and probs with towers."""
+
+    @staticmethod
+    def forward(ctx, sh, launch, x, *flat):
+        s = launch()
+        ctx.sh, ctx.s, ctx.flat, ctx.B = sh, s, flat, x.shape[0]
+        B, pm = x.shape[0], p4(sh.H)
+        outs = []
+        for j in range(sh.L):
+            outs += [s["reps"][j].view(B, sh.nq(j), pm)[:, :, :sh.H], s["gates"][j]]
+        if sh.heads:
+            outs += [s["logits"], s["probs"]]
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        sh, s, flat, B = ctx.sh, ctx.s, ctx.flat, ctx.B
+        L = sh.L
+        if any(g is not None for j in range(L) for g in (grads[2 * j + 1],) + ((grads[2 * j],) if j < L - 1 else ())):
+            raise NotImplementedError("rankops.ple: a gradient flowing into a gate output or a lower level's "
+                                      "representations is not supported (differentiate logits, probs or the last "
+                                      "level's representations)")
+        d_reps = grads[2 * (L - 1)]
+        d_logits, d_probs = (grads[2 * L], grads[2 * L + 1]) if sh.heads else (None, None)
+        levels, towers, wst = s["weights"]
+        dev = s["x"].device
+        if B == 0:
+            return (None, None, torch.zeros(0, sh.width, device=dev)) + tuple(
+                None if t is None else torch.zeros_like(t) for t in flat)
+        like = lambda g, shape: None if g is None else g.to(torch.float32).reshape(shape).contiguous()
+        dx, lg, tg = ple_backward(sh, B, s, wst, levels, towers, 0.0, like(d_reps, (B, sh.K, sh.H)),
+                                  like(d_logits, (B, sh.K)), like(d_probs, (B, sh.K)), ctx.needs_input_grad[2], dev)
+        out = ple_flat_grads(sh, lg, tg)
+        return (None, None, dx, *[None if t is None else g.reshape(t.shape) for t, g in zip(flat, out)])
+
+
+def _ple_autograd(x, flat, sh: PleShape, experts, gate_entries, tower_entries, heads, return_levels):
+    """rankops.ple's differentiable path over the checked, detached (W, b) lists of ops.ple."""
+    B, dev, L, K, GT = x.shape[0], x.device, sh.L, sh.K, sh.GT
+    Dt = len(sh.tu)
+    levels = ple_level_lists(sh, experts, gate_entries)
+    towers = None
+    if sh.heads:
+        towers = [(tower_entries[k * Dt:(k + 1) * Dt], heads[k]) for k in range(K)]
+
+    def launch():
+        if B == 0:  # (an empty batch launches nothing)
+            s = ple_forward_train(None, sh, 0, None, dev, 0.0, 0, None)
+            s["weights"] = (levels, towers, None)
+            return s
+        stream = _lib.raw_stream(dev)
+        table = experts + gate_entries + tower_entries
+        packed = [wb for wb in table if wb is not None]
+        images = [mlp_image(w.shape[0], w.shape[1], dev) for w, _ in packed]
+        pack_mlp_weights([(w, img) for (w, _), img in zip(packed, images)], stream)
+        it = iter(images)
+        entries = [(next(it), wb[1]) if wb is not None else (images[0], None) for wb in table] + heads
+        segs = [dense_segment(x.detach(), min(128, sh.width - c), c, c) for c in range(0, sh.width, 128)]
+        s = ple_forward_train(segs, sh, B, entries, dev, 0.0, 0, None)
+        s["weights"] = (levels, towers, ple_stacked_weights(sh, levels))
+        return s
+    out = _PleFn.apply(sh, launch, x, *flat)
+
+    def split(j):
+        g = out[2 * j + 1]
+        return (out[2 * j], g[:, :K * GT].view(B, K, GT), g[:, K * GT:] if j < L - 1 else None)
+    if not sh.heads:
+        return [split(j) for j in range(L)] if return_levels else split(L - 1)[:2]
+    logits, probs = out[2 * L], out[2 * L + 1]
     return (logits, probs, [split(j) for j in range(L)]) if return_levels else (logits, probs)

@@ -6,7 +6,7 @@ conventions of rankops.MMoE and the reference's DCN (algorithm/DCN/dcn.py):
 
 `PLE(vocab_dir, num_levels=2, num_specific_experts=2, num_shared_experts=2, expert_hidden_units=(256, 128),
      tower_hidden_units=(64,), task_names=("read_comment", "like", "click_avatar"), dropout_rate=0.1, *,
-     vocab_sizes=None)`
+     vocab_sizes=None, trainable=False, sparse_grad=False)`
 `forward(dense [B, 16], category {6 x [B]}) -> (probabilities [B, K], logits [B, K])`, column k = task_names[k].
 
 With L = num_levels, ms = num_specific_experts, mc = num_shared_experts, K tasks, x = cat[dense, embeddings]
@@ -30,12 +30,27 @@ Sequential), shared_experts (ModuleList[mc]), gates (ModuleList[K] of Linear) an
 shared_gate (Linear); then towers and tower_outputs as in MMoE.
 
 One launch, rk_ple_forward (csrc/ple.hip): the row gather, every level's gates, experts and mixtures, the
-towers and the heads; nothing between the gather and the logits reaches HBM.  Train mode raises
-NotImplementedError (training is later work), CPU tensors raise the engine's "ROCm GPU" error, and a
-configuration outside the kernel's envelope (common.ple_fits) is an error, not a fallback.
+towers and the heads; nothing between the gather and the logits reaches HBM.  CPU tensors raise the engine's
+"ROCm GPU" error, and a configuration outside the kernel's envelope (common.ple_fits) is an error, not a
+fallback.
 
-`rankops.ple(x, levels, towers=None, return_levels=False)` is the same kernel on plain tensors (ops.ple); this
-module is callable so that `rankops.ple` is both the module and that function.
+Training is opt-in, as rankops.MMoE's: `PLE(..., trainable=True)` in train mode returns (probabilities, logits)
+attached to autograd (rankops.train._PLETrain): rk_ple_forward_train, the same kernel with Dropout live behind
+every ReLU and the activations kept, then ops.ple_backward — the heads and towers as MMoE's, per level
+rk_ple_mix_backward and the grouped Linear backwards, in a number of launches that depends on L, the depths
+and ceil((K ms + mc) / 16) only — and the embedding gradients; under no_grad it runs the same forward and keeps
+nothing; `sparse_grad=True` hands the tables sparse COO gradients (rankops.SparseAdam).  The default
+(trainable=False) raises NotImplementedError in train mode, as before.  Neither flag adds, reorders or
+re-initialises a parameter.  Dropout masks are the engine's counter hash: with NE = K ms + mc stacks per level
+(task k's at k ms + i, the shared at K ms + i), De = len(expert_hidden_units), Dt = len(tower_hidden_units) and
+(seed, slot) of the last forward (seed = model._dropout.seed, slot = model._dropout.counter - 1: the device
+counter is advanced once per train forward), expert s of level j, layer l drew
+`ops.dropout_mask(seed + (j * NE + s) * De + l, slot, B, n, p)` and tower k layer l
+`ops.dropout_mask(seed + L * NE * De + k * Dt + l, slot, B, n, p)` (element b * n + c).
+
+`rankops.ple(x, levels, towers=None, return_levels=False)` is the same kernel on plain tensors (ops.ple),
+differentiable when an input requires grad; this module is callable so that `rankops.ple` is both the module
+and that function.
 """
 from __future__ import annotations
 
@@ -97,13 +112,15 @@ class PLE(MultiTask):
 
     def __init__(self, vocab_dir, num_levels=2, num_specific_experts=2, num_shared_experts=2,
                  expert_hidden_units=(256, 128), tower_hidden_units=(64,), task_names=DEFAULT_TASKS, dropout_rate=0.1,
-                 *, vocab_sizes=None):
+                 *, vocab_sizes=None, trainable=False, sparse_grad=False):
         if int(num_levels) <= 0:
             raise ValueError(f"num_levels must be positive, got {num_levels!r}")
         if int(num_specific_experts) < 0 or int(num_shared_experts) <= 0:
             raise ValueError(f"num_specific_experts must be >= 0 and num_shared_experts >= 1, got "
                              f"{num_specific_experts!r}, {num_shared_experts!r}")
         super().__init__(vocab_dir, expert_hidden_units, tower_hidden_units, task_names, dropout_rate, vocab_sizes)
+        self.trainable = bool(trainable)      # train mode runs the HIP train forward / backward (rankops.train)
+        self.sparse_grad = bool(sparse_grad)  # train mode: tables get sparse COO gradients (rankops.SparseAdam)
         self.num_levels = int(num_levels)
         self.num_specific_experts = int(num_specific_experts)
         self.num_shared_experts = int(num_shared_experts)

@@ -748,8 +748,8 @@ class _MMoETrain(torch.autograd.Function):
         return (None, None, None, None, *out)
 
 
-class _MMoEEmpty(torch.autograd.Function):
-    """MMoE's train forward over an empty batch: empty outputs attached to the parameters, whose
+class _MultiTaskEmpty(torch.autograd.Function):
+    """A multi-task model's (MMoE, PLE) train forward over an empty batch: empty outputs attached to the parameters, whose
     gradients are zeros (what the reference's loop gets from autograd); no kernel of the engine runs."""
 
     @staticmethod
@@ -763,17 +763,7 @@ class _MMoEEmpty(torch.autograd.Function):
         return (None, None, *[torch.zeros_like(p) for p in ctx.params])
 
 
-def mmoe_train_forward(model, dense, names, idx, grad: bool = True):
-    """MMoE train-mode forward: (probabilities [B, K], logits [B, K]) attached to _MMoETrain when `grad`;
-    otherwise the same launches with nothing kept.  An empty batch returns empty outputs (attached, with
-    zero gradients, when `grad`) without running the engine."""
-    if dense.shape[0] == 0:
-        if not grad:
-            return common.empty_rows(dense.device, 2, (0, len(model.task_names)))
-        return _MMoEEmpty.apply(len(model.task_names), dense.device, *[p for p in model.parameters() if p.requires_grad])
-    if not grad:
-        _, s = _mmoe_front(model, dense, names, idx)
-        return s["probs"], s["logits"]
+def _mmoe_params(model, names):
     lin = model._linears
     params = [model.embeddings[n].weight for n in names]
     for seq in model.experts:
@@ -786,7 +776,123 @@ def mmoe_train_forward(model, dense, names, idx, grad: bool = True):
             params += [l.weight, l.bias]
     for o in model.tower_outputs:
         params += [o.weight, o.bias]
-    return _MMoETrain.apply(model, dense, names, idx, *params)
+    return params
+
+
+def multitask_train_forward(model, dense, names, idx, grad: bool = True):
+    """Train-mode forward of a multi-task model (MMoE, PLE): (probabilities [B, K], logits [B, K]) attached
+    to the model's autograd function when `grad`; otherwise the same launches with nothing kept.  An empty
+    batch returns empty outputs (attached, with zero gradients, when `grad`) without running the engine."""
+    front, fn, params = {"MMoE": (_mmoe_front, _MMoETrain, _mmoe_params),
+                         "PLE": (_ple_front, _PLETrain, _ple_params)}[model.NAME]
+    if dense.shape[0] == 0:
+        if not grad:
+            return common.empty_rows(dense.device, 2, (0, len(model.task_names)))
+        return _MultiTaskEmpty.apply(len(model.task_names), dense.device,
+                                     *[p for p in model.parameters() if p.requires_grad])
+    if not grad:
+        _, s = front(model, dense, names, idx)
+        return s["probs"], s["logits"]
+    return fn.apply(model, dense, names, idx, *params(model, names))
+
+
+# ---------------------------------------------------------------- PLE
+
+def _ple_lists(model):
+    """(levels, towers) of a rankops.PLE in ops.ple_backward's form, detached."""
+    lin = model._linears
+    levels = [([[(l.weight.detach(), l.bias) for l in lin(seq)] for seq in level.stacks()],
+               [(g.weight.detach(), g.bias) for g in level.all_gates()]) for level in model.levels]
+    towers = [([(l.weight.detach(), l.bias) for l in lin(seq)], (o.weight.detach().reshape(-1), o.bias))
+              for seq, o in zip(model.towers, model.tower_outputs)]
+    return levels, towers
+
+
+def _ple_front(model, dense, names, idx):
+    """The train forward, as _mmoe_front: every image the kernel reads repacked on the stream into the
+    model's own buffers (one rk_mlp_pack_weights for all of them, so the addresses and with them the
+    device layer table are the same every step and a hipGraph replay follows the optimizer), the
+    per-level stacked first-layer / gate weights assembled (ops.ple_stacked_weights), the dropout stream
+    advanced (rk_rng_next), then rk_ple_forward_train.  Returns (shape, saved buffers)."""
+    B, dev = dense.shape[0], dense.device
+    K = len(model.task_names)
+    sh = ops.PleShape(model.input_dim, model.num_levels, K, model.num_specific_experts, model.num_shared_experts,
+                      model.expert_hidden_units, model.tower_hidden_units, True)
+    levels, towers = _ple_lists(model)
+    wst = ops.ple_stacked_weights(sh, levels)
+    own = model.__dict__.setdefault("_train_images", {})
+    if own.get("device") != dev:
+        own.clear()
+        own["device"] = dev
+    pairs = []
+
+    def image(key, w):
+        img = own.get(key)
+        if img is None:
+            img = own[key] = ops.mlp_image(w.shape[0], w.shape[1], dev)
+        pairs.append((w, img))
+        return img
+    experts, gates = [], []
+    for j, (stacks, lgates) in enumerate(levels):
+        experts += [(image(("e", j, i, l), w), b) for i, layers in enumerate(stacks) for l, (w, b) in enumerate(layers)]
+        gates += [(image(("g", j, q), w), b) for q, (w, b) in enumerate(lgates)]
+        if len(lgates) == K:  # the last level: the shared gate's slot is never read
+            gates.append((gates[-1][0], None))
+    tw = [(image(("t", k, l), w), b) for k, (hidden, _) in enumerate(towers) for l, (w, b) in enumerate(hidden)]
+    heads = [(o.weight.detach(), o.bias) for o in model.tower_outputs]
+    stream = ops._lib.raw_stream(dev)
+    ops.pack_mlp_weights(pairs, stream)
+    p = float(model.dropout_rate)
+    seed, slot = 0, None
+    if p > 0:
+        seed, slot = model.__dict__.setdefault("_dropout", DropoutStreams()).next(dev)
+    s = ops.ple_forward_train(model._segments(dense, names, idx), sh, B, experts + gates + tw + heads, dev, p, seed, slot)
+    s["weights"] = (levels, towers, wst)
+    s["dropout"] = (seed, slot)
+    return sh, s
+
+
+class _PLETrain(torch.autograd.Function):
+    """PLE forward + backward in train mode: rk_ple_forward_train (one launch: gather, every level's gates,
+    experts with dropout and mixtures, towers, heads, every activation kept), then ops.ple_backward and the
+    embedding gradients.  Inputs after the fixed arguments: the tables, then per level every stack Linear's
+    (weight, bias) stack-major and the gates', then per tower its Linears' and its output layer's."""
+
+    @staticmethod
+    def forward(ctx, model, dense, names, idx, *params):
+        sh, s = _ple_front(model, dense, names, idx)
+        ctx.model, ctx.sh, ctx.s, ctx.names, ctx.idx, ctx.B = model, sh, s, names, idx, dense.shape[0]
+        ctx.set_materialize_grads(False)
+        return s["probs"], s["logits"]
+
+    @staticmethod
+    def backward(ctx, dprob, dlogit):
+        model, sh, s, B = ctx.model, ctx.sh, ctx.s, ctx.B
+        dev = s["x"].device
+        levels, towers, wst = s["weights"]
+        if dprob is None and dlogit is None:
+            dlogit = torch.zeros(B, sh.K, device=dev, dtype=torch.float32)
+        dx, lg, tg = ops.ple_backward(sh, B, s, wst, levels, towers, float(model.dropout_rate), None,
+                                      _grad_out(dlogit, s["logits"]), _grad_out(dprob, s["probs"]), True, dev)
+        tables = [model.embeddings[n].weight for n in ctx.names]
+        g_tab = embedding_grads(tables, ctx.idx, model.num_dense_features, dx, sparse=model.sparse_grad)
+        return (None, None, None, None, *g_tab, *ops.ple_flat_grads(sh, lg, tg))  # (_ple_params' order)
+
+
+def _ple_params(model, names):
+    lin = model._linears
+    params = [model.embeddings[n].weight for n in names]
+    for level in model.levels:
+        for seq in level.stacks():
+            for l in lin(seq):
+                params += [l.weight, l.bias]
+        for g in level.all_gates():
+            params += [g.weight, g.bias]
+    for seq, o in zip(model.towers, model.tower_outputs):
+        for l in lin(seq):
+            params += [l.weight, l.bias]
+        params += [o.weight, o.bias]
+    return params
 
 
 # ---------------------------------------------------------------- DIN

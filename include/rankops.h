@@ -66,6 +66,8 @@
  *   rk_gemm_wgrad      dW = dZ^T X, db over long reductions (one tile owner per row slab)
  *   rk_gemm_grouped, rk_gemm_wgrad_grouped   G same-shaped Linear backwards in one launch each
  *   rk_mmoe_forward_train, rk_mmoe_mix_backward, rk_mmoe_head_backward   MMoE training
+ *   rk_ple_forward_train, rk_ple_mix_backward   PLE training: the train form of the one-launch forward
+ *                      and the backward of one level's mixtures and gates ("Training")
  *   rk_logit_head_backward  output_layer + sigmoid backward      dcn.py:177-179
  *   rk_dcn_cross_backward   cross_layer backward w.r.t. x0        dcn.py:46-49
  *   rk_relu_backward   ReLU backward (residual_unit's outer ReLU) deepcrossing.py:41
@@ -107,7 +109,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 5
+#define RK_ABI_VERSION 6
 
 #define RK_OK 0
 #define RK_ERR_INVALID 1     /* bad argument (shape, null pointer, limit) */
@@ -876,6 +878,57 @@ int rk_ple_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t 
                    int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
                    const rk_mmoe_layer* table, int64_t table_len, float* logits, float* probs,
                    float* const* level_reps, float* const* level_gates, void* stream);
+
+/* ---- PLE training ("Training") ---- */
+/* rk_ple_forward in train mode, still one launch: dropout (probability dropout_p in [0, 1), scale
+ * 1 / (1 - p)) behind every ReLU, and everything the backward reads kept.  Dropout sites:
+ *   expert s of level j, layer l    (j NE + s) De + l          (its index in the layer table)
+ *   tower k, layer l                L NE De + k Dt + l
+ * element (b, c) of a site's [batch, n] output is kept iff the counter hash of rk_dropout_mask(seed +
+ * site, stream_slot, ...) keeps element b * n + c (stream_slot may be NULL when dropout_p == 0).  With
+ * p4(v) = v rounded up to a multiple of 4, the saved buffers (all required, 16-B aligned, the columns
+ * between a width and its p4 written as zeros) are
+ *   x_out                   [batch, p4(width)]            the gathered rows
+ *   expert_acts[j De + l]   [batch, NE * p4(n_l)]         level j: stack s's layer l (after ReLU and dropout)
+ *                                                         at columns s * p4(n_l); l = De - 1 is f_s
+ *   tower_acts[l]           [batch, K * p4(n_l)]          tower k's layer l at columns k * p4(n_l)
+ *   level_reps[j]           [batch, (K + 1) * p4(H)]      mixture i at columns i * p4(H) ([batch, K * p4(H)] at
+ *                                                         the last level; not rk_ple_forward's layout)
+ *   level_gates[j]          rk_ple_forward's layout
+ *   logits, probs           [batch, K], required with has_heads != 0
+ * With dropout_p == 0 the logits, probs and every level's representations and gates have
+ * rk_ple_forward's bits.  Envelope and errors as rk_ple_forward; in addition dropout_p outside [0, 1),
+ * a NULL or misaligned saved buffer, or a NULL stream_slot with dropout_p > 0: RK_ERR_INVALID before
+ * any launch.  batch == 0: RK_OK, no launch.                                                       */
+int rk_ple_forward_train(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch, int32_t num_levels,
+                         int32_t num_tasks, int32_t num_specific, int32_t num_shared, const int32_t* expert_units,
+                         int32_t expert_depth, const int32_t* tower_units, int32_t tower_depth, int32_t has_heads,
+                         const rk_mmoe_layer* table, int64_t table_len, double dropout_p, uint64_t seed,
+                         const int64_t* stream_slot, float* x_out, float* const* expert_acts,
+                         float* const* tower_acts, float* logits, float* probs, float* const* level_reps,
+                         float* const* level_gates, void* stream);
+
+/* Backward of one level's mixtures and gates, one launch, rows independent.  K = num_tasks, ms =
+ * num_specific, mc = num_shared, NE = K ms + mc, nq = K + 1 mixtures (K when has_shared_mix == 0: the
+ * last level).  s(i, c), the stack behind column c of gate i: i ms + c (c < ms) or K ms + c - ms for i < K,
+ * c for i == K.  Per row b, with dm_i = dm[b * ld_dm + i * pitch_dm ..] [H], f_s = f[b * ld_f + s *
+ * pitch_f ..] [H] (the stacks' last outputs after ReLU and dropout) and g_i the gate weights at
+ * gates[b * ld_gates ..] in rk_ple_forward's level_gates layout:
+ *   dg_i[c]  = sum_h dm_i[h] f_{s(i,c)}[h]
+ *   dgate_logits[b * ld_dgl + gate_offsets[i] + c] = g_i[c] (dg_i[c] - sum_c' g_i[c'] dg_i[c'])
+ *   dz[b * ld_dz + stack_offsets[s] + h] = (sum over the (i, c) with s(i, c) = s, i ascending, of g_i[c]
+ *                                          dm_i[h]) * mask_scale * [f_s[h] > 0]
+ * with zeros behind a gate's columns up to the next multiple of 4 and behind H up to pitch_dz.
+ * gate_offsets [nq] and stack_offsets [NE] are host arrays (copied into the kernel arguments).  Sums in a
+ * fixed order, no atomics: two launches give the same bits; a one-column gate's gradient is exactly 0.
+ * Envelope: K <= 8, NE <= 64, H <= 512 (RK_ERR_UNSUPPORTED); NULL, a pitch, leading dimension or
+ * offset that does not fit, a pointer not aligned to 4 B, batch < 0: RK_ERR_INVALID; both before any
+ * launch, nothing is written.  batch == 0: RK_OK, no launch.                                       */
+int rk_ple_mix_backward(int64_t batch, int32_t num_tasks, int32_t num_specific, int32_t num_shared,
+                        int32_t has_shared_mix, int32_t H, const float* dm, int64_t ld_dm, int32_t pitch_dm,
+                        const float* f, int64_t ld_f, int32_t pitch_f, const float* gates, int64_t ld_gates,
+                        float mask_scale, float* dgate_logits, int64_t ld_dgl, const int32_t* gate_offsets,
+                        float* dz, int64_t ld_dz, const int32_t* stack_offsets, int32_t pitch_dz, void* stream);
 
 /* ---- xDeepFM training: the CIN's train forward, data backward and weight gradient ---- */
 /* rk_cin_forward that also writes every layer's feature maps for the backward:

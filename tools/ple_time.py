@@ -14,8 +14,19 @@ The method is tools/mmoe_time.py's: every leg is captured in a hipGraph once and
 device events; the legs alternate and the median over the rounds is reported with the fastest and slowest
 round.  The three are compared with each other before anything is timed.  From the shapes the tool computes
 the forward's flops per sample and reports the kernel's rate as a share of the 157.3 TF FP32 matrix peak of
-the MI355X (the MFMA FP32 peak, not a measured ceiling).  `--batches 2048,8192` measures other batch sizes.
-Needs a GPU; prints one JSON line at the end."""
+the MI355X (the MFMA FP32 peak, not a measured ceiling).  `--batches 2048,8192` measures other batch sizes;
+`--legs kernel` times leg (a) alone.  Needs a GPU; prints one JSON line at the end.
+
+`--train` times one training step instead (forward + backward of BCE-with-logits over the K label columns,
+gradients set to None first, optimizer excluded) at the same four points, two legs by the same method
+(tools/mmoe_time.py --train's):
+
+  (a) engine    rankops.PLE(trainable=True) in train mode: rk_ple_forward_train and ops.ple_backward
+  (b) torch     float32 torch autograd of the same module (torch_forward in train mode: nn.Dropout live)
+
+with the same dropout rate (a whole step captured with dien_time.grad_graph_of), and prints the launches of
+one eager step of (a), counted on the host (tests/launch_count.py's launches_of) — their number depends on L,
+the depths and ceil((K ms + mc) / 16) only."""
 import json
 import os
 import statistics
@@ -30,7 +41,8 @@ import helpers as H  # noqa: E402
 import rankops  # noqa: E402
 from rankops import common, ops  # noqa: E402
 
-from dien_time import shader_clock  # noqa: E402
+from dien_time import grad_graph_of, shader_clock  # noqa: E402
+from launch_count import launches_of  # noqa: E402  (tests/launch_count.py)
 from mmoe_time import FP32_MATRIX_PEAK_TF, ROUNDS, replay_us  # noqa: E402
 
 
@@ -129,6 +141,8 @@ def measure(L, B):
         return out
     composed = composed_forward(model, dense, cat)
     fns = {"kernel": kernel, "torch": lambda: torch_forward(model, dense, cat), "composed": composed}
+    if "--legs" in sys.argv[1:]:
+        fns = {k: fns[k] for k in sys.argv[sys.argv.index("--legs") + 1].split(",")}
     with torch.no_grad():
         prob_a, logit_a = [t.clone() for t in kernel()]
         prob_b, logit_b = torch_forward(model, dense, cat)
@@ -152,10 +166,53 @@ def measure(L, B):
     r["flops_per_sample"] = flops
     r["kernel_tflops"] = round(flops * B / med["kernel"] / 1e6, 2)
     r["share_of_fp32_matrix_peak"] = round(flops * B / med["kernel"] / 1e6 / FP32_MATRIX_PEAK_TF, 4)
-    r["torch_over_kernel"] = round(med["torch"] / med["kernel"], 2)
-    r["composed_over_kernel"] = round(med["composed"] / med["kernel"], 2)
+    if "torch" in med:
+        r["torch_over_kernel"] = round(med["torch"] / med["kernel"], 2)
+    if "composed" in med:
+        r["composed_over_kernel"] = round(med["composed"] / med["kernel"], 2)
     r["kernel_vs_torch_max_rel_err"], r["kernel_vs_composed_max_rel_err"] = err_b, err_c
     del graphs, model
+    torch.cuda.empty_cache()
+    return r
+
+
+def measure_train(L, B):
+    torch.manual_seed(42)
+    engine = rankops.PLE(None, num_levels=L, vocab_sizes=H.WECHAT_VOCAB, trainable=True).cuda().train()
+    torch.manual_seed(42)
+    plain = rankops.PLE(None, num_levels=L, vocab_sizes=H.WECHAT_VOCAB).cuda().train()
+    inp = H.to_device(H.dcn_inputs(B, H.WECHAT_VOCAB, 1000), "cuda")
+    dense, cat = inp["dense"], inp["category"]
+    K = len(engine.task_names)
+    labels = (torch.rand(B, K, generator=torch.Generator().manual_seed(3)) < 0.3).float().cuda()
+    crit = torch.nn.BCEWithLogitsLoss()
+
+    def step_of(model, forward):
+        def step():
+            with torch.enable_grad():
+                for prm in model.parameters():
+                    prm.grad = None
+                crit(forward()[1], labels).backward()
+        return step
+    fns = {"engine": step_of(engine, lambda: engine(dense, cat)),
+           "torch": step_of(plain, lambda: torch_forward(plain, dense, cat))}
+    graphs = {k: grad_graph_of(fn) for k, fn in fns.items()}
+    times = {k: [] for k in graphs}
+    for _ in range(ROUNDS):
+        for k, g in graphs.items():
+            times[k].append(replay_us(g))
+    r = {}
+    for k, t in times.items():
+        r[f"{k}_us"] = {"median": round(statistics.median(t), 2), "min": round(min(t), 2), "max": round(max(t), 2)}
+    med = {k: statistics.median(t) for k, t in times.items()}
+    r["torch_over_engine"] = round(med["torch"] / med["engine"], 2)
+    r["torch_over_engine_range"] = [round(min(times["torch"]) / max(times["engine"]), 2),
+                                    round(max(times["torch"]) / min(times["engine"]), 2)]
+    del graphs
+    names = launches_of(fns["engine"])  # after the timing: nothing of the count runs before a capture
+    r["engine_launches"] = len(names)
+    r["engine_launch_list"] = names
+    del engine, plain
     torch.cuda.empty_cache()
     return r
 
@@ -170,7 +227,7 @@ def main():
         batches = tuple(int(b) for b in sys.argv[sys.argv.index("--batches") + 1].split(","))
     for L in (2, 3):
         for B in batches:
-            r = measure(L, B)
+            r = measure_train(L, B) if "--train" in sys.argv[1:] else measure(L, B)
             result[f"L{L}_B{B}"] = r
             print(f"L {L} B {B}: " + ", ".join(f"{k} {v}" for k, v in r.items()), flush=True)
     result["sclk_after"] = shader_clock()
