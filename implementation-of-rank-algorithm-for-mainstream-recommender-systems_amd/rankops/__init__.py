@@ -28,6 +28,14 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
                                            (rk_ple_forward); rankops.ple is the module and, called, the op;
                                            trainable=True trains (rk_ple_forward_train, rk_ple_mix_backward
                                            and the grouped Linear backwards), ple is differentiable
+    ESMM, esmm, esmm_loss                  ESMM, the entire space multi-task model (the multi-task list's
+                                           first model, no script in the reference): towers over one gathered
+                                           row, probabilities multiplied along the chain of events, the
+                                           whole eval forward in one launch (rk_esmm_forward); rankops.esmm
+                                           is the module and, called, the op; trainable=True trains
+                                           (rk_esmm_forward_train, rk_esmm_joint_backward and the grouped
+                                           Linear backwards); esmm_loss is the entire-space loss in the log
+                                           domain with its analytic gradient (rk_esmm_loss)
 
 `rankops.sharded.ShardedDeepFM` adds the table-sharded multi-GPU DeepFM lookup (RCCL
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the
@@ -57,6 +65,9 @@ from . import mmoe  # noqa: F401  (callable: rankops.mmoe(x, experts, gates, tow
 from .mmoe import MMoE  # noqa: F401
 from . import ple  # noqa: F401  (callable: rankops.ple(x, levels, towers=None, return_levels=False))
 from .ple import PLE  # noqa: F401
+from . import esmm  # noqa: F401  (callable: rankops.esmm(x, towers, return_conditional=False))
+from .esmm import ESMM  # noqa: F401
+from .ops import esmm_loss  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
 from .ranking import GroupedAUC, GroupTable, RequestTopK, grouped_auc, topk_per_request, topk_segments  # noqa: F401
 from .ops import cin  # noqa: F401
@@ -69,5 +80,5 @@ __all__ = [
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
     "dien_aux_loss", "dien_aux_loss_gather", "dien_extract", "dien_extract_gather", "dien_evolve", "DIENInterests",
-    "SparseAdam", "XDeepFM", "cin", "MMoE", "mmoe", "PLE", "ple", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
+    "SparseAdam", "XDeepFM", "cin", "MMoE", "mmoe", "PLE", "ple", "ESMM", "esmm", "esmm_loss", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
 ]

@@ -469,6 +469,17 @@ SIGNATURES = {
     "rk_mmoe_head_backward": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                              POINTER(c_void_p), c_void_p, c_float, c_void_p, c_int32, c_void_p, c_int32,
                                              c_void_p]),
+    "rk_esmm_forward": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
+                                       POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rk_esmm_forward_train": (ctypes.c_int, [_SEG_P, c_int32, c_int32, c_int64, POINTER(MmoeLayer), c_int32, c_int32,
+                                             POINTER(c_void_p), POINTER(c_void_p), ctypes.c_double, ctypes.c_uint64,
+                                             c_void_p, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    "rk_esmm_loss_workspace_floats": (c_int64, [c_int64]),
+    "rk_esmm_loss": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, POINTER(c_float), c_void_p,
+                                    c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "rk_esmm_joint_backward": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                              c_int32, c_void_p, c_int64, c_void_p]),
     "rk_gemm_grouped": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, POINTER(c_void_p), c_int64,
                                        POINTER(c_void_p), c_int64, POINTER(c_void_p), c_int64, POINTER(c_void_p),
                                        c_int64, c_float, c_int32, c_void_p]),

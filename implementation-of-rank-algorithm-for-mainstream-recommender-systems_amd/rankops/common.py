@@ -502,6 +502,19 @@ def mmoe_fits(width: int, num_segments: int, num_experts: int, num_tasks: int, e
     return base + 16 * _pad64(expert_units[-1]) * 4 <= 160 * 1024
 
 
+def esmm_fits(width: int, num_segments: int, num_tasks: int, tower_units) -> bool:
+    """Whether rk_esmm_forward takes this shape (the mirror of its envelope, csrc/esmm.hip): width <= 256 in
+    at most 16 segments, 2 <= K <= 8, 1..3 tower layers, every hidden width <= 512 (the row, the two
+    activation buffers and the logits then always fit the 160 KiB of LDS)."""
+    tower_units = list(tower_units)
+    if not (0 < width <= 256 and 0 < num_segments <= 16 and 2 <= num_tasks <= 8 and 1 <= len(tower_units) <= 3):
+        return False
+    if min(tower_units) <= 0 or max(tower_units) > 512:
+        return False
+    ldx, ldh = _pad64(width) + 8, max(64, max(_pad64(n) for n in tower_units)) + 8  # rows padded by kMlpLdPad
+    return 16 * (ldx + 2 * ldh + 8) * 4 <= 160 * 1024
+
+
 def ple_fits(width: int, num_segments: int, num_levels: int, num_tasks: int, num_specific: int, num_shared: int,
              expert_units, tower_units) -> bool:
     """Whether rk_ple_forward takes this shape (the mirror of its envelope and LDS check, csrc/ple.hip):

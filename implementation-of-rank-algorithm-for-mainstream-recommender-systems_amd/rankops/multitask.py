@@ -1,4 +1,4 @@
-"""What the multi-task models (rankops.MMoE, rankops.PLE) share: the inputs of the reference's DCN
+"""What the multi-task models (rankops.MMoE, rankops.PLE, rankops.ESMM) share: the inputs of the reference's DCN
 (16 dense columns and six embedding tables, width 50), K towers with one head each, and an eval forward
 that is one launch returning (probabilities [B, K], logits [B, K]).
 
@@ -8,7 +8,8 @@ LOGITS_SLOT / PROBS_SLOT (the two outputs' positions in its argument list), `fit
 what it must keep alive.  Training is opt-in per instance (`trainable`, `sparse_grad`, set by the model's
 constructor): train mode then runs rankops.train.multitask_train_forward, which finds the model's train
 forward, autograd function and parameter list by NAME.  Its __init__ calls this one first (embeddings are the first modules created),
-then creates its experts and gates, then calls `_make_towers`.
+then creates its experts and gates, then calls `_make_towers`.  A model without experts (ESMM) passes
+expert_hidden_units=None and builds its towers over the row.
 """
 from __future__ import annotations
 
@@ -38,10 +39,12 @@ class MultiTask(EngineModule):
     def __init__(self, vocab_dir, expert_hidden_units, tower_hidden_units, task_names, dropout_rate, vocab_sizes):
         super().__init__()
         self.dropout_rate = float(dropout_rate)
-        expert_hidden_units = tuple(int(h) for h in expert_hidden_units)
+        no_experts = expert_hidden_units is None  # (ESMM: the towers stand on the row itself)
+        expert_hidden_units = () if no_experts else tuple(int(h) for h in expert_hidden_units)
         tower_hidden_units = tuple(int(h) for h in tower_hidden_units)
         task_names = tuple(task_names)
-        if len(expert_hidden_units) == 0 or any(h <= 0 for h in expert_hidden_units + tower_hidden_units):
+        if (not no_experts and len(expert_hidden_units) == 0) or any(
+                h <= 0 for h in expert_hidden_units + tower_hidden_units):
             raise ValueError(f"expert_hidden_units must be a non-empty list of positive widths and tower_hidden_units "
                              f"a list of positive widths, got {expert_hidden_units!r}, {tower_hidden_units!r}")
         if len(task_names) == 0 or len(set(task_names)) != len(task_names):

@@ -1839,13 +1839,17 @@ def _wgrad(B, N, Kd, A, lda, Bm, ldb, device, st):
     return dW, db
 
 
-def mtl_tower_backward(K, H, tu, B, tacts, mixed, probs, towers, scale, d_mixed, d_logits, d_probs, device, st):
+def mtl_tower_backward(K, H, tu, B, tacts, mixed, probs, towers, scale, d_mixed, d_logits, d_probs, device, st, *,
+                       first=0):
     """The heads and towers of a multi-task model (MMoE, PLE), backward: rk_mmoe_head_backward, one
     rk_gemm_wgrad for the heads and per tower layer the grouped pair over the K tasks.  tacts, mixed
     [B, K p4(H)], probs: the train forward's buffers; towers: K (hidden [(W, b)…], (w, b)) or None;
     d_mixed [B, K, H], d_logits, d_probs [B, K]: the incoming gradients, each may be None.  Returns (the
     gradient of the mixtures [B, K p4(H)] — a private buffer —, tower grads [([(dW, db)…], (dw, db))…] or
-    None)."""
+    None).  first=1 (ESMM: the towers' first layers read one shared row, not per-task mixtures; Dt >= 1,
+    mixed = d_mixed = None) stops above layer 0: the first result is then dz_0 [B, K p4(tu[0])], the gradient
+    at layer 0's pre-activations with zeros in its pad columns, and every hidden_grads[k][0] is None for
+    the caller to fill."""
     tu = tuple(tu)
     Dt = len(tu)
     pt, pm = [p4(n) for n in tu], p4(H)
@@ -1876,7 +1880,7 @@ def mtl_tower_backward(K, H, tu, B, tacts, mixed, probs, towers, scale, d_mixed,
         hd, hb = wgrad(pk, K * plast, g, pk, feed, K * plast)  # the heads' dw are its diagonal blocks
         head_grads = [(hd[k, k * plast:k * plast + last].view(1, last), hb[k:k + 1]) for k in range(K)]
         hidden_grads = [[None] * Dt for _ in range(K)]
-        for l in range(Dt - 1, -1, -1):
+        for l in range(Dt - 1, first - 1, -1):
             n, n_in, p_in = tu[l], (tu[l - 1] if l else H), (pt[l - 1] if l else pm)
             inp = tacts[l - 1] if l else mixed
             dW, db = torch.empty(K, pt[l], p4(n_in), **f32), torch.empty(K, pt[l], **f32)
@@ -1887,7 +1891,9 @@ def mtl_tower_backward(K, H, tu, B, tacts, mixed, probs, towers, scale, d_mixed,
             for k in range(K):
                 hidden_grads[k][l] = (dW[k], db[k])
             add = l == 0 and d_mixed is not None
-            d_in = incoming() if add else new(B, K * p_in, **f32)
+            # (dz_0 of first=1 is read whole by the stacked layer-0 products: its pad columns must be zero)
+            fill = torch.zeros if first and l == first and p_in != n_in else new
+            d_in = incoming() if add else fill(B, K * p_in, **f32)
             ws_ = [towers[k][0][l][0] for k in range(K)]
             gemm_grouped(False, True, B, n_in, n, [fptr(dz, k * pt[l]) for k in range(K)], K * pt[l],
                          [w.data_ptr() for w in ws_], ws_[0].stride(0), [fptr(d_in, k * p_in) for k in range(K)],
@@ -2619,3 +2625,263 @@ def _ple_autograd(x, flat, sh: PleShape, experts, gate_entries, tower_entries, h
         return [split(j) for j in range(L)] if return_levels else split(L - 1)[:2]
     logits, probs = out[2 * L], out[2 * L + 1]
     return (logits, probs, [split(j) for j in range(L)]) if return_levels else (logits, probs)
+
+
+# ---------------------------------------------------------------- ESMM (rk_esmm_forward)
+
+# argument slots of rk_esmm_forward patched per call (esmm_forward_args)
+ESMM_LOGITS_SLOT, ESMM_PROBS_SLOT, ESMM_COND_SLOT = 9, 10, 11
+
+
+def esmm_forward_args(segs, width, batch, towers, heads, device, *, logits=None, probs=None, cond=None):
+    """The rk_esmm_forward argument list (the stream last, None) and the ctypes arrays it points into.
+    towers: K stacks of equal depth, each a list of (pack_mlp_weight image, bias or None, n, act); heads: K
+    (w [last width], b [1]).  logits [9], probs [10], cond [11] and the stream [-1] are the per-call slots
+    of a cached forward."""
+    _lib.ensure_device(device)
+    arr = _as_seg_array(segs)
+    K = len(towers)
+    depth = len(towers[0]) if towers else 0
+    if any(len(s) != depth for s in towers):
+        raise ValueError("rankops.esmm: every tower must have the same number of layers")
+    if len(heads) != K:
+        raise ValueError(f"rankops.esmm: {K} towers need {K} heads")
+    tw = _mmoe_layer_array(towers)
+    hw = (ctypes.c_void_p * max(1, K))(*[w.data_ptr() for w, _ in heads])
+    hb = (ctypes.c_void_p * max(1, K))(*[b.data_ptr() for _, b in heads])
+    args = [arr, len(arr), width, batch, tw, K, depth, hw, hb, ptr(logits), ptr(probs), ptr(cond), None]
+    return args, (arr, tw, hw, hb)
+
+
+class EsmmShape:
+    """Widths of one ESMM: the row and K towers of units tu."""
+
+    def __init__(self, width, K, tu):
+        self.width, self.K, self.tu = width, K, tuple(tu)
+
+
+def esmm_stacked_weight(sh: EsmmShape, towers):
+    """[W_{0,0}; …; W_{K-1,0}] as one [K p4(n_0), p4(width)] matrix (rows and columns on the 4 grid, zeros
+    between): layer 0 of every tower reads the same x, so their data gradient is one GEMM against it and
+    their weight gradients one product (as mmoe_stacked_weight)."""
+    first = [hidden[0][0].detach() for hidden, _ in towers]
+    pad = torch.nn.functional.pad
+    n0, cols = sh.tu[0], p4(sh.width) - sh.width
+    if n0 % 4 == 0:
+        out = torch.cat(first, 0)
+        return pad(out, (0, cols)) if cols else out
+    return pad(torch.stack(first, 0), (0, cols, 0, p4(n0) - n0)).view(sh.K * p4(n0), p4(sh.width))
+
+
+def esmm_forward_train(segs, sh: EsmmShape, B, tstacks, heads, device, p, seed, slot):
+    """rk_esmm_forward_train: one launch; returns the saved buffers (include/rankops.h) as a dict."""
+    f32 = dict(device=device, dtype=torch.float32)
+    K = sh.K
+    s = dict(x=torch.empty(B, p4(sh.width), **f32), tacts=[torch.empty(B, K * p4(n), **f32) for n in sh.tu],
+             logits=torch.empty(B, K, **f32), probs=torch.empty(B, K, **f32), cond=torch.empty(B, K, **f32))
+    if B == 0:
+        return s
+    args, keep = esmm_forward_args(segs, sh.width, B, tstacks, heads, device)
+    ta = _ptrs([t.data_ptr() for t in s["tacts"]])
+    call = args[:9] + [float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(slot), s["x"].data_ptr(), ta, s["logits"].data_ptr(),
+                       s["probs"].data_ptr(), s["cond"].data_ptr(), _lib.raw_stream(device)]
+    check(_lib.load().rk_esmm_forward_train(*call), "rk_esmm_forward_train")
+    return s
+
+
+def esmm_joint_backward(logits, d_logits, d_probs, d_cond, stream):
+    """rk_esmm_joint_backward over contiguous [B, K] tensors (each incoming gradient may be None, not all):
+    the gradient at the conditional logits, [B, K]."""
+    B, K = logits.shape
+    g = torch.empty(B, K, device=logits.device, dtype=torch.float32)
+    check(_lib.load().rk_esmm_joint_backward(logits.data_ptr(), logits.stride(0), ptr(d_logits), ptr(d_probs),
+                                             ptr(d_cond), K, B, K, g.data_ptr(), K, stream), "rk_esmm_joint_backward")
+    return g
+
+
+def esmm_backward(sh: EsmmShape, B, s, wst, towers, p, d_logits, d_probs, d_cond, need_dx, device):
+    """The ESMM backward from the buffers of esmm_forward_train (s), the stacked layer-0 weight (wst) and
+    the plain weights (towers: K (hidden [(W, b)…], (w, b))).  d_logits, d_probs, d_cond [B, K]: the incoming
+    gradients, each may be None (not all).  Returns (dx [B, width] or None, tower grads [([(dW, db)…],
+    (dw, db))…]); a db is returned for every layer.  The launches do not depend on K:
+    rk_esmm_joint_backward; the heads and the layers above the first as mtl_tower_backward runs them for
+    MMoE and PLE; layer 0 of all towers as one rk_gemm_wgrad against x and one rk_gemm against the stacked
+    weight.  No float atomics, fixed-order sums."""
+    K, width = sh.K, sh.width
+    n0, p0, w4 = sh.tu[0], p4(sh.tu[0]), p4(width)
+    st = _lib.raw_stream(device)
+    g = esmm_joint_backward(s["logits"], d_logits, d_probs, d_cond, st)
+    dz0, tower_grads = mtl_tower_backward(K, width, sh.tu, B, s["tacts"], None, None, towers, 1.0 / (1.0 - p), None, g,
+                                          None, device, st, first=1)
+    dWs, dbs = _wgrad(B, K * p0, w4, dz0, K * p0, s["x"], w4, device, st)
+    dW0 = dWs.view(K, p0, w4)[:, :n0, :width].contiguous()   # one cut for all towers
+    db0 = dbs.view(K, p0)[:, :n0].contiguous()
+    for k in range(K):
+        tower_grads[k][0][0] = (dW0[k], db0[k])
+    dx = None
+    if need_dx:
+        dx = torch.empty(B, width, device=device, dtype=torch.float32)
+        gemm(False, True, B, width, K * p0, dz0, K * p0, wst, wst.stride(0), dx, split=1)
+    return dx, tower_grads
+
+
+def esmm_flat_grads(sh: EsmmShape, tower_grads):
+    """tower grads in the order tower-major: every hidden (dW, db), then the head's (dw, db)."""
+    out = []
+    for hidden, head in tower_grads:
+        for wb in hidden:
+            out += list(wb)
+        out += list(head)
+    return out
+
+
+class _EsmmFn(torch.autograd.Function):
+    """rankops.esmm with autograd: rk_esmm_forward_train without dropout, esmm_backward.  Inputs after the
+    fixed arguments: x, then per tower every hidden (W, b) and the output (w, b) (None for an absent bias)."""
+
+    @staticmethod
+    def forward(ctx, sh, launch, x, *flat):
+        s = launch()
+        ctx.sh, ctx.s, ctx.flat, ctx.B = sh, s, flat, x.shape[0]
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
+        return s["probs"], s["logits"], s["cond"]
+
+    @staticmethod
+    def backward(ctx, d_probs, d_logits, d_cond):
+        sh, s, flat, B = ctx.sh, ctx.s, ctx.flat, ctx.B
+        towers, wst = s["weights"]
+        dev = s["x"].device
+        if B == 0 or (d_probs is None and d_logits is None and d_cond is None):
+            return (None, None, torch.zeros(B, sh.width, device=dev)) + tuple(
+                None if t is None else torch.zeros_like(t) for t in flat)
+        like = lambda g: None if g is None else g.to(torch.float32).reshape(B, sh.K).contiguous()
+        dx, tg = esmm_backward(sh, B, s, wst, towers, 0.0, like(d_logits), like(d_probs), like(d_cond),
+                               ctx.needs_input_grad[2], dev)
+        out = esmm_flat_grads(sh, tg)
+        return (None, None, dx, *[None if t is None else g.reshape(t.shape) for t, g in zip(flat, out)])
+
+
+def esmm(x: torch.Tensor, towers, return_conditional: bool = False):
+    """The entire-space multi-task forward on rows x [B, width] (float32, unit column stride, any row
+    stride >= width), in one launch (rk_esmm_forward):
+
+        logit_k = towers[k](x)          towers: K (hidden [(W, b)…], (w_out [1, ·], b_out)), hidden layers
+                                        Linear + ReLU, 1..3 of them; a bias may be None
+        cond_k  = sigmoid(logit_k)      prob_k = cond_0 … cond_k  (k ascending)
+
+    Returns (probs [B, K], logits [B, K]), with return_conditional also cond [B, K].  Differentiable
+    whenever x or any weight or bias requires grad (rk_esmm_forward_train without dropout and
+    esmm_backward): gradients for x and every (W, b) from the incoming gradients of
+    probs, logits and cond.  With nothing requiring grad the call is the eval launch, bit for bit."""
+    as_f32(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"rankops.esmm: x must be [B, width] with unit column stride, got {tuple(x.shape)}")
+    B, width = x.shape
+    dev = x.device
+    K = len(towers)
+    if K == 0:
+        raise ValueError("rankops.esmm: at least two towers")
+    tstacks, heads, zero = [], [], None
+    for k, (hidden, (w_out, b_out)) in enumerate(towers):
+        st, last = _mmoe_stack(hidden, width, f"tower {k}", B > 0)
+        as_f32(w_out, f"tower {k} output weight")
+        if w_out.numel() != last or (b_out is not None and as_f32(b_out, f"tower {k} output bias").numel() != 1):
+            raise ValueError(f"rankops.esmm: tower {k} output must be (w [1, {last}], b [1] or None)")
+        if b_out is None:
+            zero = torch.zeros(1, device=dev, dtype=torch.float32) if zero is None else zero
+        tstacks.append(st)
+        heads.append((w_out.detach().reshape(-1).contiguous(), zero if b_out is None else b_out.detach().reshape(1)))
+    flat = [t for hidden, out in towers for wb in list(hidden) + [out] for t in wb]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x] + flat):
+        tu = [w.shape[0] for w, _ in towers[0][0]]
+        if len(tu) == 0 or any([w.shape[0] for w, _ in hidden] != tu for hidden, _ in towers):
+            raise ValueError("rankops.esmm: with autograd all towers must have the same, non-empty widths")
+        sh = EsmmShape(width, K, tu)
+        dtow = [([(w.detach(), b) for w, b in hidden], (wo.detach().reshape(-1), bo)) for hidden, (wo, bo) in towers]
+        wst = esmm_stacked_weight(sh, dtow) if B > 0 else None  # (an empty batch launches nothing)
+        segs = [dense_segment(x.detach(), min(128, width - c), c, c) for c in range(0, width, 128)]
+
+        def launch():
+            s = esmm_forward_train(segs, sh, B, tstacks, heads, dev, 0.0, 0, None)
+            s["weights"] = (dtow, wst)
+            return s
+        probs, logits, cond = _EsmmFn.apply(sh, launch, x, *flat)
+        return (probs, logits, cond) if return_conditional else (probs, logits)
+    f32 = dict(device=dev, dtype=torch.float32)
+    probs, logits = torch.empty(B, K, **f32), torch.empty(B, K, **f32)
+    cond = torch.empty(B, K, **f32) if return_conditional else None
+    if B > 0:
+        # (a segment holds at most 255 columns: the kernel's column map is one byte per column)
+        segs = [dense_segment(x, min(128, width - c), c, c) for c in range(0, width, 128)]
+        args, _keep = esmm_forward_args(segs, width, B, tstacks, heads, dev, logits=logits, probs=probs, cond=cond)
+        args[-1] = _lib.raw_stream(dev)
+        check(_lib.load().rk_esmm_forward(*args), "rk_esmm_forward")
+    return (probs, logits, cond) if return_conditional else (probs, logits)
+
+
+def esmm_loss_launch(logits, labels, weights, loss, per_task, dlogits):
+    """rk_esmm_loss over logits / labels [B, K] (unit column stride, any row stride); weights: K floats or
+    None; loss [1], per_task [K], dlogits [B, K] or None."""
+    B, K = logits.shape
+    lib = _lib.load()
+    dev = logits.device
+    _lib.ensure_device(dev)
+    nws = lib.rk_esmm_loss_workspace_floats(B)
+    ws = torch.empty(nws, device=dev, dtype=torch.float32)
+    w = (ctypes.c_float * K)(*[float(v) for v in weights]) if weights is not None else None
+    check(lib.rk_esmm_loss(logits.data_ptr(), logits.stride(0) if B else K, labels.data_ptr(),
+                           labels.stride(0) if B else K, B, K, w, ptr(loss), ptr(per_task), ptr(dlogits),
+                           dlogits.stride(0) if dlogits is not None and B else K, ws.data_ptr(), nws,
+                           _lib.raw_stream(dev)), "rk_esmm_loss")
+
+
+class _EsmmLossFn(torch.autograd.Function):
+    """rankops.esmm_loss: the forward launches rk_esmm_loss with the analytic gradient, the backward is
+    grad_out * dlogits.  The per-task means are returned detached."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weights):
+        B, K = logits.shape
+        f32 = dict(device=logits.device, dtype=torch.float32)
+        loss, per_task = torch.empty((), **f32), torch.empty(K, **f32)
+        dlogits = torch.empty(B, K, **f32) if ctx.needs_input_grad[0] else None
+        esmm_loss_launch(logits, labels, weights, loss, per_task, dlogits)
+        ctx.dlogits = dlogits
+        ctx.mark_non_differentiable(per_task)
+        return loss, per_task
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_per_task):
+        if ctx.dlogits is None or grad_loss is None:
+            return None, None, None
+        return grad_loss.to(torch.float32) * ctx.dlogits, None, None
+
+
+def esmm_loss(logits: torch.Tensor, labels: torch.Tensor, task_weights=None, return_per_task: bool = False):
+    """ESMM's entire-space loss, fused with its analytic gradient (rk_esmm_loss):
+
+        (1 / B) sum_b [ w_0 BCE(sigmoid(z_0), y_0) + sum_{k >= 1} w_k BCE(sigmoid(z_0) … sigmoid(z_k), y_k) ]
+
+    over conditional logits z [B, K] (any model's, when its tasks are nested events) and the joint events'
+    labels y [B, K] in [0, 1], computed in the log domain so that saturated logits lose nothing.
+    task_weights: K floats (default ones).  Returns the scalar loss, with return_per_task also the K
+    unweighted per-task means (detached).  Differentiable in logits; capturable in a hipGraph."""
+    as_f32(logits, "logits")
+    require_gpu(labels, "labels")
+    if logits.dim() != 2 or labels.shape != logits.shape:
+        raise ValueError(f"rankops.esmm_loss: logits and labels must both be [B, K], got {tuple(logits.shape)} and "
+                         f"{tuple(labels.shape)}")
+    K = logits.shape[1]
+    if not 1 <= K <= 8:
+        raise ValueError(f"rankops.esmm_loss: 1..8 tasks, got {K}")
+    if task_weights is not None:
+        task_weights = tuple(float(v) for v in task_weights)
+        if len(task_weights) != K:
+            raise ValueError(f"rankops.esmm_loss: task_weights must hold {K} values, got {len(task_weights)}")
+    labels = labels.detach().to(torch.float32)
+    if logits.shape[0] and logits.stride(1) != 1:
+        logits = logits.contiguous()
+    if labels.shape[0] and labels.stride(1) != 1:
+        labels = labels.contiguous()
+    loss, per_task = _EsmmLossFn.apply(logits, labels, task_weights)
+    return (loss, per_task) if return_per_task else loss

@@ -749,7 +749,7 @@ class _MMoETrain(torch.autograd.Function):
 
 
 class _MultiTaskEmpty(torch.autograd.Function):
-    """A multi-task model's (MMoE, PLE) train forward over an empty batch: empty outputs attached to the parameters, whose
+    """A multi-task model's (MMoE, PLE, ESMM) train forward over an empty batch: empty outputs attached to the parameters, whose
     gradients are zeros (what the reference's loop gets from autograd); no kernel of the engine runs."""
 
     @staticmethod
@@ -780,11 +780,12 @@ def _mmoe_params(model, names):
 
 
 def multitask_train_forward(model, dense, names, idx, grad: bool = True):
-    """Train-mode forward of a multi-task model (MMoE, PLE): (probabilities [B, K], logits [B, K]) attached
+    """Train-mode forward of a multi-task model (MMoE, PLE, ESMM): (probabilities [B, K], logits [B, K]) attached
     to the model's autograd function when `grad`; otherwise the same launches with nothing kept.  An empty
     batch returns empty outputs (attached, with zero gradients, when `grad`) without running the engine."""
     front, fn, params = {"MMoE": (_mmoe_front, _MMoETrain, _mmoe_params),
-                         "PLE": (_ple_front, _PLETrain, _ple_params)}[model.NAME]
+                         "PLE": (_ple_front, _PLETrain, _ple_params),
+                         "ESMM": (_esmm_front, _ESMMTrain, _esmm_params)}[model.NAME]
     if dense.shape[0] == 0:
         if not grad:
             return common.empty_rows(dense.device, 2, (0, len(model.task_names)))
@@ -891,6 +892,89 @@ def _ple_params(model, names):
     for seq, o in zip(model.towers, model.tower_outputs):
         for l in lin(seq):
             params += [l.weight, l.bias]
+        params += [o.weight, o.bias]
+    return params
+
+
+# ---------------------------------------------------------------- ESMM
+
+def _esmm_front(model, dense, names, idx):
+    """The train forward, as _mmoe_front: every image the kernel reads repacked on the stream into the
+    model's own buffers (one rk_mlp_pack_weights for all of them, one torch.cat for the stacked layer-0
+    weight; a hipGraph replay follows the optimizer), the dropout stream advanced (rk_rng_next), then
+    rk_esmm_forward_train.  Returns (shape, saved buffers)."""
+    B, dev = dense.shape[0], dense.device
+    lin = model._linears
+    sh = ops.EsmmShape(model.input_dim, len(model.task_names), model.tower_hidden_units)
+    towers = [([(l.weight.detach(), l.bias) for l in lin(seq)], (o.weight.detach().reshape(-1), o.bias))
+              for seq, o in zip(model.towers, model.tower_outputs)]
+    wst = ops.esmm_stacked_weight(sh, towers)
+    own = model.__dict__.setdefault("_train_images", {})
+    if own.get("device") != dev:
+        own.clear()
+        own["device"] = dev
+    pairs, tstacks = [], []
+
+    def image(key, w):
+        img = own.get(key)
+        if img is None:
+            img = own[key] = ops.mlp_image(w.shape[0], w.shape[1], dev)
+        pairs.append((w, img))
+        return img
+    for k, (hidden, _) in enumerate(towers):
+        tstacks.append([(image(("t", k, l), w), b, w.shape[0], "relu") for l, (w, b) in enumerate(hidden)])
+    ops.pack_mlp_weights(pairs, ops._lib.raw_stream(dev))
+    p = float(model.dropout_rate)
+    seed, slot = 0, None
+    if p > 0:
+        seed, slot = model.__dict__.setdefault("_dropout", DropoutStreams()).next(dev)
+    heads = [(w, b) for _, (w, b) in towers]
+    s = ops.esmm_forward_train(model._segments(dense, names, idx), sh, B, tstacks, heads, dev, p, seed, slot)
+    s["weights"] = (towers, wst)
+    s["dropout"] = (seed, slot)
+    return sh, s
+
+
+class _ESMMTrain(torch.autograd.Function):
+    """ESMM forward + backward in train mode: rk_esmm_forward_train (one launch: the gather, the towers with
+    dropout, the heads and the chain, every activation kept), then ops.esmm_backward (the fold onto the
+    logits, the heads, the towers grouped over the tasks, the stacked layer 0: a fixed number of launches
+    whatever K) and the embedding gradients.  Inputs after the fixed arguments: the tables, then every
+    tower Linear's (weight, bias) tower-major, the output layers'."""
+
+    @staticmethod
+    def forward(ctx, model, dense, names, idx, *params):
+        sh, s = _esmm_front(model, dense, names, idx)
+        ctx.model, ctx.sh, ctx.s, ctx.names, ctx.idx, ctx.B = model, sh, s, names, idx, dense.shape[0]
+        ctx.set_materialize_grads(False)
+        return s["probs"], s["logits"]
+
+    @staticmethod
+    def backward(ctx, dprob, dlogit):
+        model, sh, s, B = ctx.model, ctx.sh, ctx.s, ctx.B
+        dev = s["x"].device
+        towers, wst = s["weights"]
+        if dprob is None and dlogit is None:
+            dlogit = torch.zeros(B, sh.K, device=dev, dtype=torch.float32)
+        dx, tg = ops.esmm_backward(sh, B, s, wst, towers, float(model.dropout_rate), _grad_out(dlogit, s["logits"]),
+                                   _grad_out(dprob, s["probs"]), None, True, dev)
+        tables = [model.embeddings[n].weight for n in ctx.names]
+        out = list(embedding_grads(tables, ctx.idx, model.num_dense_features, dx, sparse=model.sparse_grad))
+        for k in range(sh.K):
+            for l in range(len(sh.tu)):
+                out += list(tg[k][0][l])
+        for k in range(sh.K):
+            out += [tg[k][1][0], tg[k][1][1]]
+        return (None, None, None, None, *out)
+
+
+def _esmm_params(model, names):
+    lin = model._linears
+    params = [model.embeddings[n].weight for n in names]
+    for seq in model.towers:
+        for l in lin(seq):
+            params += [l.weight, l.bias]
+    for o in model.tower_outputs:
         params += [o.weight, o.bias]
     return params
 

@@ -57,6 +57,8 @@
  *                      (the reference lists the model, its script is not in the snapshot)
  *   rk_ple_forward     PLE (progressive layered extraction) eval forward in one launch: row gather, L
  *                      levels of task / shared experts and gates, towers, heads
+ *   rk_esmm_forward    ESMM (entire space multi-task model) eval forward in one launch: row gather once
+ *                      for all towers, towers, heads, the chain of probabilities
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
  *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
  *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
@@ -68,6 +70,9 @@
  *   rk_mmoe_forward_train, rk_mmoe_mix_backward, rk_mmoe_head_backward   MMoE training
  *   rk_ple_forward_train, rk_ple_mix_backward   PLE training: the train form of the one-launch forward
  *                      and the backward of one level's mixtures and gates ("Training")
+ *   rk_esmm_forward_train, rk_esmm_loss, rk_esmm_joint_backward   ESMM training: the train form of the
+ *                      one-launch forward, the entire-space loss with its analytic gradient, and the
+ *                      fold of gradients at the joint probabilities onto the logits
  *   rk_logit_head_backward  output_layer + sigmoid backward      dcn.py:177-179
  *   rk_dcn_cross_backward   cross_layer backward w.r.t. x0        dcn.py:46-49
  *   rk_relu_backward   ReLU backward (residual_unit's outer ReLU) deepcrossing.py:41
@@ -841,6 +846,74 @@ int rk_mmoe_head_backward(int64_t batch, int32_t num_tasks, int32_t n, int32_t p
                           const float* dprobs, const float* probs, const float* const* head_w, const float* t,
                           float mask_scale, float* g_out, int32_t ld_g, float* dt, int32_t accumulate,
                           void* stream);
+
+/* ---- ESMM: entire space multi-task model (Ma et al., SIGIR 2018) ---- */
+/* The whole ESMM eval forward in one launch.  Per row b, with x = the `width` columns gathered from
+ * segs (rk_mmoe_forward's column map; out-of-range ids read zero rows and raise RK_FLAG_INDEX_OOB),
+ * gathered once for all towers:
+ *   logit_k = towers[k](x) . head_w[k] + head_b[k][0]    towers[k * tower_depth + l], l = 0 .. tower_depth - 1,
+ *                                                        every tower reads the same x; head_w[k] [last width]
+ *   cond_k  = sigmoid(logit_k)                           the conditional probability (pCTR, pCVR, ...)
+ *   prob_k  = cond_0 cond_1 ... cond_k                   k ascending, FP32: the entire-space probability
+ * Outputs, each may be NULL but not all: logits, probs, cond [batch, num_tasks], contiguous.  No tower
+ * activation reaches memory; two launches give the same bits.
+ * Envelope: nseg <= 16 segments of at most 255 columns each, width <= 256, 2 <= num_tasks <= 8,
+ * 1 <= tower_depth <= 3, every n <= 512, activations none / ReLU (else RK_ERR_UNSUPPORTED); NULL or
+ * shape errors, no output and batch < 0: RK_ERR_INVALID; both before any launch.  batch == 0: RK_OK,
+ * no launch.                                                                                      */
+int rk_esmm_forward(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                    const rk_mmoe_layer* towers, int32_t num_tasks, int32_t tower_depth,
+                    const float* const* head_w, const float* const* head_b, float* logits, float* probs,
+                    float* cond, void* stream);
+
+/* rk_esmm_forward in train mode, still one launch: dropout (probability dropout_p in [0, 1), scale
+ * 1 / (1 - p)) behind every ReLU, and what the backward reads kept.  Every hidden layer must be ReLU and
+ * all towers must have the same widths layer by layer.  Dropout site s = k * tower_depth + l for tower k
+ * layer l; element (b, j) of a site's [batch, n] output is kept iff the counter hash of
+ * rk_dropout_mask(seed + s, stream_slot, ...) keeps element b * n + j (stream_slot may be NULL when
+ * dropout_p == 0).  Saved buffers (16-B aligned, p4 as in rk_mmoe_forward_train):
+ *   x_out          [batch, p4(width)]               the gathered rows, zeros past the width
+ *   tower_acts[l]  [batch, num_tasks * p4(n_l)]     tower k's layer l (after ReLU and dropout) at columns
+ *                                                   k * p4(n_l), zeros up to the pitch:
+ *                                                   rk_mmoe_forward_train's tower_acts layout
+ * With dropout_p == 0 the outputs have rk_esmm_forward's bits.  Errors and envelope as rk_esmm_forward. */
+int rk_esmm_forward_train(const rk_segment* segs, int32_t nseg, int32_t width, int64_t batch,
+                          const rk_mmoe_layer* towers, int32_t num_tasks, int32_t tower_depth,
+                          const float* const* head_w, const float* const* head_b, double dropout_p, uint64_t seed,
+                          const int64_t* stream_slot, float* x_out, float* const* tower_acts, float* logits,
+                          float* probs, float* cond, void* stream);
+
+/* The entire-space loss and its gradient.  logits [batch, num_tasks] (row stride ld_logits) are the
+ * conditional logits z, labels [batch, num_tasks] (row stride ld_labels, floats in [0, 1]) the labels of
+ * the joint events (click; click and conversion; ...), task_weights a HOST array w [num_tasks] or NULL
+ * (ones).  With ls_j = logsigmoid(z_j) and S_k = ls_0 + ... + ls_k (= log prob_k):
+ *   L_0 = softplus(-z_0) y_0 + softplus(z_0) (1 - y_0)
+ *   L_k = -(y_k S_k + (1 - y_k) log1mexp(S_k)),  k >= 1;  log1mexp(s) = log(-expm1(s)) for s > -ln 2,
+ *                                                          else log1p(-exp(s))
+ *   loss[0]     = (1 / batch) sum_b sum_k w_k L_k                        (device scalar)
+ *   per_task[k] = (1 / batch) sum_b L_k                                  (device [num_tasks], unweighted)
+ *   dlogits[b * ld_dlogits + j] = d loss / d z_j
+ *     = ([j == 0] (sigmoid(z_0) - y_0) w_0 + sigmoid(-z_j) sum_{k >= max(j, 1)} w_k ((1 - y_k) / expm1(-S_k) - y_k)) / batch
+ * S_k is clamped to at most -FLT_MIN where it is the argument of expm1 or log1mexp, so every output is
+ * finite for every finite logit.  Each of loss, per_task, dlogits may be NULL, not all.  Sums run in a
+ * fixed order without atomics (a second, one-workgroup launch adds the workgroups' sums): two runs give
+ * the same bits.  workspace: rk_esmm_loss_workspace_floats(batch) device floats.  batch == 0: loss and
+ * per_task are written as 0.  num_tasks <= 8 (RK_ERR_UNSUPPORTED); NULL, a leading dimension below
+ * num_tasks, a short workspace: RK_ERR_INVALID.                                                    */
+int64_t rk_esmm_loss_workspace_floats(int64_t batch);
+int rk_esmm_loss(const float* logits, int64_t ld_logits, const float* labels, int64_t ld_labels, int64_t batch,
+                 int32_t num_tasks, const float* task_weights, float* loss, float* per_task, float* dlogits,
+                 int64_t ld_dlogits, float* workspace, int64_t workspace_floats, void* stream);
+
+/* Folds the gradients arriving at rk_esmm_forward's outputs onto the conditional logits, one launch:
+ *   g[b * ld_g + j] = dlogits_j + s(z_j) s(-z_j) dcond_j + s(-z_j) sum_{k >= j} dprobs_k prob_k
+ * with s = sigmoid and prob_k recomputed from logits [batch, num_tasks] (row stride ld_logits); no
+ * division by a probability.  dlogits, dprobs, dcond [batch, num_tasks] (row stride ld_in) may each be
+ * NULL, not all.  g then enters rk_mmoe_head_backward as its dlogits (dprobs = NULL).  num_tasks <= 8
+ * (RK_ERR_UNSUPPORTED); NULL / size errors: RK_ERR_INVALID.  batch == 0: RK_OK, no launch.       */
+int rk_esmm_joint_backward(const float* logits, int64_t ld_logits, const float* dlogits, const float* dprobs,
+                           const float* dcond, int64_t ld_in, int64_t batch, int32_t num_tasks, float* g,
+                           int64_t ld_g, void* stream);
 
 /* ---- PLE: progressive layered extraction (Tang et al., RecSys 2020), eval forward ---- */
 /* The whole PLE eval forward in one launch.  L = num_levels, K = num_tasks, ms = num_specific, mc =

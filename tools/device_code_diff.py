@@ -9,8 +9,10 @@ mlp_stream.h / mtl_core.h) is compiled in each tree with the flags that tree's c
 objects (read from `make -n`), plus --offload-device-only --no-gpu-bundle-output, at most 16
 compiles at once.  One line per file: `identical` when the two device ELFs have the same sha256,
 otherwise the __global__ kernels whose instruction stream (llvm-objdump -d, addresses and encodings
-stripped) or metadata (llvm-readelf --notes) differs, and the kernels added or missing.  The exit
-status is non-zero unless every file is identical.  Host only: needs hipcc, no GPU.
+stripped) or metadata (llvm-readelf --notes) differs, and the kernels added or missing.  A file that
+only one of the trees has (a translation unit added or removed between them) is reported as such and
+compared with nothing.  The exit status is non-zero unless every file both trees have is identical.
+Host only: needs hipcc, no GPU.
 """
 import argparse
 import concurrent.futures
@@ -24,7 +26,7 @@ import sys
 import tempfile
 
 DEFAULT_FILES = ["mlp.hip", "din_fused.hip", "deepfm_fused.hip", "bst_small.hip", "dien_forward.hip",
-                 "linear_tiled.hip", "afm.hip", "mmoe.hip", "ple.hip"]
+                 "linear_tiled.hip", "afm.hip", "mmoe.hip", "ple.hip", "esmm.hip"]
 DEVICE_ONLY = ["--offload-device-only", "--no-gpu-bundle-output"]
 # per-kernel metadata named in a report (any other difference in the kernel's note is "other")
 META_KEYS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size",
@@ -155,6 +157,8 @@ def main():
             csrc = find_csrc(materialise(rev, repo, tmp, side))
             os.makedirs(os.path.join(csrc, ELF_DIR))
             for name in names:
+                if not os.path.isfile(os.path.join(csrc, name)):
+                    continue
                 elf = os.path.join(ELF_DIR, name + ".elf")  # relative to csrc, the same in both trees
                 argv = compile_command(csrc, name, elf)
                 llvm_bin = llvm_bin or os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(argv[0]))), "llvm", "bin")
@@ -174,6 +178,10 @@ def main():
         all_same = True
         elf = {(side, name): path for side, name, _, _, path in jobs}
         for name in names:
+            if (0, name) not in elf or (1, name) not in elf:
+                have = [t for i, t in enumerate("AB") if (i, name) in elf]
+                print(f"{name}: only in tree {have[0]}" if have else f"{name}: in neither tree", flush=True)
+                continue
             same, line = compare(name, elf[0, name], elf[1, name], llvm_bin)
             all_same &= same
             print(line, flush=True)
