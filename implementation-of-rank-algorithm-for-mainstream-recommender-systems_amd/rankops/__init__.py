@@ -37,6 +37,12 @@ hand-written HIP kernels (gfx950) through the C ABI in include/rankops.h:
                                            Linear backwards); esmm_loss is the entire-space loss in the log
                                            domain with its analytic gradient (rk_esmm_loss)
 
+    FiBiNET, fibinet_interaction           FiBiNET (listed in the reference's README, no script in the
+                                           snapshot): SENET field attention and the bilinear interaction,
+                                           the whole eval forward in one launch (rk_fibinet_forward);
+                                           fibinet_interaction is the interaction alone on plain tensors
+                                           (rk_fibinet_interaction); eval only
+
 `rankops.sharded.ShardedDeepFM` adds the table-sharded multi-GPU DeepFM lookup (RCCL
 all-to-all); `rankops.loader` (Vocabulary, BatchAssembler, wechat_vocabularies) replaces the
 reference's Dataset bucketing + collate with C++ column bucketing and one H2D copy per batch;
@@ -59,6 +65,7 @@ from .deepfm import DeepFM  # noqa: F401
 from .din import DIN, Dice, din_attention, din_attention_gather  # noqa: F401
 from .dien import (DIEN, DIENInterests, dien_aux_loss, dien_aux_loss_gather, dien_evolve, dien_extract,  # noqa: F401
                    dien_extract_gather, dien_interest, dien_interest_gather)
+from .fibinet import FiBiNET  # noqa: F401
 from .fwfm import FwFM  # noqa: F401
 from .loader import BatchAssembler, Vocabulary, label_encode, wechat_vocabularies  # noqa: F401
 from . import mmoe  # noqa: F401  (callable: rankops.mmoe(x, experts, gates, towers=None))
@@ -70,7 +77,7 @@ from .esmm import ESMM  # noqa: F401
 from .ops import esmm_loss  # noqa: F401
 from .metrics import EvalAccumulator, roc_auc  # noqa: F401
 from .ranking import GroupedAUC, GroupTable, RequestTopK, grouped_auc, topk_per_request, topk_segments  # noqa: F401
-from .ops import cin  # noqa: F401
+from .ops import cin, fibinet_interaction  # noqa: F401
 from .train import Adam, SparseAdam  # noqa: F401
 from .xdeepfm import XDeepFM  # noqa: F401
 
@@ -80,5 +87,5 @@ __all__ = [
     "error_flags", "load_library", "residual_unit", "wechat_vocabularies", "EvalAccumulator", "roc_auc",
     "label_encode", "Adam", "DIEN", "dien_interest", "dien_interest_gather",
     "dien_aux_loss", "dien_aux_loss_gather", "dien_extract", "dien_extract_gather", "dien_evolve", "DIENInterests",
-    "SparseAdam", "XDeepFM", "cin", "MMoE", "mmoe", "PLE", "ple", "ESMM", "esmm", "esmm_loss", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
+    "SparseAdam", "XDeepFM", "cin", "FiBiNET", "fibinet_interaction", "MMoE", "mmoe", "PLE", "ple", "ESMM", "esmm", "esmm_loss", "RequestTopK", "GroupedAUC", "GroupTable", "topk_segments", "topk_per_request", "grouped_auc",
 ]

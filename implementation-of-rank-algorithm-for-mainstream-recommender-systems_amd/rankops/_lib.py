@@ -475,6 +475,12 @@ SIGNATURES = {
                                              POINTER(c_void_p), POINTER(c_void_p), ctypes.c_double, ctypes.c_uint64,
                                              c_void_p, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
+    "rk_fibinet_interaction": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int32,
+                                              c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                              c_int64, c_void_p]),
+    "rk_fibinet_forward": (ctypes.c_int, [_SEG_P, _SEG_P, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int32,
+                                          c_void_p, c_void_p, c_int32, _MLP_P, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rk_esmm_loss_workspace_floats": (c_int64, [c_int64]),
     "rk_esmm_loss": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, POINTER(c_float), c_void_p,
                                     c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),

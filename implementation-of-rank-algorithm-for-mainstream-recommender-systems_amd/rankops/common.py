@@ -456,6 +456,10 @@ FUSED_DIEN = True  # DIEN: gather + interest recurrence + fcn tail + head in one
 # ... while the batch is at most this many 16-sample workgroups per CU (B 4096 on 256 CUs): one more
 # workgroup than that and the three launches are faster again; None: at any batch
 FUSED_DIEN_WG_PER_CU = 1
+# FiBiNET: the one rk_fibinet_forward launch while the batch is at most this many 16-sample workgroups per CU
+# (B 4096 on 256 CUs); past that rk_fibinet_interaction + the deep tail, whose streamed / tiled layers take 32-
+# and 64-row tiles, are faster; None: the one launch at any batch
+FUSED_FIBINET_WG_PER_CU = 1
 FUSED_BST = True  # BST: all transformer blocks + pooling in one rk_bst_forward_blocks launch
 FUSED_BST_FWD = True  # BST at d_model 16: row gather + blocks + pooling + DNN tail in one rk_bst_small_forward
 # A first layer this wide runs as its own 2D-tiled GEMM (rk_linear_tiled) before the fused tail:
@@ -535,6 +539,24 @@ def ple_fits(width: int, num_segments: int, num_levels: int, num_tasks: int, num
     ldh = max(64, max(_pad64(n) for n in units)) + 8
     gate_cols = K * (ms + mc) + K * ms + mc
     return 16 * (nx * ldr + 2 * ldh + 2 * (64 + 8) + gate_cols + (K + 1) * _pad64(H)) * 4 <= 160 * 1024
+
+
+def fibinet_fits(num_fields: int, dim: int, reduced: int, bilinear_type: str, hidden_units) -> bool:
+    """Whether rk_fibinet_forward takes this shape (the mirror of its envelope and LDS check,
+    csrc/fibinet.hip): 2 <= m <= 32, D a multiple of 4 in [4, 64], r <= 32, the interaction vector
+    m (m - 1) D and the 1..8 hidden layers (each <= 512) inside the fused MLP (fused_mlp_fits), one float4
+    of the 16 gathered rows per thread, and the two activation buffers, the rows, the left fields'
+    products ("all" / "each"), the SENET vectors and the first-order sums within 160 KiB of LDS."""
+    m, D, r, widths = int(num_fields), int(dim), int(reduced), list(hidden_units)
+    if not (2 <= m <= 32 and 4 <= D <= 64 and D % 4 == 0 and 1 <= r <= 32 and bilinear_type in ops.FIBINET_TYPES):
+        return False
+    k0 = m * (m - 1) * D
+    if k0 > 1024 or not fused_mlp_fits(k0, widths) or min(widths) <= 0 or 16 * m * (D // 4) > 1024:
+        return False
+    need0 = max([_pad64(k0)] + [_pad64(n) for i, n in enumerate(widths) if i % 2 == 1])
+    need1 = max([64] + [_pad64(n) for i, n in enumerate(widths) if i % 2 == 0])
+    tile = 16 * m * D + (0 if bilinear_type == "interaction" else 2 * 16 * (m - 1) * D) + 3 * 16 * 32
+    return (16 * (need0 + 8 + need1 + 8) + tile + 16) * 4 <= 160 * 1024
 
 
 class PackedWeights:

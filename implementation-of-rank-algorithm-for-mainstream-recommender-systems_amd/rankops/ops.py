@@ -298,6 +298,93 @@ def cin_forward(second, first, dim, batch, images, biases, sizes, activation, de
     check(_lib.load().rk_cin_forward(*args), "rk_cin_forward")
 
 
+FIBINET_TYPES = {"all": 0, "each": 1, "interaction": 2}  # RK_FIBINET_ALL / EACH / INTERACTION
+# argument slots of the two FiBiNET launches patched per call
+FIBINET_LINEAR_SLOT = 13                   # rk_fibinet_interaction: linear
+FIBINET_OUT_SLOTS = (20, 19, 17, 18)       # rk_fibinet_forward: prob, total_logit, linear, deep_logit
+
+
+def fibinet_matrices(num_fields: int, bilinear_type: str) -> int:
+    """How many D x D matrices each bilinear layer of this type holds."""
+    if bilinear_type not in FIBINET_TYPES:
+        raise ValueError(f"bilinear_type must be one of {sorted(FIBINET_TYPES)}, got {bilinear_type!r}")
+    m = int(num_fields)
+    return {"all": 1, "each": m - 1, "interaction": m * (m - 1) // 2}[bilinear_type]
+
+
+def _fibinet_front(second, first, dim, batch, senet_w1, senet_w2, bilinear_e, bilinear_v, bilinear_type, device):
+    _lib.ensure_device(device)
+    a2 = _as_seg_array(second)
+    a1 = _as_seg_array(first) if first is not None else None
+    return [a2, a1, len(second), dim, batch, ptr(senet_w1), ptr(senet_w2), senet_w1.shape[0], ptr(bilinear_e),
+            ptr(bilinear_v), FIBINET_TYPES[bilinear_type]], (a2, a1)
+
+
+def fibinet_interaction_args(second, first, dim, batch, senet_w1, senet_w2, bilinear_e, bilinear_v, bilinear_type, c,
+                             linear, attention, device):
+    """The rk_fibinet_interaction argument list (the stream last, None) and the ctypes arrays it points
+    into.  senet_w1 [r, m] / senet_w2 [m, r] contiguous, bilinear_e / bilinear_v the stacked contiguous
+    [nmat, D, D] weights; linear at [FIBINET_LINEAR_SLOT] is the per-call slot of a cached forward."""
+    args, keep = _fibinet_front(second, first, dim, batch, senet_w1, senet_w2, bilinear_e, bilinear_v, bilinear_type,
+                                device)
+    args += [ptr(c), c.stride(0), ptr(linear), ptr(attention), attention.stride(0) if attention is not None else 0,
+             None]
+    return args, keep
+
+
+def fibinet_forward_args(second, first, dim, batch, senet_w1, senet_w2, bilinear_e, bilinear_v, bilinear_type, layers,
+                         head_w, head_b, final_w, final_b, device):
+    """The rk_fibinet_forward argument list (the stream last, None; the four outputs at FIBINET_OUT_SLOTS
+    are per-call slots) and the ctypes arrays it points into.  layers: MlpLayer structs over packed images."""
+    args, keep = _fibinet_front(second, first, dim, batch, senet_w1, senet_w2, bilinear_e, bilinear_v, bilinear_type,
+                                device)
+    la = (_lib.MlpLayer * max(1, len(layers)))(*layers)
+    args += [la, len(layers), ptr(head_w), ptr(head_b), ptr(final_w), ptr(final_b), None, None, None, None, None]
+    return args, keep + (la,)
+
+
+def fibinet_interaction(x0: torch.Tensor, senet_w1: torch.Tensor, senet_w2: torch.Tensor, bilinear_e, bilinear_v,
+                        bilinear_type: str = "interaction", return_attention: bool = False):
+    """FiBiNET's SENET field attention and bilinear interaction over dense rows x0 [B, m, D] (any row
+    stride; field rows 16-B aligned), one launch (rk_fibinet_interaction):
+
+        z[b, i] = mean_d x0[b, i, d],  a[b, :] = relu(senet_w2 relu(senet_w1 z[b, :])),  v = a[..., None] * x0
+        p[b, (i, j), :] = (We x0[b, i, :]) * x0[b, j, :],  q[b, (i, j), :] = (Wv v[b, i, :]) * v[b, j, :]
+
+    over the pairs i < j in lexicographic order, W x = nn.Linear's x @ W.T.  senet_w1 [r, m], senet_w2
+    [m, r]; bilinear_e / bilinear_v: lists of [D, D] weights, 1 ("all"), m - 1 ("each": We = the left
+    field's) or m (m - 1) / 2 ("interaction": the pair's) of them.  Returns c [B, m (m - 1) D] = all of
+    p, then all of q; with return_attention=True also a [B, m]."""
+    as_f32(x0, "x0")
+    if x0.dim() != 3 or x0.stride(2) != 1:
+        raise ValueError(f"rankops.fibinet_interaction: x0 must be [B, m, D] with unit stride along D, got "
+                         f"{tuple(x0.shape)}")
+    B, m, D = x0.shape
+    nmat = fibinet_matrices(m, bilinear_type)
+    bilinear_e, bilinear_v = list(bilinear_e), list(bilinear_v)
+    for name, ws in (("bilinear_e", bilinear_e), ("bilinear_v", bilinear_v)):
+        if len(ws) != nmat or any(tuple(as_f32(w, name).shape) != (D, D) for w in ws):
+            raise ValueError(f"rankops.fibinet_interaction: {name} must be {nmat} weights of shape {(D, D)} for "
+                             f"bilinear_type {bilinear_type!r}")
+    as_f32(senet_w1, "senet_w1"), as_f32(senet_w2, "senet_w2")
+    r = senet_w1.shape[0]
+    if senet_w1.dim() != 2 or tuple(senet_w1.shape) != (r, m) or tuple(senet_w2.shape) != (m, r):
+        raise ValueError(f"rankops.fibinet_interaction: senet_w1 must be [r, {m}] and senet_w2 [{m}, r], got "
+                         f"{tuple(senet_w1.shape)} and {tuple(senet_w2.shape)}")
+    dev = x0.device
+    c = torch.empty(B, m * (m - 1) * D, device=dev, dtype=torch.float32)
+    attn = torch.empty(B, m, device=dev, dtype=torch.float32) if return_attention else None
+    if B > 0:
+        be = torch.stack([w.detach() for w in bilinear_e]).contiguous()
+        bv = torch.stack([w.detach() for w in bilinear_v]).contiguous()
+        w1, w2 = senet_w1.detach().contiguous(), senet_w2.detach().contiguous()
+        segs = [Segment(fptr(x0, i * x0.stride(1)), None, 0, x0.stride(0), 0, D, i * D) for i in range(m)]
+        args, _keep = fibinet_interaction_args(segs, None, D, B, w1, w2, be, bv, bilinear_type, c, None, attn, dev)
+        args[-1] = _lib.raw_stream(dev)
+        check(_lib.load().rk_fibinet_interaction(*args), "rk_fibinet_interaction")
+    return (c, attn) if return_attention else c
+
+
 def pack_cin_weight_t(weight: torch.Tensor, num_fields: int, out: torch.Tensor = None) -> torch.Tensor:
     """One CIN layer's weight ([n, hprev * num_fields] or nn.Conv1d's [n, k, 1]) -> rk_cin_pack_weight_t's
     image for rk_cin_backward: W^T, field-major, a flat num_fields * pad16(hprev) * pad16(n) tensor

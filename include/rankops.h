@@ -59,6 +59,10 @@
  *                      levels of task / shared experts and gates, towers, heads
  *   rk_esmm_forward    ESMM (entire space multi-task model) eval forward in one launch: row gather once
  *                      for all towers, towers, heads, the chain of probabilities
+ *   rk_fibinet_interaction, rk_fibinet_forward  FiBiNET: SENET field attention and the bilinear
+ *                      interaction as one launch, and the whole eval forward (row gather, first-order
+ *                      sum, SENET, both bilinear layers, deep layers, head) in one launch (the
+ *                      reference lists the model, its script is not in the snapshot)
  *   rk_eval_batch, rk_auc  evaluate(): loss / accuracy / AUC on the device  dcn.py:214-239
  *   rk_topk_segments, rk_topk_by_request, rk_grouped_auc  the best k candidates of each request and
  *                      the per-user AUC / GAUC on the device (no counterpart in the reference)
@@ -744,6 +748,51 @@ int rk_cin_forward(const rk_segment* second_order, const rk_segment* first_order
                    const int32_t* layer_sizes, int32_t num_layers, int32_t activation,
                    const float* out_w, const float* out_b, float* deep_in, int64_t ld_deep, float* fm1,
                    float* pooled, int64_t ld_pooled, float* cin_logit, void* stream);
+
+/* ---- FiBiNET: SENET field attention and the bilinear interaction (Huang et al., RecSys 2019) ---- */
+#define RK_FIBINET_ALL 0         /* one D x D matrix for every pair                          */
+#define RK_FIBINET_EACH 1        /* one per left field i < num_fields - 1                    */
+#define RK_FIBINET_INTERACTION 2 /* one per pair (i, j), i < j, pairs in lexicographic order */
+
+/* SENET and both bilinear layers in one launch.  second_order: num_fields segments of `dim` columns,
+ * all tables or all dense, rows 16-B aligned (src_ld % 4 == 0; out_col is not read);
+ * e[b, i, :] = the row of field i.  With m = num_fields, r = reduced, pair p = (i, j), i < j:
+ *   z[b, i] = mean_d e[b, i, d],  a[b, :] = relu(W2 relu(W1 z[b, :])),  v[b, i, :] = a[b, i] e[b, i, :]
+ *   c[b, p * dim + d]                 = (We e[b, i, :])[d] * e[b, j, d]
+ *   c[b, (m (m-1)/2 + p) * dim + d]   = (Wv v[b, i, :])[d] * v[b, j, d]
+ * senet_w1 [r, m] and senet_w2 [m, r] row-major (nn.Linear's weights, no bias); bilinear_e and
+ * bilinear_v: the stacked [nmat, dim, dim] row-major nn.Linear weights (W x = x . W^T), 16-B aligned,
+ * nmat = 1 / m - 1 / m (m-1)/2 and We = matrix 0 / i / p by bilinear_type.
+ * Outputs: c [batch, ldc] (required, ldc >= m (m-1) dim); linear [batch] = the sum over fields, in
+ * order, of first_order's one-column segments (may be NULL, first_order then too); attention
+ * [batch, ld_attention] = a (may be NULL).  Rows, products and attention stay in LDS; fp32 on the
+ * VALU, every sum in a fixed order (no atomics): two launches give the same bits.
+ * Envelope: 2 <= num_fields <= 32, dim a multiple of 4 in [4, 64], reduced <= 32 (else
+ * RK_ERR_UNSUPPORTED); NULL or shape errors and batch < 0: RK_ERR_INVALID; both before any launch.
+ * batch == 0: RK_OK, no launch.  Out-of-range ids read zero rows and raise RK_FLAG_INDEX_OOB.     */
+int rk_fibinet_interaction(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                           int32_t dim, int64_t batch, const float* senet_w1, const float* senet_w2,
+                           int32_t reduced, const float* bilinear_e, const float* bilinear_v,
+                           int32_t bilinear_type, float* c, int64_t ldc, float* linear, float* attention,
+                           int64_t ld_attention, void* stream);
+
+/* The whole FiBiNET eval forward in one launch: per 16-row workgroup the row gather,
+ * the first-order sum, rk_fibinet_interaction's c written straight into the MLP's LDS input row, the
+ * deep layers as rk_mlp_forward (layers packed by rk_mlp_pack_weight for K0 = m (m-1) dim; Linear,
+ * folded BatchNorm, activation), then
+ *   deep = h . head_w + head_b[0],  total = final_w[0] * linear + final_w[1] * deep + final_b[0],
+ *   prob = sigmoid(total)
+ * into linear / deep_logit / total_logit / prob [batch] (each may be NULL, not all).  first_order
+ * is required.  Envelope: rk_fibinet_interaction's, with m (m-1) dim <= 1024, 1..8 layers of n <= 512
+ * without residual or store, and the two activation buffers, the rows and the products within
+ * 160 KiB of LDS (else RK_ERR_UNSUPPORTED: rk_fibinet_interaction + rk_mlp_forward compute the same).
+ * Errors, batch == 0 and out-of-range ids as rk_fibinet_interaction.                              */
+int rk_fibinet_forward(const rk_segment* second_order, const rk_segment* first_order, int32_t num_fields,
+                       int32_t dim, int64_t batch, const float* senet_w1, const float* senet_w2,
+                       int32_t reduced, const float* bilinear_e, const float* bilinear_v,
+                       int32_t bilinear_type, const rk_mlp_layer* layers, int32_t nlayers, const float* head_w,
+                       const float* head_b, const float* final_w, const float* final_b, float* linear,
+                       float* deep_logit, float* total_logit, float* prob, void* stream);
 
 /* ---- MMoE: multi-gate mixture of experts (Ma et al., KDD 2018), eval forward ---- */
 /* One Linear (+ ReLU) of an expert or a tower: w = the rk_mlp_pack_weight image of W [n, K] (K = the
